@@ -63,6 +63,9 @@ def parse():
                     help="headline run only: do not append the secondary workloads (gow, big, stock) as child runs")
     ap.add_argument("--sub-steps", type=int, default=100, help="timed steps of the gow / stock child runs (big: a tenth)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (its loss, the trained parameters after "
+                         "AdamW) as DIR/<name>.npy, float32, at most 64 MB in all (larger arrays: a fixed seeded sample)")
     return ap.parse_args()
 
 
@@ -590,6 +593,37 @@ def time_chain(R, C, F, reps=50, p_drop=0.1):
     return _graph_time(fn, reps)
 
 
+DUMP_BYTES = 63 * 10 ** 6          # array data of --dump-outputs; the .npy headers (128 B each) stay inside 64 MB
+
+
+def dump_outputs(ts, model, out_dir, budget=DUMP_BYTES):
+    """--dump-outputs: what a caller of the timed step holds after its last step -- the loss tensor `step` returned and every
+    trained parameter as that step's AdamW left it -- as <out_dir>/<name>.npy (float32).  Parameters are named by parameter
+    (`param.<name>`), not by their place in the flat buffer, so that two builds can be compared output for output.  The flat
+    gradient buffer is the step's scratch, not an output (and its key-projection bias slices are pure round-off: exactly 0 in
+    exact arithmetic).  Over `budget` bytes the largest parameters are cut down to a sample of elements whose flat indices are
+    drawn from a generator seeded by the parameter's name and shape: the same elements in every run."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    names = {id(p): n for n, p in model.named_parameters()}
+    arrays = [("loss", ts.loss_out.detach().reshape(1))] + [("param." + names[id(p)], p.detach()) for p in ts.flat.params]
+    # budget shared smallest first: an array either fits its share whole or is sampled down to it
+    keep, left = {}, budget
+    order = sorted(range(len(arrays)), key=lambda k: arrays[k][1].numel())
+    for j, k in enumerate(order):
+        keep[k] = min(arrays[k][1].numel(), left // 4 // (len(order) - j))
+        left -= keep[k] * 4
+    sampled = []
+    for k, (name, t) in enumerate(arrays):
+        if keep[k] < t.numel():
+            rng = np.random.default_rng(zlib.crc32(f"{name}:{tuple(t.shape)}".encode()))
+            t = t.reshape(-1)[torch.from_numpy(np.sort(rng.choice(t.numel(), size=keep[k], replace=False))).to(t.device)]
+            sampled.append(name)
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    print(f"bench.py: {len(arrays)} outputs of the last timed step written to {out_dir}"
+          + (f" (sampled: {', '.join(sampled)})" if sampled else ""), file=sys.stderr)
+
+
 def usable_cores():
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     try:                                            # cgroup v2 CPU quota of the container, if any
@@ -892,6 +926,8 @@ def main():
     host_stalls = {"gc": "collected before, disabled inside the timed region", "max_step_gap_ms": round(max(gaps), 3) if gaps else 0.0,
                    "threshold_ms": round(gap_thr, 2), "gaps_over_threshold": [[i, round(g, 2)] for i, g in enumerate(gaps) if g > gap_thr][:8]}
     chunk_ms = [marks[k].elapsed_time(marks[k + 1]) / max(bounds[k + 1] - bounds[k], 1) for k in range(n_chunks)]
+    if args.dump_outputs and rank == 0:             # (before anything below steps the model again)
+        dump_outputs(ts, model, args.dump_outputs)
     loss = float(ts.loss_out.item())
     if loss != loss or abs(loss) == float("inf"):
         raise SystemExit(f"bench.py: training diverged (final loss {loss}) -- the timing would be meaningless")
