@@ -331,6 +331,23 @@ int mobgt_gather_rows_t(const void* a, int64_t ld, const int64_t* rows, void* ou
  * rank[2g+1] counts equal scores at a HIGHER index instead (the reference's reversed ascending argsort in
  * MRR_metric).  -1 for a target outside [0, V). */
 int mobgt_target_rank(const float* scores, const int64_t* target, int32_t* rank, int64_t G, int64_t V, void* stream);
+/* The same evaluation with the bookkeeping of test_epoch_end (model_fqandtoyo.py:1546-1597, metrics.evaluate_outputs) on the
+ * device, replacing get_acc's top-k (:48-90), MRR_metric's argsort (:122-131) and their per-batch host reads.  For the batch's
+ * rows g < G with class t = target[g] + target_offset, acc [10] f64 receives
+ *   += {G, hit@1, hit@5, hit@10, hit@20, dcg@1, dcg@5, dcg@10, dcg@20, sum 1 / (mrr_rank + 1)}
+ * with the positions of mobgt_target_rank (acc_rank = rank[2g], mrr_rank = rank[2g+1]); hits and DCG (gain 1 / log2(acc_rank + 2))
+ * stop at the first row whose t is 0, n and MRR count every row.  `work`: mobgt_rank_metrics_work_bytes(G, V) bytes, any
+ * contents (every byte read is written first); no state survives a call, so captured graphs replay it freely.  Not re-entrant
+ * across streams on one `work`.
+ * mobgt_rank_metrics: stored scores [G,V] f32 (toyotagraph's log_softmax, shapes the fused form does not take).
+ * mobgt_skinny_linear_rank_metrics: the scores are the classifier's logits x w^T + b (:1394), computed by the column tiles of
+ * mobgt_skinny_linear_fwd_mfma -- bit-identical logits -- and never stored; G <= 16, K % 64 == 0, K <= 448, x, w 16-byte
+ * aligned.  Three launches: the target logits, the ranking pass over w, a one-workgroup finish. */
+int64_t mobgt_rank_metrics_work_bytes(int64_t G, int64_t V);
+int mobgt_rank_metrics(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V, double* acc,
+                       void* work, void* stream);
+int mobgt_skinny_linear_rank_metrics(const float* x, const float* w, const float* b, const int64_t* target, int64_t target_offset,
+                                     int G, int K, int V, double* acc, void* work, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused elementwise / normalisation pieces of EncoderLayer.forward between the library GEMMs

@@ -79,6 +79,9 @@ SIGNATURES = {
     "mobgt_hop_table_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mobgt_hop_table_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mobgt_target_rank": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    "mobgt_rank_metrics_work_bytes": (_i64, [_i64, _i64]),
+    "mobgt_rank_metrics": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "mobgt_skinny_linear_rank_metrics": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "mobgt_skinny_linear_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mobgt_skinny_linear_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mobgt_skinny_linear_dx": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -280,6 +280,46 @@ constexpr int FG_MAXB = 1024;               // workgroups per launch (a wave wal
 __device__ unsigned long long fg_cell[9 * 32];
 __device__ unsigned int fg_bad = 0u;
 
+// The column-tile body of skinny_fwd_gtl_kernel below, for the evaluation kernels at the end of this file: the same loads into
+// the same MFMA slots and the same chain of v_mfma_f32_16x16x4f32 in the same k order, so a logit is the same bits whichever
+// kernel computes it (tests/test_gpu_eval.py checks it with exact ties).  (skinny_fwd_gtl_kernel keeps its own copy of these
+// lines: calling the helpers changes its instruction schedule, and it is on the training step's path.)
+// Keep these three in step with the inline copy in skinny_fwd_gtl_kernel.
+// Lane (j, q) of a wave: W[v][16 s + 4 q .. + 3] for its column v = v0 + j, zeros past V.
+template <int KT>
+__device__ __forceinline__ void fg_load_w(const float* w, int v, int V, int q, float4 (&wr)[4 * KT]) {
+    constexpr int K = 64 * KT;
+    const float* wrow = w + (int64_t)(v < V ? v : 0) * K + 4 * q;
+#pragma unroll
+    for (int s_ = 0; s_ < 4 * KT; ++s_)
+        wr[s_] = v < V ? *reinterpret_cast<const float4*>(wrow + 16 * s_) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// x [G, K] -> xs [GMAX][K + 4] (rows G.. zero) by `nthreads` threads; the caller synchronises
+template <int KT>
+__device__ __forceinline__ void fg_stage_x(float (*xs)[64 * KT + 4], const float* x, int G, int nthreads) {
+    constexpr int K = 64 * KT;
+    for (int e = threadIdx.x; e < GMAX * (K / 4); e += nthreads) {
+        const int g = e / (K / 4), c = e % (K / 4);
+        *reinterpret_cast<float4*>(&xs[g][4 * c]) = g < G ? *reinterpret_cast<const float4*>(x + (int64_t)g * K + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// lane (j, q) receives C[4 q + i][v0 + j] = sum_k x[4 q + i][k] W[v0 + j][k], i < 4 (the bias is the caller's)
+template <int KT>
+__device__ __forceinline__ f32x4_ fg_tile(const float (*xs)[64 * KT + 4], const float4 (&wr)[4 * KT], int j, int q) {
+    f32x4_ acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s_ = 0; s_ < 4 * KT; ++s_) {
+        const float4 a = *reinterpret_cast<const float4*>(&xs[j][16 * s_ + 4 * q]);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wr[s_].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wr[s_].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, wr[s_].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wr[s_].w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
 template <int KT>
 __global__ __launch_bounds__(64 * FG_WAVES) void skinny_fwd_gtl_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                       const float* __restrict__ b, const int64_t* __restrict__ target,
@@ -300,6 +340,9 @@ __global__ __launch_bounds__(64 * FG_WAVES) void skinny_fwd_gtl_kernel(const flo
     for (int v0 = ((int)blockIdx.x * FG_WAVES + wave) * 16; v0 < V || first; v0 += (int)gridDim.x * FG_WAVES * 16) {
     const int v = v0 + j;
     // this lane's weights: all in flight before anything else
+    // (the same lines as fg_load_w / fg_stage_x / fg_tile above, kept inline here -- calling them changes this kernel's schedule.
+    //  The evaluation kernels rely on the two producing the same logit bits: change both together;
+    //  tests/test_gpu_eval.py::test_fused_classifier_ranking_equals_unfused_exactly checks it)
     float4 wr[4 * KT];
     {
         const float* wrow = w + (int64_t)(v < V ? v : 0) * K + 4 * q;
@@ -483,3 +526,275 @@ int fwd_gtl_dispatch(const float* x, const float* w, const float* b, const int64
     }
 }
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------
+// Evaluation: the classifier and the ranking metrics of test_epoch_end (model_fqandtoyo.py:48-90 get_acc, :122-131 MRR_metric,
+// :1546-1597) without storing the logits.  Per row g, with t = target[g] + target_offset and s = the row's scores:
+//   greater = #{v : s[v] > s[t]},  tie_lo = #{v < t : s[v] == s[t]},  tie_hi = #{v > t : s[v] == s[t]}
+// (the two columns of mobgt_target_rank: the ACC / NDCG position is greater + tie_lo, the MRR position greater + tie_hi).
+// The column-splitting launch leaves each workgroup's counts in its own slice of a slab (plain stores, no atomics, no ticket);
+// a one-workgroup launch behind it sums the slab and applies metrics.evaluate_outputs' bookkeeping to acc[10] in f64.  Nothing
+// is left armed between calls, so a captured graph replays the pair any number of times.
+// Work buffer: f32 target scores [round64(G)] | int32 counts [blocks][G][3] (mobgt_rank_metrics_work_bytes).
+namespace {
+
+constexpr int RM_CHUNK = 2048;               // columns per workgroup of the stored-scores form
+constexpr int RM_MAXB = 128;
+
+inline int rm_blocks(int64_t V) {
+    const int64_t nb = (V + RM_CHUNK - 1) / RM_CHUNK;
+    return (int)(nb < RM_MAXB ? nb : RM_MAXB);
+}
+inline int fg_blocks(int64_t V) {
+    const int64_t nb = (V + 16 * FG_WAVES - 1) / (16 * FG_WAVES);
+    return (int)(nb < FG_MAXB ? nb : FG_MAXB);
+}
+inline int64_t rm_ts_floats(int64_t G) { return (G + 63) / 64 * 64; }
+
+__device__ __forceinline__ int64_t rm_target(const int64_t* __restrict__ target, int64_t target_offset, int64_t g, int64_t V, bool& ok) {
+    const int64_t t = target[g] + target_offset;
+    ok = t >= 0 && t < V;
+    return t;
+}
+
+// stored scores [G, V]: grid (blocks, G), a workgroup counts one row over a run of RM_CHUNK-ish columns
+__global__ __launch_bounds__(256) void rank_counts_kernel(const float* __restrict__ scores, const int64_t* __restrict__ target,
+                                                          int64_t target_offset, int32_t* __restrict__ slab, int G, int64_t V) {
+    __shared__ int s_c[4][3];
+    const int g = blockIdx.y;
+    bool ok;
+    const int64_t t = rm_target(target, target_offset, g, V, ok);
+    const float* s = scores + (int64_t)g * V;
+    const int64_t per = (V + gridDim.x - 1) / gridDim.x;
+    const int64_t c0 = (int64_t)blockIdx.x * per, c1 = c0 + per < V ? c0 + per : V;
+    int greater = 0, tie_lo = 0, tie_hi = 0;
+    if (ok) {
+        const float ts = s[t];
+        for (int64_t c = c0 + threadIdx.x; c < c1; c += 256) {
+            const float v = s[c];
+            greater += v > ts;
+            tie_lo += (v == ts) & (c < t);
+            tie_hi += (v == ts) & (c > t);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        greater += __shfl_xor(greater, o, 64);
+        tie_lo += __shfl_xor(tie_lo, o, 64);
+        tie_hi += __shfl_xor(tie_hi, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6][0] = greater; s_c[threadIdx.x >> 6][1] = tie_lo; s_c[threadIdx.x >> 6][2] = tie_hi; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int k = threadIdx.x;
+        slab[((int64_t)blockIdx.x * G + g) * 3 + k] = s_c[0][k] + s_c[1][k] + s_c[2][k] + s_c[3][k];
+    }
+}
+
+// The target's own logit, ts[g] = x[g] . W[t] + b[t], computed by the column tile that holds column t in the slot the ranking
+// kernel below gives it (tile (t / 16) * 16, lane j = t % 16, row g in its MFMA slot): the very instructions on the very
+// operands, so the comparison at v = t is equality and every other column compares bits the eager forward would produce.
+// One wave per row.
+template <int KT>
+__global__ __launch_bounds__(64) void skinny_target_logit_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ b, const int64_t* __restrict__ target,
+                                                                int64_t target_offset, float* __restrict__ ts, int G, int V) {
+    constexpr int K = 64 * KT, LDX = K + 4;
+    __shared__ __attribute__((aligned(16))) float xs[GMAX][LDX];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int j = lane & 15, q = lane >> 4;
+    bool ok;
+    const int64_t t = rm_target(target, target_offset, g, V, ok);
+    const int v = (ok ? (int)(t & ~15ll) : 0) + j;
+    float4 wr[4 * KT];
+    fg_load_w<KT>(w, v, V, q, wr);
+    const float bv = (b && v < V) ? b[v] : 0.f;
+    fg_stage_x<KT>(xs, x, G, 64);
+    __syncthreads();
+    const f32x4_ acc = fg_tile<KT>(xs, wr, j, q);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (4 * q + i == g && ok && v == t) ts[g] = acc[i] + bv;
+    if (!ok && lane == 0) ts[g] = 0.f;
+}
+
+// The classifier's logits, counted against the target logits as they are produced: the tile walk of skinny_fwd_gtl_kernel
+// (same grid, same tiles, same body); the logits never leave the registers.
+template <int KT>
+__global__ __launch_bounds__(64 * FG_WAVES) void skinny_rank_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                   const float* __restrict__ b, const int64_t* __restrict__ target,
+                                                                   int64_t target_offset, const float* __restrict__ ts_in,
+                                                                   int32_t* __restrict__ slab, int G, int V) {
+    constexpr int K = 64 * KT, LDX = K + 4;
+    __shared__ __attribute__((aligned(16))) float xs[GMAX][LDX];
+    __shared__ int part[FG_WAVES][GMAX][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 15, q = lane >> 4;
+    int64_t tgt[4];
+    float ts[4];
+    int cg[4] = {0, 0, 0, 0}, clo[4] = {0, 0, 0, 0}, chi[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        bool ok = false;
+        tgt[i] = 4 * q + i < G ? rm_target(target, target_offset, 4 * q + i, V, ok) : -1;
+        if (!ok) tgt[i] = -1;                         // (an invalid target counts nothing: the finish writes rank -1)
+        ts[i] = ok ? ts_in[4 * q + i] : 0.f;
+    }
+    bool first = true;
+    for (int v0 = ((int)blockIdx.x * FG_WAVES + wave) * 16; v0 < V || first; v0 += (int)gridDim.x * FG_WAVES * 16) {
+        const int v = v0 + j;
+        float4 wr[4 * KT];
+        fg_load_w<KT>(w, v, V, q, wr);
+        const float bv = (b && v < V) ? b[v] : 0.f;
+        if (first) {
+            fg_stage_x<KT>(xs, x, G, 64 * FG_WAVES);
+            __syncthreads();
+            first = false;
+        }
+        const f32x4_ acc = fg_tile<KT>(xs, wr, j, q);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (tgt[i] < 0 || v >= V) continue;
+            const float z = acc[i] + bv;
+            cg[i] += z > ts[i];
+            clo[i] += (z == ts[i]) & (v < tgt[i]);
+            chi[i] += (z == ts[i]) & (v > tgt[i]);
+        }
+    }
+    // lanes of one q (16 columns) hold partial counts of the same four rows: fold them onto j = 0
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) {
+            cg[i] += __shfl_xor(cg[i], o, 64);
+            clo[i] += __shfl_xor(clo[i], o, 64);
+            chi[i] += __shfl_xor(chi[i], o, 64);
+        }
+    }
+    if (j == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { part[wave][4 * q + i][0] = cg[i]; part[wave][4 * q + i][1] = clo[i]; part[wave][4 * q + i][2] = chi[i]; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 3 * G) {
+        const int g = threadIdx.x / 3, k = threadIdx.x % 3;
+        int s = 0;
+#pragma unroll
+        for (int u = 0; u < FG_WAVES; ++u) s += part[u][g][k];
+        slab[((int64_t)blockIdx.x * G + g) * 3 + k] = s;
+    }
+}
+
+// One workgroup: the slab's column sums per row, then metrics.evaluate_outputs' bookkeeping for the batch, added to acc =
+// {n, hit@1, hit@5, hit@10, hit@20, dcg@1, dcg@5, dcg@10, dcg@20, sum 1 / rank}.  ACC / NDCG stop at the first row whose
+// (shifted) target is 0 (get_acc's `else: break`); n and MRR count every row; gain = 1 / log2(position + 2) in f64.
+// Sixteen rows at a time, 16 lanes per row: every row's slab column is in flight at once (a row after row walk paid one memory
+// round trip per row: ~1 us each); thread 0 then walks the rows' totals in LDS in order.
+constexpr int RF_ROWS = 16;
+
+__global__ __launch_bounds__(256) void rank_finish_kernel(const int32_t* __restrict__ slab, int nb, const int64_t* __restrict__ target,
+                                                          int64_t target_offset, int G, int64_t V, double* __restrict__ acc) {
+    __shared__ int s_c[RF_ROWS][3];
+    __shared__ int64_t s_t[RF_ROWS];
+    __shared__ bool s_ok[RF_ROWS];
+    double hit[4] = {0.0, 0.0, 0.0, 0.0}, dcg[4] = {0.0, 0.0, 0.0, 0.0}, mrr = 0.0;
+    bool stopped = false;
+    const int ks[4] = {1, 5, 10, 20};
+    const int r = threadIdx.x >> 4, l = threadIdx.x & 15;
+    for (int g0 = 0; g0 < G; g0 += RF_ROWS) {
+        const int g = g0 + r;
+        int c[3] = {0, 0, 0};
+        if (g < G) {
+            for (int bk = l; bk < nb; bk += 16) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) c[k] += slab[((int64_t)bk * G + g) * 3 + k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int o = 8; o >= 1; o >>= 1) c[k] += __shfl_xor(c[k], o, 64);
+        __syncthreads();                              // (s_c of the previous rows has been read)
+        if (l == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_c[r][k] = c[k];
+            bool ok = false;
+            s_t[r] = g < G ? rm_target(target, target_offset, g, V, ok) : -1;     // (the targets too: all rows' loads at once)
+            s_ok[r] = ok;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int i = 0; i < RF_ROWS && g0 + i < G; ++i) {
+                const bool ok = s_ok[i];
+                const int64_t t = s_t[i];
+                const int lo = ok ? s_c[i][0] + s_c[i][1] : -1;
+                const int hi = ok ? s_c[i][0] + s_c[i][2] : -1;
+                if (t == 0) stopped = true;
+                if (!stopped && lo >= 0 && lo < 20) {
+                    const double gain = 1.0 / log2((double)lo + 2.0);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (lo < ks[q]) { hit[q] += 1.0; dcg[q] += gain; }
+                }
+                mrr += 1.0 / ((double)hi + 1.0);
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        acc[0] += (double)G;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { acc[1 + q] += hit[q]; acc[5 + q] += dcg[q]; }
+        acc[9] += mrr;
+    }
+}
+
+template <int KT>
+int launch_rank_fused(const float* x, const float* w, const float* b, const int64_t* target, int64_t target_offset, double* acc,
+                      char* work, int G, int V, hipStream_t st) {
+    float* ts = reinterpret_cast<float*>(work);
+    int32_t* slab = reinterpret_cast<int32_t*>(ts + rm_ts_floats(G));
+    const int blocks = fg_blocks(V);
+    hipLaunchKernelGGL((skinny_target_logit_kernel<KT>), dim3(G), dim3(64), 0, st, x, w, b, target, target_offset, ts, G, V);
+    hipLaunchKernelGGL((skinny_rank_kernel<KT>), dim3(blocks), dim3(64 * FG_WAVES), 0, st, x, w, b, target, target_offset, ts, slab, G, V);
+    hipLaunchKernelGGL(rank_finish_kernel, dim3(1), dim3(256), 0, st, slab, blocks, target, target_offset, G, (int64_t)V, acc);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int64_t mobgt_rank_metrics_work_bytes(int64_t G, int64_t V) {
+    if (G <= 0 || V <= 0) return 0;
+    const int64_t nb = rm_blocks(V) > fg_blocks(V) ? rm_blocks(V) : fg_blocks(V);
+    return 4 * rm_ts_floats(G) + 12 * nb * G;
+}
+
+extern "C" int mobgt_rank_metrics(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V, double* acc,
+                                  void* work, void* stream) {
+    if (G <= 0 || V <= 0 || G > 65535 || V > (int64_t)INT32_MAX) return MOBGT_EBADDIM;
+    if (!scores || !target || !acc || !work) return MOBGT_EBADDIM;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* slab = reinterpret_cast<int32_t*>(reinterpret_cast<float*>(work) + rm_ts_floats(G));
+    const int nb = rm_blocks(V);
+    hipLaunchKernelGGL(rank_counts_kernel, dim3(nb, (unsigned)G), dim3(256), 0, st, scores, target, target_offset, slab, (int)G, V);
+    hipLaunchKernelGGL(rank_finish_kernel, dim3(1), dim3(256), 0, st, slab, nb, target, target_offset, (int)G, V, acc);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mobgt_skinny_linear_rank_metrics(const float* x, const float* w, const float* b, const int64_t* target, int64_t target_offset,
+                                                int G, int K, int V, double* acc, void* work, void* stream) {
+    const int rc = check_dims(G, K, V);
+    if (rc) return rc;
+    if ((K & 63) || K > 448 || !target || !acc || !work) return MOBGT_EBADDIM;
+    if (((uintptr_t)x | (uintptr_t)w) & 15) return MOBGT_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    char* wk = reinterpret_cast<char*>(work);
+    switch (K / 64) {
+        case 1: return launch_rank_fused<1>(x, w, b, target, target_offset, acc, wk, G, V, st);
+        case 2: return launch_rank_fused<2>(x, w, b, target, target_offset, acc, wk, G, V, st);
+        case 3: return launch_rank_fused<3>(x, w, b, target, target_offset, acc, wk, G, V, st);
+        case 4: return launch_rank_fused<4>(x, w, b, target, target_offset, acc, wk, G, V, st);
+        case 5: return launch_rank_fused<5>(x, w, b, target, target_offset, acc, wk, G, V, st);
+        case 6: return launch_rank_fused<6>(x, w, b, target, target_offset, acc, wk, G, V, st);
+        default: return launch_rank_fused<7>(x, w, b, target, target_offset, acc, wk, G, V, st);
+    }
+}

@@ -67,3 +67,26 @@ def evaluate_outputs(outputs):
     tot /= max(n, 1)
     return {"acc@1": tot[0], "acc@5": tot[1], "acc@10": tot[2], "ndcg@1": tot[3], "ndcg@5": tot[4], "ndcg@10": tot[5],
             "acc@20": tot[6], "ndcg@20": tot[7], "mrr": mrr / max(n, 1)}
+
+
+# ---- device accumulation (ops.rank_metrics / ops.skinny_linear_rank_metrics, train.EvalLoop) --------------------------------------
+# One f64 [10] tensor on the device: {n, hit@1, hit@5, hit@10, hit@20, dcg@1, dcg@5, dcg@10, dcg@20, sum 1 / rank}.  A batch adds
+# exactly what evaluate_outputs adds for it (counts bit for bit; the DCG / MRR sums in another order: ~1e-16 relative), so a whole
+# split is one host read at the end.
+ACC_FIELDS = ("n", "hit@1", "hit@5", "hit@10", "hit@20", "dcg@1", "dcg@5", "dcg@10", "dcg@20", "rr")
+
+
+def new_accumulator(device):
+    return torch.zeros(len(ACC_FIELDS), dtype=torch.float64, device=device)
+
+
+def finalize(acc):
+    """The dict of evaluate_outputs (each sum divided by the number of samples) plus "n", from an accumulator (device or host)."""
+    a = np.asarray(torch.as_tensor(acc).detach().double().cpu().numpy(), dtype=np.float64).reshape(-1)
+    assert a.size == len(ACC_FIELDS)
+    n = a[0]
+    d = max(n, 1.0)
+    out = {k: float(a[i] / d) for k, i in (("acc@1", 1), ("acc@5", 2), ("acc@10", 3), ("ndcg@1", 5), ("ndcg@5", 6), ("ndcg@10", 7),
+                                              ("acc@20", 4), ("ndcg@20", 8), ("mrr", 9))}
+    out["n"] = int(n)
+    return out

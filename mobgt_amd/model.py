@@ -663,3 +663,8 @@ class Graphormer(nn.Module):
         if ops.cross_entropy_ok(logits, y):
             return ops.cross_entropy(logits, y, ignore_index=0)           # value + gradient in one launch (csrc/layer.hip)
         return F.cross_entropy(logits.float(), y.long(), ignore_index=0)
+
+    def metric_step(self, batched_data, acc, work=None):
+        """The fq model's device evaluation (model_fqandtoyo.Graphormer.metric_step) has no counterpart in this variant: the
+        reference's model.py evaluates through Lightning's generic metric hooks, not test_epoch_end's ACC / NDCG / MRR."""
+        raise NotImplementedError("metric_step / train.EvalLoop: the fq model (model_fqandtoyo.Graphormer) only")

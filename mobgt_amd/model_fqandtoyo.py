@@ -534,6 +534,22 @@ class Graphormer(nn.Module):
         ops.trace_nan("tok", tok)
         y_head = getattr(self, "_loss_in_head", None)
         toyota = self.dataset_name == "toyotagraph"
+        m_head = getattr(self, "_metrics_in_head", None)
+        if m_head is not None:
+            # metric_step: the classifier ends in the ranking metrics of test_epoch_end (:1546-1597) added to a device
+            # accumulator; cat_decoder's output (read by nobody there) is not produced
+            y_m, acc, work = m_head
+            W, b = self.out_proj.weight, self.out_proj.bias
+            # (the logits are stored and ranked by mobgt_rank_metrics: measured faster than the fused classifier-ranking form,
+            #  ops.skinny_linear_rank_metrics, at every width from 3 680 to 100 001 classes -- 15.1 against 23.4 us at S-FSQ's
+            #  7 857, 49 against 75 us at S-BIG's 100 001 (tools/eval_bench.py); both give the same bits)
+            logits = ops.skinny_linear(tok, W, b) if ops.skinny_linear_ok(tok, W) else self.out_proj(tok)
+            if toyota:
+                # :1484-1495: toyotagraph is not in the y - 1 list -- unshifted y, and the POI head's log-probabilities (:1417-1428)
+                ops.rank_metrics(torch.log_softmax(logits.float(), dim=1), y_m, acc, target_offset=0, work=work)
+            else:
+                ops.rank_metrics(logits, y_m, acc, target_offset=-1, work=work)
+            return [None, None]
         if y_head is not None and not toyota and ops.skinny_linear_gtl_ok(tok, self.out_proj.weight):
             # training_step: the classifier and GradientTailLoss(alpha = 0.2) on y - 1 (:1394, :1446-1460) in ONE launch; the
             # logits are never stored
@@ -591,6 +607,27 @@ class Graphormer(nn.Module):
     def test_step(self, batched_data, batch_idx=0):
         """model_fqandtoyo.py:1530-1544"""
         return {"y_pred": self(batched_data), "y_true": batched_data.y.long() - 1, "idx": batched_data.idx}
+
+    def metric_step(self, batched_data, acc, work=None):
+        """validation_step / test_step + test_epoch_end's per-batch bookkeeping in one pass: the batch's ACC / NDCG @1/5/10/20
+        and MRR sums (metrics.evaluate_outputs, quirks included) are ADDED to `acc` (metrics.new_accumulator) on the device --
+        no category head, no host read.  Eval mode, under no_grad.  toyotagraph ranks log_softmax(logits) against
+        the UNSHIFTED y, as the reference's validation / test step does (:1484-1495).  `work`: ops.rank_metrics' buffer."""
+        if self.training:
+            raise RuntimeError("metric_step: the model is in training mode (call .eval() first)")
+        with torch.no_grad():
+            self._metrics_in_head = (batched_data.y, acc, work)
+            try:
+                self(batched_data)
+            finally:
+                self._metrics_in_head = None
+        return acc
+
+    def evaluate(self, dataset, collator, **kw):
+        """train.EvalLoop(self, collator, dataset, **kw).run(): the reference's validation / test protocol over a whole split."""
+        from .train import EvalLoop
+        max_batches = kw.pop("max_batches", None)
+        return EvalLoop(self, collator, dataset, **kw).run(max_batches=max_batches)
 
     def test_epoch_end(self, outputs):
         """model_fqandtoyo.py:1546-1597: ACC / NDCG @1/5/10/20 and MRR over all test samples."""

@@ -920,6 +920,77 @@ def target_rank(scores, target):
     return rank
 
 
+# (device, stream) -> work buffer of the ranking launches.  A buffer that is outgrown stays alive (_RANK_WORK_OLD): a captured
+# graph may still name it.
+_RANK_WORK, _RANK_WORK_OLD = {}, []
+
+
+def rank_metrics_work_bytes(G, V):
+    return int(_lib.lib().mobgt_rank_metrics_work_bytes(G, V))
+
+
+def _rank_work(device, G, V, work=None):
+    n = rank_metrics_work_bytes(G, V)
+    if work is not None:
+        assert work.is_cuda and work.numel() * work.element_size() >= n, f"rank metrics: work buffer of {n} bytes needed"
+        return work
+    key = (device, torch.cuda.current_stream(device).stream_id)
+    buf = _RANK_WORK.get(key)
+    if buf is None or buf.numel() < n:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("mobgt rank metrics: no work buffer of this size on this stream yet -- pass `work` or run the call "
+                               "once eagerly before capturing it")
+        if buf is not None:
+            _RANK_WORK_OLD.append(buf)
+        buf = _RANK_WORK[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
+    return buf
+
+
+def _check_acc(acc):
+    assert acc.is_cuda and acc.dtype == torch.float64 and acc.numel() == 10 and acc.is_contiguous(), \
+        "acc: the f64 [10] device accumulator of metrics.new_accumulator"
+
+
+def rank_metrics(scores, target, acc, target_offset=0, work=None):
+    """Adds one batch's test_epoch_end sums (metrics.evaluate_outputs' quirks kept; see metrics.new_accumulator) to `acc`, ranking
+    the stored scores [G, V] against class target[g] + target_offset: mobgt_rank_metrics, two launches, no host read."""
+    _require_cuda(scores, target, acc)
+    _check_acc(acc)
+    scores = scores.float().contiguous()
+    target = target.reshape(-1).long().contiguous()
+    G, V = scores.shape
+    assert target.numel() >= G
+    work = _rank_work(scores.device, G, V, work)
+    check(_lib.lib().mobgt_rank_metrics(_p(scores), _p(target), int(target_offset), G, V, _p(acc), _p(work), _stream()),
+          "mobgt_rank_metrics")
+    return acc
+
+
+def skinny_linear_rank_metrics_ok(x, weight):
+    return skinny_linear_gtl_ok(x, weight)
+
+
+def skinny_linear_rank_metrics(x, weight, bias, target, acc, target_offset=0, work=None):
+    """rank_metrics(skinny_linear(x, weight, bias), target, acc, target_offset) without storing the logits: the classifier's
+    column tiles (bit-identical logits) ranked in the same pass over the weight (mobgt_skinny_linear_rank_metrics).  Shapes:
+    skinny_linear_rank_metrics_ok.  `work`: a device buffer of rank_metrics_work_bytes(G, V) bytes (default: one per stream)."""
+    _require_cuda(x, weight, target, acc)
+    _check_acc(acc)
+    assert skinny_linear_rank_metrics_ok(x, weight), "skinny_linear_rank_metrics: G <= 16 rows, K % 64 == 0, K <= 448, f32"
+    x = x.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    G, K = x.shape
+    V = weight.shape[0]
+    target = target.reshape(-1)[:G].long().contiguous()
+    assert target.numel() == G
+    b = bias.detach().contiguous() if bias is not None else None
+    work = _rank_work(x.device, G, V, work)
+    check(_lib.lib().mobgt_skinny_linear_rank_metrics(_p(x.detach()), _p(weight.detach()), _p(b), _p(target), int(target_offset),
+                                                      G, K, V, _p(acc), _p(work), _stream()), "mobgt_skinny_linear_rank_metrics")
+    return acc
+
+
 def node_index(x, time_normal, poi2cat, rows_only, in_degree=None, out_degree=None):
     """Row indices of the node-feature gathers (model_fqandtoyo.py:1259-1264, 1287-1298) in one launch.
     x [G,N] int64/int32 POI ids, time_normal [G,N] f32 -> (idx [8,G,N] int64, real [G,N] f32); rows of idx:

@@ -981,7 +981,93 @@ class TrainStep:
         return self.loss_out
 
 
-class EpochLoop:
+class _StagedBatches:
+    """Fresh batches on the device data path, shared by EpochLoop and EvalLoop: shape buckets, pinned staging, the device collate
+    on the copy stream and the host-side index checks.  The owner sets model, collator, dataset, buckets, device, copy_stream,
+    slots = {}, limits = None and side_collate."""
+
+    # ---- buckets --------------------------------------------------------------------------------------------------------
+    def _slot(self, G, N):
+        from .data import BatchLayout, RawLayout
+        key = (G, N)
+        s = self.slots.get(key)
+        if s is None:
+            # `side`: the device collate of the NEXT batch runs on the copy stream, beside the current step (whose kernels
+            # leave most of the chip idle); the step graph then reads a collated static batch.  Collators that need torch
+            # ops (coordinate bins, S-BIG) keep the collate inside the step graph (batch_fn = finish).
+            side = self.side_collate and self.collator.can_finish_into()
+            lay = BatchLayout(G, N, self.collator.D) if side else RawLayout(G, N)
+            buf = torch.zeros(lay.nbytes, dtype=torch.uint8, device=self.device)
+            views = lay.views_torch(buf)
+            s = dict(layout=lay, buf=buf, views=views, index=None, stages=[], turn=0, side=side,
+                     batch=self.collator.batch_from_views(views) if side else views,
+                     copy_bytes=lay.copy_bytes if side else lay.nbytes)
+            raw_bytes = lay.raw_bytes if side else lay.nbytes
+            for _ in range(2):
+                pin = torch.zeros(raw_bytes, dtype=torch.uint8).pin_memory()
+                dev = torch.zeros(lay.nbytes, dtype=torch.uint8, device=self.device)
+                dv = lay.views_torch(dev) if side else None
+                s["stages"].append(dict(pin=pin, np=lay.views_np(pin.numpy()), dev=dev, dev_views=dv,
+                                        work=None, ready=torch.cuda.Event(), free=None, used=False, index=None,
+                                        batch=None))
+            # (the zero fills above are queued on the current stream, behind whatever it still runs; the copy stream writes the
+            #  staging buffers next and must not overtake them -- a fill landing after the copy left a batch of zeros)
+            self.copy_stream.wait_stream(torch.cuda.current_stream())
+            self.slots[key] = s
+        return s
+
+    def _check_host(self, h):
+        """What nn.Embedding would raise on in the reference (IndexError), checked on the host arrays of a fresh batch --
+        the captured step cannot look at values (model.validate_batch does this for pre-collated batches)."""
+        m = self.model
+        if self.limits is None:
+            # (the model says which fields it indexes tables with -- model.index_limits(); a model without the hook is not checked)
+            self.limits = m.index_limits() if hasattr(m, "index_limits") else {}
+        L = self.limits
+        nz = h["counts"] != 0
+        bad = None
+        if "x" in L and int(h["x"].max()) > L["x"]:
+            bad = ("x", int(h["x"].max()), L["x"] + 1)
+        elif "user" in L and int(h["user"].max()) > L["user"]:
+            bad = ("user", int(h["user"].max()), L["user"] + 1)
+        elif "y" in L and int(h["y"].max()) > L["y"]:
+            bad = ("y", int(h["y"].max()), L["y"] + 1)
+        elif "edge" in L and int(h["counts"].max()) + 3 >= L["edge"]:
+            bad = ("edge_input", int(h["counts"].max()) + 3, L["edge"])
+        elif "deg" in L and max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1 >= L["deg"]:
+            bad = ("degree", max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1, L["deg"])
+        elif "slots" in L and int(float(h["time_normal"].max()) * 48) >= L["slots"]:
+            bad = ("time_normal", float(h["time_normal"].max()), L["slots"])
+        if bad:
+            raise IndexError(f"batch.{bad[0]} has index {bad[1]}, out of range for a table of {bad[2]} rows")
+
+    def _stage(self, ids):
+        """Host half of a step's input: raw trajectories -> the bucket's pinned buffer -> async copy to a device staging
+        buffer on the copy stream.  Returns (slot, stage)."""
+        from .data import bucket_nodes
+        trajs = [self.dataset[i] for i in ids]
+        trajs = [t for t in trajs if t is not None and len(t["node_name"]) <= self.collator.max_node]
+        G = len(trajs)
+        if G == 0:
+            return None                                # (every trajectory filtered out: the reference's collator skips such a batch too, collator.py:313)
+        N = bucket_nodes(max(len(t["node_name"]) for t in trajs), self.buckets)
+        slot = self._slot(G, N)
+        st = slot["stages"][slot["turn"]]
+        slot["turn"] ^= 1
+        if st["free"] is not None:
+            st["free"].synchronize()                   # its previous device-to-device copy has been executed
+        self.collator.pack_host(trajs, idx0=ids[:G] if len(ids) == G else 0, n_pad=N, out=st["np"])
+        self._check_host(st["np"])
+        st["used"] = True
+        with torch.cuda.stream(self.copy_stream):
+            st["dev"][:st["pin"].numel()].copy_(st["pin"], non_blocking=True)
+            if slot["side"]:
+                st["work"] = self.collator.finish_into(st["dev_views"], st["work"])
+            st["ready"].record(self.copy_stream)
+        return slot, st
+
+
+class EpochLoop(_StagedBatches):
     """The fit loop over the training set (Lightning's `trainer.fit` on `train_dataloader`: entry.py:141-161,
     data.py:282-295), one process per GPU: a NEW batch every step, collated on the device.
 
@@ -1041,83 +1127,6 @@ class EpochLoop:
         B = self.batch_size
         return [idx[i:i + B] for i in range(0, len(idx), B)]
 
-    # ---- buckets --------------------------------------------------------------------------------------------------------
-    def _slot(self, G, N):
-        from .data import BatchLayout, RawLayout
-        key = (G, N)
-        s = self.slots.get(key)
-        if s is None:
-            # `side`: the device collate of the NEXT batch runs on the copy stream, beside the current step (whose kernels
-            # leave most of the chip idle); the step graph then reads a collated static batch.  Collators that need torch
-            # ops (coordinate bins, S-BIG) keep the collate inside the step graph (batch_fn = finish).
-            side = self.side_collate and self.collator.can_finish_into()
-            lay = BatchLayout(G, N, self.collator.D) if side else RawLayout(G, N)
-            buf = torch.zeros(lay.nbytes, dtype=torch.uint8, device=self.device)
-            views = lay.views_torch(buf)
-            s = dict(layout=lay, buf=buf, views=views, index=None, stages=[], turn=0, side=side,
-                     batch=self.collator.batch_from_views(views) if side else views,
-                     copy_bytes=lay.copy_bytes if side else lay.nbytes)
-            raw_bytes = lay.raw_bytes if side else lay.nbytes
-            for _ in range(2):
-                pin = torch.zeros(raw_bytes, dtype=torch.uint8).pin_memory()
-                dev = torch.zeros(lay.nbytes, dtype=torch.uint8, device=self.device)
-                dv = lay.views_torch(dev) if side else None
-                s["stages"].append(dict(pin=pin, np=lay.views_np(pin.numpy()), dev=dev, dev_views=dv,
-                                        work=None, ready=torch.cuda.Event(), free=None, used=False, index=None,
-                                        batch=None))
-            self.slots[key] = s
-        return s
-
-    def _check_host(self, h):
-        """What nn.Embedding would raise on in the reference (IndexError), checked on the host arrays of a fresh batch --
-        the captured step cannot look at values (model.validate_batch does this for pre-collated batches)."""
-        m = self.model
-        if self.limits is None:
-            # (the model says which fields it indexes tables with -- model.index_limits(); a model without the hook is not checked)
-            self.limits = m.index_limits() if hasattr(m, "index_limits") else {}
-        L = self.limits
-        nz = h["counts"] != 0
-        bad = None
-        if "x" in L and int(h["x"].max()) > L["x"]:
-            bad = ("x", int(h["x"].max()), L["x"] + 1)
-        elif "user" in L and int(h["user"].max()) > L["user"]:
-            bad = ("user", int(h["user"].max()), L["user"] + 1)
-        elif "y" in L and int(h["y"].max()) > L["y"]:
-            bad = ("y", int(h["y"].max()), L["y"] + 1)
-        elif "edge" in L and int(h["counts"].max()) + 3 >= L["edge"]:
-            bad = ("edge_input", int(h["counts"].max()) + 3, L["edge"])
-        elif "deg" in L and max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1 >= L["deg"]:
-            bad = ("degree", max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1, L["deg"])
-        elif "slots" in L and int(float(h["time_normal"].max()) * 48) >= L["slots"]:
-            bad = ("time_normal", float(h["time_normal"].max()), L["slots"])
-        if bad:
-            raise IndexError(f"batch.{bad[0]} has index {bad[1]}, out of range for a table of {bad[2]} rows")
-
-    def _stage(self, ids):
-        """Host half of a step's input: raw trajectories -> the bucket's pinned buffer -> async copy to a device staging
-        buffer on the copy stream.  Returns (slot, stage)."""
-        from .data import bucket_nodes
-        trajs = [self.dataset[i] for i in ids]
-        trajs = [t for t in trajs if t is not None and len(t["node_name"]) <= self.collator.max_node]
-        G = len(trajs)
-        if G == 0:
-            return None                                # (every trajectory filtered out: the reference's collator skips such a batch too, collator.py:313)
-        N = bucket_nodes(max(len(t["node_name"]) for t in trajs), self.buckets)
-        slot = self._slot(G, N)
-        st = slot["stages"][slot["turn"]]
-        slot["turn"] ^= 1
-        if st["free"] is not None:
-            st["free"].synchronize()                   # its previous device-to-device copy has been executed
-        self.collator.pack_host(trajs, idx0=ids[:G] if len(ids) == G else 0, n_pad=N, out=st["np"])
-        self._check_host(st["np"])
-        st["used"] = True
-        with torch.cuda.stream(self.copy_stream):
-            st["dev"][:st["pin"].numel()].copy_(st["pin"], non_blocking=True)
-            if slot["side"]:
-                st["work"] = self.collator.finish_into(st["dev_views"], st["work"])
-            st["ready"].record(self.copy_stream)
-        return slot, st
-
     def _ensure_trainer(self, slot):
         """The first batch builds the TrainStep (dry run for the trained-parameter set, flat buffers, optimizer graph)."""
         if self.ts is None:
@@ -1171,3 +1180,160 @@ class EpochLoop:
         if self.ts is not None:
             self.ts.check_faults(on_fault="raise")
         return dict(steps=steps, graphs=len(self.slots), sample_ids=seen)
+
+
+class EvalLoop(_StagedBatches):
+    """The validation / test loop (Lightning's `trainer.validate` / `trainer.test` over the reference's eval DataLoader,
+    entry.py:120-161, with test_epoch_end's bookkeeping, model_fqandtoyo.py:1484-1597) on the device data path of EpochLoop.
+
+    * order: the reference's eval loader -- no shuffle, consecutive runs of `batch_size`, drop_last=False; with `world` > 1 the
+      non-shuffling DistributedSampler (data.shard_indices, wrap-around duplicates included).  Batches are never regrouped by
+      length: which rows share a batch decides where get_acc's stop at the first target 0 applies;
+    * shapes and staging: EpochLoop's buckets (one static batch per (G, bucket)), pinned buffers, device collate on the copy
+      stream, host index checks; trajectories over `collator.max_node` are dropped;
+    * per (G, bucket, ops.SAFE_FORMS[0]) ONE captured graph = eval forward + the fused classifier-ranking launches
+      (Graphormer.metric_step) adding into ONE f64 accumulator; `use_graph=False` runs the same launches eagerly, and so do
+      collators whose finish needs torch ops (coordinate bins, S-BIG: see _launch);
+    * `run()` reads the accumulator once (after one all-reduce of its 10 doubles when world > 1: every rank's samples pooled).
+    The weights are read as they are when `run()` starts (bf16 shadows and MFMA packs re-derived there, outside any graph), so an
+    evaluation between training epochs sees the current model; it leaves no state behind that the trainer's next step reads."""
+
+    def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
+                 side_collate=True):
+        from .data import BUCKETS
+        from . import metrics
+        if not hasattr(model, "metric_step"):
+            raise TypeError("EvalLoop: the model has no metric_step (the fq model, model_fqandtoyo.Graphormer)")
+        self.model, self.collator, self.dataset = model, collator, dataset
+        self.batch_size = int(batch_size)
+        self.buckets = tuple(buckets or BUCKETS)
+        ddp = dist.is_available() and dist.is_initialized()
+        self.rank = rank if rank is not None else (dist.get_rank() if ddp else 0)
+        self.world = world if world is not None else (dist.get_world_size() if ddp else 1)
+        self.device = next(model.parameters()).device
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.stream = torch.cuda.Stream(device=self.device) if use_graph else None     # warm-ups and captures
+        self.use_graph = bool(use_graph)
+        self.side_collate = bool(side_collate)
+        self.slots, self.limits, self.graphs = {}, None, {}
+        self._graph_ptrs = None
+        self.captures = 0                                   # graphs captured so far (a replayed run captures none)
+        self.acc = metrics.new_accumulator(self.device)
+        self._scratch = metrics.new_accumulator(self.device)                          # warm-up passes count nowhere
+        V = model.out_proj.out_features
+        self.work = torch.empty(ops.rank_metrics_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
+
+    def batches(self):
+        from .data import shard_indices
+        idx = shard_indices(len(self.dataset), self.rank, self.world, shuffle=False)
+        B = self.batch_size
+        return [idx[i:i + B] for i in range(0, len(idx), B)]
+
+    def _forward(self, batch, acc):
+        b = self.collator.finish(batch) if isinstance(batch, dict) else batch      # (raw views: the in-graph collate)
+        self.model.metric_step(b, acc, work=self.work)
+
+    def _weights_ptrs(self):
+        """Addresses a captured eval forward reads besides its batch: parameters, bf16 shadows, MFMA packs, the dropout seed.  A
+        change (a trainer built after the capture re-homes the shadows) drops the graphs."""
+        ptrs = [p.data_ptr() for p in self.model.parameters()]
+        for layer in getattr(self.model, "layers", []):
+            for name in ("_shadows", "_packed"):
+                t = getattr(layer, name, None)
+                ptrs += [x.data_ptr() for x in t] if t is not None else [0]
+        ptrs += [m.seed_dev.data_ptr() for m in self.model.modules() if getattr(m, "seed_dev", None) is not None]
+        return tuple(ptrs)
+
+    def _launch(self, slot, st):
+        cur = torch.cuda.current_stream()
+        cur.wait_event(st["ready"])
+        n = slot["copy_bytes"]
+        slot["buf"][:n].copy_(st["dev"][:n], non_blocking=True)
+        if st["free"] is None:
+            st["free"] = torch.cuda.Event()
+        st["free"].record(cur)
+        if not self.use_graph or not slot["side"]:
+            # Buckets whose collate needs torch ops (coordinate bins: S-BIG) run eagerly.  Captured with the collate inside, the
+            # replay took 130 ms per 16 x 784 batch against 13 ms eager: inside the replayed graph the SPD kernel's split form
+            # (workgroups that wait for each other, csrc/spd.hip) gave up on every call and its one-workgroup-per-graph redo
+            # pass ran (fw_kernel: 75 ms per call, rocprofv3).  Why it gives up only there is not known.
+            self._forward(slot["batch"], self.acc)
+            return
+        key = (slot["layout"].G, slot["layout"].N, bool(ops.SAFE_FORMS[0]))
+        g = self.graphs.get(key)
+        if g is None:
+            self.stream.wait_stream(cur)
+            with torch.cuda.stream(self.stream):
+                self._forward(slot["batch"], self._scratch)                          # allocator, lazy initialisations
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self.stream):
+                self._forward(slot["batch"], self.acc)
+            cur.wait_stream(self.stream)
+            self.graphs[key] = g
+            self.captures += 1
+        g.replay()
+
+    def _refresh_weights(self):
+        """bf16 shadows and MFMA packs from the current fp32 weights, once, outside any graph (the captured forwards then skip
+        the copy: layer._weights_frozen)."""
+        from .model import refresh_shadows
+        layers = list(getattr(self.model, "layers", []))
+        for layer in layers:
+            if not getattr(layer, "_shadow_external", False):
+                layer._shadow_ver = None                    # (unconditional copy: see model._may_skip_shadow_copy)
+            layer._packed_ver = None
+        refresh_shadows(layers)
+        for layer in layers:                                # (a pack is good for the forward that follows a refresh only)
+            layer._packed_fresh = layer._packed_t_fresh = False
+
+    def run(self, max_batches=None):
+        """One pass over this rank's part of the split -> dict of metrics.evaluate_outputs' keys + "n" (samples counted)."""
+        from . import metrics
+        model = self.model
+        batches = self.batches()
+        if max_batches is not None:
+            batches = batches[:max_batches]
+        layers = list(getattr(model, "layers", []))
+        was_training = model.training
+        frozen = [getattr(l, "_weights_frozen", False) for l in layers]
+        saved = {k: model.__dict__.get(k) for k in ("_enc_out", "_bias_pack", "_cuts")}
+        token_chain = ops._TOKEN_CHAIN.get("cur")
+        model.eval()
+        try:
+            with torch.no_grad():
+                self._refresh_weights()
+                for l in layers:
+                    l._weights_frozen = True
+                ptrs = self._weights_ptrs()
+                if ptrs != self._graph_ptrs:
+                    self.graphs.clear()
+                    self._graph_ptrs = ptrs
+                self.acc.zero_()
+                nxt = self._stage(batches[0]) if batches else None
+                for j in range(len(batches)):
+                    cur = nxt
+                    if cur is not None:
+                        self._launch(*cur)                   # asynchronous: the GPU evaluates batch j ...
+                    nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None     # ... while the host packs j + 1
+                if self.world > 1 and dist.is_available() and dist.is_initialized():
+                    if dist.get_backend() == "gloo":
+                        host = self.acc.cpu()
+                        dist.all_reduce(host)
+                        self.acc.copy_(host)
+                    else:
+                        dist.all_reduce(self.acc)
+                out = metrics.finalize(self.acc)              # the one host read
+        finally:
+            for l, f in zip(layers, frozen):
+                l._weights_frozen = f
+            for k, v in saved.items():
+                setattr(model, k, v)
+            if token_chain is None:
+                ops._TOKEN_CHAIN.pop("cur", None)
+            else:
+                ops._TOKEN_CHAIN["cur"] = token_chain
+            model.train(was_training)
+        left = ops.step_state_leftovers()
+        if left:
+            raise RuntimeError(f"EvalLoop: the evaluation left parked work behind {left}")
+        return out
