@@ -348,6 +348,17 @@ int mobgt_rank_metrics(const float* scores, const int64_t* target, int64_t targe
                        void* work, void* stream);
 int mobgt_skinny_linear_rank_metrics(const float* x, const float* w, const float* b, const int64_t* target, int64_t target_offset,
                                      int G, int K, int V, double* acc, void* work, void* stream);
+/* Row-wise top-k of stored scores: the ranked next-POI list (Graphormer.recommend_step, train.PredictLoop), replacing the
+ * torch.topk a caller ran on test_step's y_pred (:1530-1544) by hand.  scores [G, V] f32 with row stride ld >= V (elements);
+ * 1 <= k <= 64, k <= V, G <= 65535, else MOBGT_EBADDIM.  Writes ids [G, k] int64 = column + col_offset and vals [G, k] f32 equal to
+ *     torch.sort(scores, dim=1, descending=True, stable=True)[:, :k]   (values, indices + col_offset)
+ * bit for bit: descending score; equal scores in ascending column order (the tie rule of mobgt_target_rank's ACC position, so
+ * target in ids[g, :k] <=> rank[2g] < k); -0.0 ties with +0.0; NaN of either sign above +inf; vals are the stored bits.
+ * `work`: mobgt_topk_work_bytes(G, V, k) bytes, any contents (every byte read is written first); no state survives a call.
+ * Not re-entrant across streams on one `work`.  Two launches: column chunks over many workgroups, then one workgroup per row. */
+int64_t mobgt_topk_work_bytes(int64_t G, int64_t V, int64_t k);
+int mobgt_topk_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, int64_t* ids, float* vals,
+                    void* work, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused elementwise / normalisation pieces of EncoderLayer.forward between the library GEMMs

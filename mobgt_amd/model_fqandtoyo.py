@@ -550,6 +550,16 @@ class Graphormer(nn.Module):
             else:
                 ops.rank_metrics(logits, y_m, acc, target_offset=-1, work=work)
             return [None, None]
+        r_head = getattr(self, "_recommend_in_head", None)
+        if r_head is not None:
+            # recommend_step: the classifier's scores ranked into the caller's [G, k] buffers, ids in y's label space (the scores
+            # and shift metric_step ranks: log_softmax and unshifted for toyotagraph, logits and column + 1 otherwise)
+            ids, vals, work = r_head
+            W, b = self.out_proj.weight, self.out_proj.bias
+            logits = ops.skinny_linear(tok, W, b) if ops.skinny_linear_ok(tok, W) else self.out_proj(tok)
+            scores = torch.log_softmax(logits.float(), dim=1) if toyota else logits
+            ops.topk_rows(scores, ids.shape[1], col_offset=0 if toyota else 1, work=work, out=(ids, vals))
+            return [None, None]
         if y_head is not None and not toyota and ops.skinny_linear_gtl_ok(tok, self.out_proj.weight):
             # training_step: the classifier and GradientTailLoss(alpha = 0.2) on y - 1 (:1394, :1446-1460) in ONE launch; the
             # logits are never stored
@@ -622,6 +632,28 @@ class Graphormer(nn.Module):
             finally:
                 self._metrics_in_head = None
         return acc
+
+    def recommend_step(self, batched_data, ids, vals, work=None):
+        """The batch's top-k next POIs, best first, into ids [G, k] int64 / vals [G, k] f32 (k = ids.shape[1] <= ops.TOPK_MAX) on
+        the device: the scores metric_step ranks (logits; log_softmax for toyotagraph) in ops.topk_rows' order, so equal scores
+        list the lower POI first and `y in ids[:, :k]` is exactly the hit ACC@k counts.  ids are in batched_data.y's label space:
+        column + 1 for foursquaregraph / gowalla (whose test_step ranks against y - 1), the column itself for toyotagraph.  Eval
+        mode, under no_grad; nothing else is stored.  `work`: ops.topk_rows' buffer."""
+        if self.training:
+            raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
+        with torch.no_grad():
+            self._recommend_in_head = (ids, vals, work)
+            try:
+                self(batched_data)
+            finally:
+                self._recommend_in_head = None
+        return ids, vals
+
+    def recommend(self, dataset, collator, k=20, **kw):
+        """train.PredictLoop(self, collator, dataset, k=k, **kw).run(): (sample_index [n], ids [n, k], vals [n, k]) on the device."""
+        from .train import PredictLoop
+        max_batches = kw.pop("max_batches", None)
+        return PredictLoop(self, collator, dataset, k=k, **kw).run(max_batches=max_batches)
 
     def evaluate(self, dataset, collator, **kw):
         """train.EvalLoop(self, collator, dataset, **kw).run(): the reference's validation / test protocol over a whole split."""

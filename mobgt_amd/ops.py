@@ -991,6 +991,60 @@ def skinny_linear_rank_metrics(x, weight, bias, target, acc, target_offset=0, wo
     return acc
 
 
+TOPK_MAX = 64                # the largest k mobgt_topk_rows takes
+_TOPK_WORK, _TOPK_WORK_OLD = {}, []
+
+
+def topk_work_bytes(G, V, k):
+    return int(_lib.lib().mobgt_topk_work_bytes(G, V, k))
+
+
+def topk_rows(scores, k, col_offset=0, work=None, out=None):
+    """(ids [G, k] int64, vals [G, k]) = the stable descending sort of each row of scores [G, V], first k entries, with
+    ids = column + col_offset: torch.sort(scores, dim=1, descending=True, stable=True)[:, :k] bit for bit -- equal scores in
+    ascending column order (the ACC@k tie rule of target_rank / rank_metrics), -0.0 tied with +0.0, NaN first.
+    CUDA f32 scores (row stride free, unit column stride): mobgt_topk_rows, two launches, no host read; 1 <= k <= TOPK_MAX.
+    Other inputs take the torch.sort slice itself.  `work`: a device buffer of topk_work_bytes(G, V, k) bytes (default: one per
+    stream); `out`: (ids, vals) to write into, contiguous [G, k] int64 / f32 on the scores' device."""
+    G, V = scores.shape
+    k = int(k)
+    if not 1 <= k <= V:
+        raise ValueError(f"topk_rows: k = {k} outside [1, {V}]")
+    if not (scores.is_cuda and scores.dtype == torch.float32):
+        vals, idx = torch.sort(scores, dim=1, descending=True, stable=True)
+        ids, vals = idx[:, :k] + int(col_offset), vals[:, :k]
+        if out is None:
+            return ids, vals
+        out[0].copy_(ids)
+        out[1].copy_(vals)
+        return out
+    if scores.stride(1) != 1 or scores.stride(0) < V:
+        scores = scores.contiguous()
+    if out is None:
+        out = (torch.empty(G, k, dtype=torch.int64, device=scores.device), torch.empty(G, k, dtype=torch.float32, device=scores.device))
+    ids, vals = out
+    assert ids.is_cuda and vals.is_cuda and ids.dtype == torch.int64 and vals.dtype == torch.float32 and ids.is_contiguous() \
+        and vals.is_contiguous() and ids.shape == (G, k) and vals.shape == (G, k), "topk_rows: out = ([G, k] int64, [G, k] f32)"
+    if G == 0:
+        return out
+    n = topk_work_bytes(G, V, k)
+    if work is not None:
+        assert work.is_cuda and work.numel() * work.element_size() >= n, f"topk_rows: work buffer of {n} bytes needed"
+    else:
+        key = (scores.device, torch.cuda.current_stream(scores.device).stream_id)
+        work = _TOPK_WORK.get(key)
+        if work is None or work.numel() < n:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("topk_rows: no work buffer of this size on this stream yet -- pass `work` or run the call "
+                                   "once eagerly before capturing it")
+            if work is not None:
+                _TOPK_WORK_OLD.append(work)           # (a captured graph may still name it)
+            work = _TOPK_WORK[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=scores.device)
+    check(_lib.lib().mobgt_topk_rows(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(ids), _p(vals), _p(work),
+                                     _stream()), "mobgt_topk_rows")
+    return out
+
+
 def node_index(x, time_normal, poi2cat, rows_only, in_degree=None, out_degree=None):
     """Row indices of the node-feature gathers (model_fqandtoyo.py:1259-1264, 1287-1298) in one launch.
     x [G,N] int64/int32 POI ids, time_normal [G,N] f32 -> (idx [8,G,N] int64, real [G,N] f32); rows of idx:

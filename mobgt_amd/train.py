@@ -15,6 +15,7 @@
   (static shapes per pre-collated batch); the learning rate and the dropout seed live in device scalars
   so a replay sees new values without re-capture.
 """
+import contextlib
 import os
 
 import torch
@@ -1041,12 +1042,16 @@ class _StagedBatches:
         if bad:
             raise IndexError(f"batch.{bad[0]} has index {bad[1]}, out of range for a table of {bad[2]} rows")
 
+    def _kept(self, traj):
+        """Whether a trajectory enters a batch: longer ones than collator.max_node are dropped (as the reference's collator does)."""
+        return traj is not None and len(traj["node_name"]) <= self.collator.max_node
+
     def _stage(self, ids):
         """Host half of a step's input: raw trajectories -> the bucket's pinned buffer -> async copy to a device staging
         buffer on the copy stream.  Returns (slot, stage)."""
         from .data import bucket_nodes
         trajs = [self.dataset[i] for i in ids]
-        trajs = [t for t in trajs if t is not None and len(t["node_name"]) <= self.collator.max_node]
+        trajs = [t for t in trajs if self._kept(t)]
         G = len(trajs)
         if G == 0:
             return None                                # (every trajectory filtered out: the reference's collator skips such a batch too, collator.py:313)
@@ -1200,10 +1205,18 @@ class EvalLoop(_StagedBatches):
 
     def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
                  side_collate=True):
-        from .data import BUCKETS
         from . import metrics
         if not hasattr(model, "metric_step"):
             raise TypeError("EvalLoop: the model has no metric_step (the fq model, model_fqandtoyo.Graphormer)")
+        self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
+        self.captures = 0                                   # graphs captured so far (a replayed run captures none)
+        self.acc = metrics.new_accumulator(self.device)
+        self._scratch = metrics.new_accumulator(self.device)                          # warm-up passes count nowhere
+        V = model.out_proj.out_features
+        self.work = torch.empty(ops.rank_metrics_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
+
+    def _setup(self, model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate):
+        from .data import BUCKETS
         self.model, self.collator, self.dataset = model, collator, dataset
         self.batch_size = int(batch_size)
         self.buckets = tuple(buckets or BUCKETS)
@@ -1217,11 +1230,6 @@ class EvalLoop(_StagedBatches):
         self.side_collate = bool(side_collate)
         self.slots, self.limits, self.graphs = {}, None, {}
         self._graph_ptrs = None
-        self.captures = 0                                   # graphs captured so far (a replayed run captures none)
-        self.acc = metrics.new_accumulator(self.device)
-        self._scratch = metrics.new_accumulator(self.device)                          # warm-up passes count nowhere
-        V = model.out_proj.out_features
-        self.work = torch.empty(ops.rank_metrics_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
 
     def batches(self):
         from .data import shard_indices
@@ -1286,13 +1294,12 @@ class EvalLoop(_StagedBatches):
         for layer in layers:                                # (a pack is good for the forward that follows a refresh only)
             layer._packed_fresh = layer._packed_t_fresh = False
 
-    def run(self, max_batches=None):
-        """One pass over this rank's part of the split -> dict of metrics.evaluate_outputs' keys + "n" (samples counted)."""
-        from . import metrics
+    @contextlib.contextmanager
+    def _evaluating(self):
+        """Eval mode under no_grad with the weights refreshed and frozen for the captured forwards; on the way out the model's
+        mode, the layers' flags and the forward state the trainer's next step reads are put back, and parked work left behind
+        is refused."""
         model = self.model
-        batches = self.batches()
-        if max_batches is not None:
-            batches = batches[:max_batches]
         layers = list(getattr(model, "layers", []))
         was_training = model.training
         frozen = [getattr(l, "_weights_frozen", False) for l in layers]
@@ -1308,21 +1315,7 @@ class EvalLoop(_StagedBatches):
                 if ptrs != self._graph_ptrs:
                     self.graphs.clear()
                     self._graph_ptrs = ptrs
-                self.acc.zero_()
-                nxt = self._stage(batches[0]) if batches else None
-                for j in range(len(batches)):
-                    cur = nxt
-                    if cur is not None:
-                        self._launch(*cur)                   # asynchronous: the GPU evaluates batch j ...
-                    nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None     # ... while the host packs j + 1
-                if self.world > 1 and dist.is_available() and dist.is_initialized():
-                    if dist.get_backend() == "gloo":
-                        host = self.acc.cpu()
-                        dist.all_reduce(host)
-                        self.acc.copy_(host)
-                    else:
-                        dist.all_reduce(self.acc)
-                out = metrics.finalize(self.acc)              # the one host read
+                yield
         finally:
             for l, f in zip(layers, frozen):
                 l._weights_frozen = f
@@ -1335,5 +1328,97 @@ class EvalLoop(_StagedBatches):
             model.train(was_training)
         left = ops.step_state_leftovers()
         if left:
-            raise RuntimeError(f"EvalLoop: the evaluation left parked work behind {left}")
+            raise RuntimeError(f"{type(self).__name__}: the evaluation left parked work behind {left}")
+
+    def run(self, max_batches=None):
+        """One pass over this rank's part of the split -> dict of metrics.evaluate_outputs' keys + "n" (samples counted)."""
+        from . import metrics
+        batches = self.batches()
+        if max_batches is not None:
+            batches = batches[:max_batches]
+        with self._evaluating():
+            self.acc.zero_()
+            nxt = self._stage(batches[0]) if batches else None
+            for j in range(len(batches)):
+                cur = nxt
+                if cur is not None:
+                    self._launch(*cur)                   # asynchronous: the GPU evaluates batch j ...
+                nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None     # ... while the host packs j + 1
+            if self.world > 1 and dist.is_available() and dist.is_initialized():
+                if dist.get_backend() == "gloo":
+                    host = self.acc.cpu()
+                    dist.all_reduce(host)
+                    self.acc.copy_(host)
+                else:
+                    dist.all_reduce(self.acc)
+            out = metrics.finalize(self.acc)              # the one host read
         return out
+
+
+class PredictLoop(EvalLoop):
+    """Top-k next-POI recommendations over a whole split (Graphormer.recommend_step) on EvalLoop's device data path: the eval
+    loader's order and sharding, EpochLoop's buckets and staging, one captured graph per (G, bucket, ops.SAFE_FORMS[0]) -- eager
+    for collators whose finish needs torch ops (S-BIG) -- and the weights as they are when run() starts.
+
+    A graph writes its batch's [G, k] ids / vals into buffers of its own (fixed pointers); a device-to-device copy on the same
+    stream, outside the graph, then moves them to the batch's rows of the result.  Trajectories over collator.max_node, which
+    the evaluation drops, keep ids -1 and vals -inf.  Gathering the ranks' shards is left to the caller."""
+
+    def __init__(self, model, collator, dataset, k=20, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
+                 side_collate=True):
+        if not hasattr(model, "recommend_step"):
+            raise TypeError("PredictLoop: the model has no recommend_step (the fq model, model_fqandtoyo.Graphormer)")
+        V = model.out_proj.out_features
+        self.k = int(k)
+        if not 1 <= self.k <= min(ops.TOPK_MAX, V):
+            raise ValueError(f"PredictLoop: k = {k} outside [1, {min(ops.TOPK_MAX, V)}]")
+        self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
+        self.captures = 0
+        self.acc = self._scratch = None                     # (EvalLoop._launch passes them to _forward, which ignores them)
+        self.outs = {}                                      # (G, N) -> the [G, k] buffers its graphs write
+        self._out = None
+        self.work = torch.empty(ops.topk_work_bytes(self.batch_size, V, self.k), dtype=torch.uint8, device=self.device)
+
+    def _forward(self, batch, _acc):
+        b = self.collator.finish(batch) if isinstance(batch, dict) else batch
+        self.model.recommend_step(b, *self._out, work=self.work)
+
+    def _launch(self, slot, st):
+        key = (slot["layout"].G, slot["layout"].N)
+        if key not in self.outs:
+            G = key[0]
+            self.outs[key] = (torch.empty(G, self.k, dtype=torch.int64, device=self.device),
+                              torch.empty(G, self.k, dtype=torch.float32, device=self.device))
+        self._out = self.outs[key]
+        super()._launch(slot, st)
+        return self._out
+
+    def run(self, max_batches=None):
+        """One pass over this rank's part of the split -> (sample_index [n] int64, ids [n, k] int64, vals [n, k] f32), device
+        tensors in batch order, no host read."""
+        batches = self.batches()
+        if max_batches is not None:
+            batches = batches[:max_batches]
+        flat = [i for b in batches for i in b]
+        sample_index = torch.tensor(flat, dtype=torch.int64).to(self.device)
+        ids = torch.full((len(flat), self.k), -1, dtype=torch.int64, device=self.device)
+        vals = torch.full((len(flat), self.k), float("-inf"), dtype=torch.float32, device=self.device)
+        with self._evaluating():
+            nxt = self._stage(batches[0]) if batches else None
+            off = 0
+            for j, b in enumerate(batches):
+                cur = nxt
+                if cur is not None:
+                    bi, bv = self._launch(*cur)          # asynchronous: the GPU ranks batch j ...
+                    rows = [off + i for i, t in enumerate(b) if self._kept(self.dataset[t])]
+                    r = 0
+                    while r < len(rows):                 # runs of kept rows (one run unless a trajectory was dropped)
+                        e = r + 1
+                        while e < len(rows) and rows[e] == rows[e - 1] + 1:
+                            e += 1
+                        ids[rows[r]:rows[e - 1] + 1].copy_(bi[r:e], non_blocking=True)
+                        vals[rows[r]:rows[e - 1] + 1].copy_(bv[r:e], non_blocking=True)
+                        r = e
+                nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None     # ... while the host packs j + 1
+                off += len(b)
+        return sample_index, ids, vals

@@ -1,0 +1,102 @@
+"""Top-k recommendation timings (ops.topk_rows, train.PredictLoop); prints one JSON line per measurement.
+
+  kernel  G = 1 and 16 rows, V = 3 680 / 7 857 / 20 000 / 100 001 columns, k = 1 / 10 / 20 / 64: the kernel pair
+          (mobgt_topk_rows), torch.topk, and the stable torch.sort slice -- the only torch route with topk_rows' tie order;
+          CUDA-event time per call over a replayed graph of `--reps` calls, the best of 5 replays;
+  loop    check-ins / s of PredictLoop.run(k = 20) and EvalLoop.run() at S-FSQ (mobgt_amd/workloads.py), batches of 16, captured
+          graphs, after one warm pass that captures them.
+
+  python tools/topk_bench.py [--part kernel|loop|all] [--batches N] [--reps N]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from mobgt_amd import ops, workloads  # noqa: E402
+from mobgt_amd.train import EvalLoop, PredictLoop  # noqa: E402
+
+DEV = "cuda"
+
+
+def _per_call_us(fn, reps):
+    fn()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        for _ in range(reps):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        b.synchronize()
+        best = min(best, a.elapsed_time(b) * 1e3 / reps)
+    return best
+
+
+def _time(fn, reps):
+    try:
+        return _per_call_us(fn, reps)
+    except RuntimeError as e:                                    # (a torch route that cannot be captured: say so, keep going)
+        return f"error: {str(e).splitlines()[0]}"
+
+
+def bench_kernel(G, V, k, reps):
+    gen = torch.Generator(device=DEV).manual_seed(V + k)
+    x = torch.randn(G, V, device=DEV, generator=gen)
+    out = (torch.empty(G, k, dtype=torch.int64, device=DEV), torch.empty(G, k, device=DEV))
+    work = torch.empty(ops.topk_work_bytes(G, V, k), dtype=torch.uint8, device=DEV)
+    ours = ops.topk_rows(x, k, work=work, out=out)
+    want = torch.sort(x, dim=1, descending=True, stable=True)
+    same = bool(torch.equal(ours[0], want[1][:, :k]) and torch.equal(ours[1], want[0][:, :k]))
+    return dict(part="kernel", G=G, V=V, k=k, same_as_stable_sort=same,
+                topk_rows_us=_per_call_us(lambda: ops.topk_rows(x, k, work=work, out=out), reps),
+                torch_topk_us=_time(lambda: torch.topk(x, k, dim=1), reps),
+                stable_sort_us=_time(lambda: torch.sort(x, dim=1, descending=True, stable=True), reps))
+
+
+def bench_loop(n_batches):
+    uni, model, coll = workloads.build("fsq", DEV, seed=1)
+    data = [t for trajs in workloads.make_pool("fsq", n_batches, 16, uni, seed0=4242) for t in trajs]
+    res = dict(part="loop", workload="fsq", samples=len(data))
+    for name, loop in (("predictloop", PredictLoop(model, coll, data, k=20, batch_size=16)),
+                       ("evalloop", EvalLoop(model, coll, data, batch_size=16))):
+        loop.run()                                               # captures every bucket's graph
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        loop.run()
+        torch.cuda.synchronize()
+        res[name + "_checkins_per_s"] = len(data) / (time.perf_counter() - t0)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--part", default="all", choices=("kernel", "loop", "all"))
+    ap.add_argument("--batches", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=50)
+    a = ap.parse_args()
+    if a.part in ("kernel", "all"):
+        for G in (1, 16):
+            for V in (3680, 7857, 20000, 100001):
+                for k in (1, 10, 20, 64):
+                    print(json.dumps(bench_kernel(G, V, k, a.reps)), flush=True)
+    if a.part in ("loop", "all"):
+        print(json.dumps(bench_loop(a.batches)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
