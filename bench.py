@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
-"""Headline benchmark: check-ins/sec of one MobGT train step (+ attention-kernel HBM GB/s vs roofline).
+"""Headline benchmark: check-ins/sec of one MobGT train step.
 
-    python bench.py --gpus N --steps K --warmup W [--workload fsq|gow|big]
+    python bench.py --gpus N --steps K --warmup W [--workload fsq|gow|big] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the result line; nothing else.
+`--full` adds every other leg behind the timed steps: the 200-step and grouped-replay runs, the exposed all-reduce, the
+fresh-batch loop, attention / chain rooflines with their PMC counters, the Gowalla tail, oracle parity, the CPU baseline and
+(S-FSQ) the secondary workloads as child runs.
 
 With N > 1 and no torch.distributed environment the script launches itself as N ranks (one process per GPU,
 `python -m torch.distributed.run --nproc-per-node N`); it can equally be started under torch.distributed.run by the caller.
@@ -49,6 +54,10 @@ def parse():
     ap.add_argument("--force-comm", action="store_true",
                     help="N = 1 only: a process group of ONE rank over RCCL, the step in its data-parallel form (layer-wise buckets, "
                          "all-reduces on RCCL's stream beside the replays): what the multi-rank structure costs without a wire")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg of the benchmark as well (long and grouped runs, exposed "
+                         "all-reduce, fresh-batch loop, rooflines, Gowalla tail, parity, CPU baseline, secondary workloads); "
+                         "the --no-* switches below turn single legs of a --full run off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the eval-step comparison with the oracle")
     ap.add_argument("--no-stress", action="store_true", help="skip the c5-shape attention roofline measurements")
@@ -347,7 +356,7 @@ def run_sub_workloads(args):
     import shutil
     import tempfile
     me = os.path.abspath(__file__)
-    common = ["--gpus", "1", "--no-sub", "--no-cpu-baseline", "--no-stress", "--no-loop", "--no-live-pmc", "--seed", str(args.seed)]
+    common = ["--gpus", "1", "--full", "--no-sub", "--no-cpu-baseline", "--no-stress", "--no-loop", "--no-live-pmc", "--seed", str(args.seed)]
     specs = {"gow": ["--workload", "gow", "--steps", str(args.sub_steps), "--warmup", "10"],
              "stock": ["--variant", "stock", "--steps", str(args.sub_steps), "--warmup", "10"],
              "big": ["--workload", "big", "--steps", str(max(args.sub_steps // 10, 5)), "--warmup", "3"]}
@@ -932,10 +941,10 @@ def main():
     if loss != loss or abs(loss) == float("inf"):
         raise SystemExit(f"bench.py: training diverged (final loss {loss}) -- the timing would be meaningless")
     # A short timed region (the driver's default call asks for 20 steps = 15 ms of work) is honoured exactly -- `value` is
-    # those K steps -- and a 200-step measurement of the same loop is reported beside it so that the line can be judged
+    # those K steps -- and (--full) a 200-step measurement of the same loop is reported beside it so that the line can be judged
     # against run-to-run noise
     long_run = None
-    if args.steps < 100:
+    if args.full and args.steps < 100:
         k_long = 200
         torch.cuda.synchronize()
         if ddp:
@@ -957,7 +966,7 @@ def main():
     # with EIGHT steps per graph replay (train.TrainStep.step_group: nothing of a step lives on the host, so k steps can be one
     # graph) against the one-step replays above.  Reported beside the headline, which stays on one replay per step.
     grouped_run = None
-    if (not args.no_graph and name != "big" and getattr(ts, "fused_opt", False) and ts.sched_dev is not None
+    if (args.full and not args.no_graph and name != "big" and getattr(ts, "fused_opt", False) and ts.sched_dev is not None
             and os.environ.get("MOBGT_BENCH_NO_GROUPED") != "1"):
         try:
             kg, n_g = 8, 200
@@ -1003,6 +1012,7 @@ def main():
         comm_backend = str(dist.get_backend())
         comm_ranks = int(one.item())                 # ranks that took part in an all-reduce on the data-path backend
         rccl_ranks = comm_ranks if comm_backend == "nccl" else None     # ("nccl" IS RCCL on ROCm; a gloo run is not one)
+    if ddp and args.full:
         # exposed all-reduce time: the same steps once more with the gradient exchange switched off
         k2 = min(args.steps, 100)
         times = []
@@ -1022,7 +1032,30 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         exposed_us = float((tt[0] - tt[1]).item()) * 1e6
 
-    if rank == 0:
+    # the result line; the legs of a --full run fill their keys below (a plain run leaves them None)
+    io_dt = torch.bfloat16 if (bf16 and args.gemm_dtype == "bf16") else torch.float32
+    G_total = args.batch_size * world
+    out = {
+        "metric": "check-ins/sec (train step)", "value": G_total * args.steps / elapsed, "unit": "check-ins/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": workloads.describe(name, args.pois, args.variant), "variant": args.variant,
+                   "global_batch": G_total, "per_gpu_batch": args.batch_size,
+                   "padded_nodes_per_batch": [s[1] - 1 for s in shapes], "parallelism": f"dp{world}",
+                   "gemm_autotune": "torch TunableOp (hipBLASLt algorithm per shape)" if os.environ.get("PYTORCH_TUNABLEOP_ENABLED") == "1" else "off",
+                   "hip_graphs": not args.no_graph, "fused_encoder_layers": not args.unfused,
+                   "precision": {"attention_mfma_operands": args.dtype, "attn_bias": args.dtype,
+                                 "attention_io": "bf16" if io_dt == torch.bfloat16 else "f32",
+                                 "gcn_adjacency_product": args.dtype, "library_gemms": args.gemm_dtype if bf16 else "f32",
+                                 "accumulate_softmax_layernorm_adamw": "f32"}},
+        "final_loss": loss, "ms_per_step_chunks": [round(c, 4) for c in chunk_ms], "host_stalls": host_stalls, "long_run": long_run, "grouped_run": grouped_run,
+        "value_with_collate": None,
+        "comm_backend": comm_backend, "comm_ranks": comm_ranks, "grad_comm_dtype": args.grad_comm if ddp else None, "forced_comm": force_comm or None, "ddp_one_graph": bool(getattr(ts, "one_graph", False)) if ddp else None, "ddp_form": ddp_form, "ddp_form_ms_per_step": ddp_form_ms, "rccl_ranks": rccl_ranks, "allreduce_exposed_us": exposed_us,
+        "parity": None, "roofline": None, "roofline_chain": None, "roofline_stress": None, "roofline_stress_bwd": None,
+        "roofline_gow_tail": None,
+        "cpu_baseline": None, "workloads": None,
+    }
+    if rank == 0 and args.full:
         m = w["model"]
         H, C = m["num_heads"], m["hidden_dim"] + (0 if stock else 64)
         # (round 4: this leg runs FIRST, right behind the timed region.  Behind the roofline legs below -- graph-timed attention /
@@ -1043,7 +1076,6 @@ def main():
             except Exception as e:                       # never lose the headline line over the secondary figure
                 with_collate = dict(error=repr(e))
         d = C // H
-        io_dt = torch.bfloat16 if (bf16 and args.gemm_dtype == "bf16") else torch.float32
         b_dt = torch.bfloat16 if bf16 else torch.float32
         s_x, s_b = (2 if io_dt == torch.bfloat16 else 4), (2 if bf16 else 4)
         s_g = 2 if bf16 else 8
@@ -1179,27 +1211,10 @@ def main():
         subs = None
         if world == 1 and not force_comm and name == "fsq" and not stock and not args.no_sub and not args.no_graph and not args.unfused and bf16:
             subs = run_sub_workloads(args)
-        G_total = args.batch_size * world
-        out = {
-            "metric": "check-ins/sec (train step)", "value": G_total * args.steps / elapsed, "unit": "check-ins/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": workloads.describe(name, args.pois, args.variant), "variant": args.variant,
-                       "global_batch": G_total, "per_gpu_batch": args.batch_size,
-                       "padded_nodes_per_batch": [s[1] - 1 for s in shapes], "parallelism": f"dp{world}",
-                       "gemm_autotune": "torch TunableOp (hipBLASLt algorithm per shape)" if os.environ.get("PYTORCH_TUNABLEOP_ENABLED") == "1" else "off",
-                       "hip_graphs": not args.no_graph, "fused_encoder_layers": not args.unfused,
-                       "precision": {"attention_mfma_operands": args.dtype, "attn_bias": args.dtype,
-                                     "attention_io": "bf16" if io_dt == torch.bfloat16 else "f32",
-                                     "gcn_adjacency_product": args.dtype, "library_gemms": args.gemm_dtype if bf16 else "f32",
-                                     "accumulate_softmax_layernorm_adamw": "f32"}},
-            "final_loss": loss, "ms_per_step_chunks": [round(c, 4) for c in chunk_ms], "host_stalls": host_stalls, "long_run": long_run, "grouped_run": grouped_run,
-            "value_with_collate": with_collate,
-            "comm_backend": comm_backend, "comm_ranks": comm_ranks, "grad_comm_dtype": args.grad_comm if ddp else None, "forced_comm": force_comm or None, "ddp_one_graph": bool(getattr(ts, "one_graph", False)) if ddp else None, "ddp_form": ddp_form, "ddp_form_ms_per_step": ddp_form_ms, "rccl_ranks": rccl_ranks, "allreduce_exposed_us": exposed_us,
-            "parity": parity, "roofline": roof, "roofline_chain": roofc, "roofline_stress": roof5, "roofline_stress_bwd": roof5b,
-            "roofline_gow_tail": gow_tail,
-            "cpu_baseline": cpu, "workloads": subs,
-        }
+        out.update({"value_with_collate": with_collate, "parity": parity, "roofline": roof, "roofline_chain": roofc,
+                    "roofline_stress": roof5, "roofline_stress_bwd": roof5b, "roofline_gow_tail": gow_tail,
+                    "cpu_baseline": cpu, "workloads": subs})
+    if rank == 0:
         real_stdout.write(json.dumps(out) + "\n")
         real_stdout.flush()
     if ddp:

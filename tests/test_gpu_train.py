@@ -267,7 +267,7 @@ def test_bench_launches_two_ranks_and_reports_them(tmp_path):
         env.pop(k, None)
     if torch.cuda.device_count() < 2:
         env["MOBGT_TEST_SHARED_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
            "--no-stress", "--no-parity", "--no-gemm-autotune", "--n-batches", "2"]
     r = subprocess.run(cmd, env=env, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     out = r.stdout.decode(errors="replace")
