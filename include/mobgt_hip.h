@@ -359,6 +359,18 @@ int mobgt_skinny_linear_rank_metrics(const float* x, const float* w, const float
 int64_t mobgt_topk_work_bytes(int64_t G, int64_t V, int64_t k);
 int mobgt_topk_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, int64_t* ids, float* vals,
                     void* work, void* stream);
+/* mobgt_topk_rows restricted to each row's candidates (next-new-POI lists, a candidate set).  Column c of row g is a candidate when
+ *   - allow is NULL, or bit c & 31 of allow[c >> 5] is set (ceil(V / 32) packed words, shared by every row), and
+ *   - excl is NULL, or no entry p of excl[g, 0:n_excl_cols] has p != 0 && p - excl_offset == c.  excl is [G, ld_excl] (row
+ *     stride ld_excl >= n_excl_cols elements) of dtype excl_dtype (MOBGT_I64 / MOBGT_I32); 0 is padding; ids mapping outside
+ *     [0, V) are ignored.
+ * ids[g, :k] / vals[g, :k] are the first k entries of mobgt_topk_rows' order (the stable descending sort, bit for bit) over the
+ * candidates only; a row with m < k candidates has ids -1 and vals -inf from position m on (a candidate scoring -inf keeps its id).
+ * Both NULL: mobgt_topk_rows' output.  Argument limits, `work` (mobgt_topk_work_bytes) and the two graph-capturable launches as
+ * mobgt_topk_rows; a bad excl_dtype is MOBGT_EDTYPE. */
+int mobgt_topk_rows_masked(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, const uint32_t* allow,
+                           const void* excl, int excl_dtype, int64_t ld_excl, int64_t n_excl_cols, int64_t excl_offset, int64_t* ids,
+                           float* vals, void* work, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused elementwise / normalisation pieces of EncoderLayer.forward between the library GEMMs

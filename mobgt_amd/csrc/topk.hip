@@ -15,6 +15,11 @@
 // 64 new keys that can change the top k (ballot against the k-th key) is sorted by a 21-stage bitonic network across lanes,
 // reversed, folded in by a lane-wise max (the best 64 of both lists, as a bitonic sequence) and re-sorted by a 6-stage merge.
 // The waves of a workgroup then fold their lists pairwise through LDS.
+//
+// mobgt_topk_rows_masked restricts each row to its candidates (an allow bitmap shared by the rows, a per-row list of excluded
+// ids).  A non-candidate takes the key 0, which is below every real key, so the same selection never picks it: launch 1 builds
+// its chunk's 32 candidate words in LDS (the allow words with the row's excluded ids cleared) before the ballot, and launch 2
+// writes a final key 0 -- a row with fewer than k candidates -- as id -1, val -inf.  No extra launch, no [G, V / 32] buffer.
 #include "common.h"
 #include "../../include/mobgt_hip.h"
 
@@ -86,10 +91,21 @@ __device__ __forceinline__ uint64_t block_fold(uint64_t top, uint64_t* s_keys, i
     return top;
 }
 
-// launch 1: grid (chunks, G); the chunk's k best keys, descending, -> work[g][chunk][0, k) (0 = no column)
+// The candidate restriction of mobgt_topk_rows_masked: allow bits (NULL: all) and a per-row list of excluded ids (NULL: none).
+struct TkMask {
+    const uint32_t* allow;                         // ceil(V / 32) words, bit c & 31 of word c >> 5 = column c may be listed
+    const void* excl;                              // [G, ld_excl] int32 / int64 ids; 0 = padding; id - excl_offset = column
+    int64_t ld_excl, n_excl, excl_offset;
+    int excl_i64;
+};
+
+// launch 1: grid (chunks, G); the chunk's k best keys, descending, -> work[g][chunk][0, k) (0 = no column).  MASK: columns that
+// are not candidates take the key 0 (below every real key), so they are never selected.
+template <bool MASK>
 __global__ __launch_bounds__(64 * TK_WAVES1) void topk_chunk_kernel(const float* __restrict__ scores, int64_t ld, int64_t V, int k,
-                                                                    uint64_t* __restrict__ work) {
+                                                                    uint64_t* __restrict__ work, TkMask m) {
     __shared__ uint64_t s_keys[TK_WAVES1 * 64];
+    __shared__ uint32_t s_ok[TK_CHUNK / 32];       // MASK: the chunk's candidate bits
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t g = blockIdx.y, nch = gridDim.x;
     const uint32_t* row = reinterpret_cast<const uint32_t*>(scores + g * ld);
@@ -99,6 +115,30 @@ __global__ __launch_bounds__(64 * TK_WAVES1) void topk_chunk_kernel(const float*
     for (int i = 0; i < TK_ITERS; ++i) {           // (all loads in flight before the first sort)
         const int64_t c = c0 + i * 64 * TK_WAVES1;
         key[i] = c < V ? tk_key(row[c], (uint32_t)c) : 0;
+    }
+    if constexpr (MASK) {
+        // the chunk's allow words, then the row's excluded ids that fall inside the chunk cleared (ids outside [0, V) land
+        // outside every chunk, or on columns >= V whose key is 0 already)
+        const int64_t base = (int64_t)blockIdx.x * TK_CHUNK;
+        if (threadIdx.x < TK_CHUNK / 32) {
+            const int64_t wi = base / 32 + threadIdx.x;
+            s_ok[threadIdx.x] = !m.allow ? ~0u : wi < (V + 31) / 32 ? m.allow[wi] : 0u;
+        }
+        __syncthreads();
+        if (m.excl) {
+            for (int64_t j = threadIdx.x; j < m.n_excl; j += 64 * TK_WAVES1) {
+                const int64_t p = m.excl_i64 ? reinterpret_cast<const int64_t*>(m.excl)[g * m.ld_excl + j]
+                                             : (int64_t)reinterpret_cast<const int32_t*>(m.excl)[g * m.ld_excl + j];
+                const uint64_t r = (uint64_t)p - (uint64_t)m.excl_offset - (uint64_t)base;     // (unsigned: no overflow)
+                if (p != 0 && r < (uint64_t)TK_CHUNK) atomicAnd(&s_ok[r >> 5], ~(1u << (r & 31)));
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < TK_ITERS; ++i) {
+            const int r = w * 64 + lane + i * 64 * TK_WAVES1;
+            if (!((s_ok[r >> 5] >> (r & 31)) & 1u)) key[i] = 0;
+        }
     }
     uint64_t top = 0, thr = 0;
 #pragma unroll
@@ -111,7 +151,9 @@ __global__ __launch_bounds__(64 * TK_WAVES1) void topk_chunk_kernel(const float*
     if (w == 0 && lane < k) work[(g * nch + blockIdx.x) * k + lane] = top;
 }
 
-// launch 2: one workgroup per row; wave w folds the chunk lists w, w + 16, ...; wave 0 writes the row's k results
+// launch 2: one workgroup per row; wave w folds the chunk lists w, w + 16, ...; wave 0 writes the row's k results.  MASK: a row
+// with m < k candidates ends in the key 0 from position m on, written as id -1, val -inf.
+template <bool MASK>
 __global__ __launch_bounds__(64 * TK_WAVES2) void topk_finish_kernel(const float* __restrict__ scores, int64_t ld, int64_t nch, int k,
                                                                      const uint64_t* __restrict__ work, int64_t col_offset,
                                                                      int64_t* __restrict__ ids, float* __restrict__ vals) {
@@ -129,6 +171,11 @@ __global__ __launch_bounds__(64 * TK_WAVES2) void topk_finish_kernel(const float
     top = block_fold<TK_WAVES2>(top, s_keys, w, lane);
     if (w == 0 && lane < k) {
         const uint32_t col = ~(uint32_t)top;       // (V >= k real keys per row: the first k are columns, never the 0 filler)
+        if (MASK && top == 0) {
+            ids[g * k + lane] = -1;
+            vals[g * k + lane] = -__builtin_inff();
+            return;
+        }
         ids[g * k + lane] = (int64_t)col + col_offset;
         reinterpret_cast<uint32_t*>(vals)[g * k + lane] = reinterpret_cast<const uint32_t*>(scores + g * ld)[col];   // the stored bits
     }
@@ -141,15 +188,42 @@ extern "C" int64_t mobgt_topk_work_bytes(int64_t G, int64_t V, int64_t k) {
     return 8 * G * tk_chunks(V) * k;
 }
 
-extern "C" int mobgt_topk_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, int64_t* ids,
-                               float* vals, void* work, void* stream) {
+namespace {
+
+int topk_launch(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, int64_t* ids, float* vals,
+                void* work, const TkMask& m, bool masked, void* stream) {
     if (G <= 0 || G > 65535 || V <= 0 || V >= (int64_t)INT32_MAX || k < 1 || k > TK_MAXK || k > V || ld < V) return MOBGT_EBADDIM;
     if (!scores || !ids || !vals || !work) return MOBGT_EBADDIM;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nch = tk_chunks(V);
     uint64_t* wk = reinterpret_cast<uint64_t*>(work);
-    hipLaunchKernelGGL(topk_chunk_kernel, dim3((unsigned)nch, (unsigned)G), dim3(64 * TK_WAVES1), 0, st, scores, ld, V, (int)k, wk);
-    hipLaunchKernelGGL(topk_finish_kernel, dim3((unsigned)G), dim3(64 * TK_WAVES2), 0, st, scores, ld, nch, (int)k,
-                       (const uint64_t*)wk, col_offset, ids, vals);
+    if (masked) {
+        hipLaunchKernelGGL(topk_chunk_kernel<true>, dim3((unsigned)nch, (unsigned)G), dim3(64 * TK_WAVES1), 0, st, scores, ld, V,
+                           (int)k, wk, m);
+        hipLaunchKernelGGL(topk_finish_kernel<true>, dim3((unsigned)G), dim3(64 * TK_WAVES2), 0, st, scores, ld, nch, (int)k,
+                           (const uint64_t*)wk, col_offset, ids, vals);
+    } else {
+        hipLaunchKernelGGL(topk_chunk_kernel<false>, dim3((unsigned)nch, (unsigned)G), dim3(64 * TK_WAVES1), 0, st, scores, ld, V,
+                           (int)k, wk, m);
+        hipLaunchKernelGGL(topk_finish_kernel<false>, dim3((unsigned)G), dim3(64 * TK_WAVES2), 0, st, scores, ld, nch, (int)k,
+                           (const uint64_t*)wk, col_offset, ids, vals);
+    }
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int mobgt_topk_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, int64_t* ids,
+                               float* vals, void* work, void* stream) {
+    return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, TkMask{}, false, stream);
+}
+
+extern "C" int mobgt_topk_rows_masked(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset,
+                                      const uint32_t* allow, const void* excl, int excl_dtype, int64_t ld_excl, int64_t n_excl_cols,
+                                      int64_t excl_offset, int64_t* ids, float* vals, void* work, void* stream) {
+    if (excl && (n_excl_cols < 0 || ld_excl < n_excl_cols)) return MOBGT_EBADDIM;
+    if (excl && excl_dtype != MOBGT_I64 && excl_dtype != MOBGT_I32) return MOBGT_EDTYPE;
+    const bool use_excl = excl && n_excl_cols > 0;
+    const TkMask m{allow, use_excl ? excl : nullptr, ld_excl, n_excl_cols, excl_offset, excl_dtype == MOBGT_I64};
+    return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, m, allow || use_excl, stream);
 }

@@ -669,6 +669,6 @@ class Graphormer(nn.Module):
         reference's model.py evaluates through Lightning's generic metric hooks, not test_epoch_end's ACC / NDCG / MRR."""
         raise NotImplementedError("metric_step / train.EvalLoop: the fq model (model_fqandtoyo.Graphormer) only")
 
-    def recommend_step(self, batched_data, ids, vals, work=None):
+    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None):
         """No counterpart in this variant either (see metric_step): the fq model's recommend_step ranks what its metrics rank."""
         raise NotImplementedError("recommend_step / train.PredictLoop: the fq model (model_fqandtoyo.Graphormer) only")

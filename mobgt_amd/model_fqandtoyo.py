@@ -554,11 +554,13 @@ class Graphormer(nn.Module):
         if r_head is not None:
             # recommend_step: the classifier's scores ranked into the caller's [G, k] buffers, ids in y's label space (the scores
             # and shift metric_step ranks: log_softmax and unshifted for toyotagraph, logits and column + 1 otherwise)
-            ids, vals, work = r_head
+            ids, vals, work, exclude_visited, allow = r_head
             W, b = self.out_proj.weight, self.out_proj.bias
             logits = ops.skinny_linear(tok, W, b) if ops.skinny_linear_ok(tok, W) else self.out_proj(tok)
             scores = torch.log_softmax(logits.float(), dim=1) if toyota else logits
-            ops.topk_rows(scores, ids.shape[1], col_offset=0 if toyota else 1, work=work, out=(ids, vals))
+            # (exclude_visited: x holds the trajectory's POI ids in y's label space, 0 = padding)
+            excl = batched_data.x.reshape(batched_data.x.shape[0], -1) if exclude_visited else None
+            ops.topk_rows(scores, ids.shape[1], col_offset=0 if toyota else 1, work=work, out=(ids, vals), allow=allow, exclude=excl)
             return [None, None]
         if y_head is not None and not toyota and ops.skinny_linear_gtl_ok(tok, self.out_proj.weight):
             # training_step: the classifier and GradientTailLoss(alpha = 0.2) on y - 1 (:1394, :1446-1460) in ONE launch; the
@@ -633,27 +635,33 @@ class Graphormer(nn.Module):
                 self._metrics_in_head = None
         return acc
 
-    def recommend_step(self, batched_data, ids, vals, work=None):
+    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None):
         """The batch's top-k next POIs, best first, into ids [G, k] int64 / vals [G, k] f32 (k = ids.shape[1] <= ops.TOPK_MAX) on
         the device: the scores metric_step ranks (logits; log_softmax for toyotagraph) in ops.topk_rows' order, so equal scores
         list the lower POI first and `y in ids[:, :k]` is exactly the hit ACC@k counts.  ids are in batched_data.y's label space:
         column + 1 for foursquaregraph / gowalla (whose test_step ranks against y - 1), the column itself for toyotagraph.  Eval
-        mode, under no_grad; nothing else is stored.  `work`: ops.topk_rows' buffer."""
+        mode, under no_grad; nothing else is stored.  `work`: ops.topk_rows' buffer.
+
+        exclude_visited: leave out the POIs of each trajectory (batched_data.x, the same label space as y) -- next *new* POI
+        lists.  allow: ops.pack_allow(candidate ids, V, offset) words (offset 0 for toyotagraph, else 1): only those POIs are
+        listed.  A row with fewer than k candidates ends in ids -1 / vals -inf."""
         if self.training:
             raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
         with torch.no_grad():
-            self._recommend_in_head = (ids, vals, work)
+            self._recommend_in_head = (ids, vals, work, bool(exclude_visited), allow)
             try:
                 self(batched_data)
             finally:
                 self._recommend_in_head = None
         return ids, vals
 
-    def recommend(self, dataset, collator, k=20, **kw):
-        """train.PredictLoop(self, collator, dataset, k=k, **kw).run(): (sample_index [n], ids [n, k], vals [n, k]) on the device."""
+    def recommend(self, dataset, collator, k=20, exclude_visited=False, candidates=None, **kw):
+        """train.PredictLoop(self, collator, dataset, k=k, exclude_visited=..., candidates=..., **kw).run(): (sample_index [n],
+        ids [n, k], vals [n, k]) on the device."""
         from .train import PredictLoop
         max_batches = kw.pop("max_batches", None)
-        return PredictLoop(self, collator, dataset, k=k, **kw).run(max_batches=max_batches)
+        return PredictLoop(self, collator, dataset, k=k, exclude_visited=exclude_visited, candidates=candidates,
+                           **kw).run(max_batches=max_batches)
 
     def evaluate(self, dataset, collator, **kw):
         """train.EvalLoop(self, collator, dataset, **kw).run(): the reference's validation / test protocol over a whole split."""

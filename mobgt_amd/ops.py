@@ -999,17 +999,65 @@ def topk_work_bytes(G, V, k):
     return int(_lib.lib().mobgt_topk_work_bytes(G, V, k))
 
 
-def topk_rows(scores, k, col_offset=0, work=None, out=None):
+def pack_allow(mask_or_ids, V, offset=0):
+    """The allow words of topk_rows / mobgt_topk_rows_masked: int32 [ceil(V / 32)], bit c & 31 of word c >> 5 set when column c
+    may be listed, on the input's device.  From a bool mask [V] over the columns, or from a 1-D integer tensor of ids in the
+    label space (column = id - offset; an id outside [0, V) after the shift is a ValueError, duplicates are fine)."""
+    V = int(V)
+    m = mask_or_ids
+    if m.dtype == torch.bool:
+        if m.dim() != 1 or m.numel() != V:
+            raise ValueError(f"pack_allow: a bool mask must be [{V}], got {tuple(m.shape)}")
+    else:
+        if m.dim() != 1 or m.dtype.is_floating_point or m.dtype.is_complex:
+            raise ValueError("pack_allow: ids must be a 1-D integer tensor")
+        cols = m.long() - int(offset)
+        if cols.numel() and bool(((cols < 0) | (cols >= V)).any()):
+            raise ValueError(f"pack_allow: ids outside [{offset}, {V + int(offset)}) (offset {offset})")
+        m = torch.zeros(V, dtype=torch.bool, device=m.device)
+        m[cols] = True
+    W = (V + 31) // 32
+    bits = torch.zeros(W * 32, dtype=torch.int64, device=m.device)
+    bits[:V] = m.long()
+    words = (bits.view(W, 32) << torch.arange(32, dtype=torch.int64, device=m.device)).sum(1)
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+
+
+def _candidates(G, V, allow, exclude, exclude_offset, device):
+    """[G, V] bool: the candidate columns of topk_rows' restricted form (see there)"""
+    ok = torch.ones(G, V, dtype=torch.bool, device=device)
+    if allow is not None:
+        w = allow.to(device=device, dtype=torch.int64)[torch.arange(V, device=device) >> 5]
+        ok &= ((w >> (torch.arange(V, device=device) & 31)) & 1).bool()[None, :]
+    if exclude is not None and exclude.numel():
+        e = exclude.to(device=device, dtype=torch.int64)
+        c = e - int(exclude_offset)
+        hit = (e != 0) & (c >= 0) & (c < V)
+        rows = torch.arange(G, device=device)[:, None].expand_as(c)
+        ok[rows[hit], c[hit]] = False
+    return ok
+
+
+def topk_rows(scores, k, col_offset=0, work=None, out=None, allow=None, exclude=None, exclude_offset=None):
     """(ids [G, k] int64, vals [G, k]) = the stable descending sort of each row of scores [G, V], first k entries, with
     ids = column + col_offset: torch.sort(scores, dim=1, descending=True, stable=True)[:, :k] bit for bit -- equal scores in
     ascending column order (the ACC@k tie rule of target_rank / rank_metrics), -0.0 tied with +0.0, NaN first.
     CUDA f32 scores (row stride free, unit column stride): mobgt_topk_rows, two launches, no host read; 1 <= k <= TOPK_MAX.
     Other inputs take the torch.sort slice itself.  `work`: a device buffer of topk_work_bytes(G, V, k) bytes (default: one per
-    stream); `out`: (ids, vals) to write into, contiguous [G, k] int64 / f32 on the scores' device."""
+    stream); `out`: (ids, vals) to write into, contiguous [G, k] int64 / f32 on the scores' device.
+
+    Restricted to candidates (next-new-POI lists, a candidate set): `allow` = pack_allow(...) words (columns whose bit is clear
+    are never listed) and / or `exclude` [G, n] int32 / int64 ids per row (entry p != 0 removes column p - exclude_offset from its
+    row; 0 is padding; ids outside [0, V) after the shift are ignored; exclude_offset defaults to col_offset).  The result is the
+    same order over the candidates only; a row with m < k candidates reads ids -1, vals -inf from position m on.  CUDA f32
+    scores: mobgt_topk_rows_masked (same two launches); other inputs: the torch statement of that contract."""
     G, V = scores.shape
     k = int(k)
     if not 1 <= k <= V:
         raise ValueError(f"topk_rows: k = {k} outside [1, {V}]")
+    if allow is not None or exclude is not None:
+        return _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude,
+                                 col_offset if exclude_offset is None else exclude_offset)
     if not (scores.is_cuda and scores.dtype == torch.float32):
         vals, idx = torch.sort(scores, dim=1, descending=True, stable=True)
         ids, vals = idx[:, :k] + int(col_offset), vals[:, :k]
@@ -1020,29 +1068,80 @@ def topk_rows(scores, k, col_offset=0, work=None, out=None):
         return out
     if scores.stride(1) != 1 or scores.stride(0) < V:
         scores = scores.contiguous()
+    ids, vals = out = _topk_out(scores, G, k, out)
+    if G == 0:
+        return out
+    work = _topk_work(scores, G, V, k, work)
+    check(_lib.lib().mobgt_topk_rows(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(ids), _p(vals), _p(work),
+                                     _stream()), "mobgt_topk_rows")
+    return out
+
+
+def _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude, exclude_offset):
+    G, V = scores.shape
+    if allow is not None:
+        assert allow.dtype == torch.int32 and allow.dim() == 1 and allow.numel() >= (V + 31) // 32, \
+            f"topk_rows: allow = pack_allow(..., {V}) words, int32 [{(V + 31) // 32}]"
+    if exclude is not None:
+        assert exclude.dim() == 2 and exclude.shape[0] == G and exclude.dtype in (torch.int32, torch.int64), \
+            f"topk_rows: exclude = [{G}, n] int32 / int64 ids"
+    if not (scores.is_cuda and scores.dtype == torch.float32):
+        # the contract in torch: the stable descending sort, then its candidates moved to the front in that order
+        sv, si = torch.sort(scores, dim=1, descending=True, stable=True)
+        ok = torch.gather(_candidates(G, V, allow, exclude, exclude_offset, scores.device), 1, si)
+        order = torch.sort((~ok).to(torch.uint8), dim=1, stable=True)[1][:, :k]
+        keep = torch.gather(ok, 1, order)
+        ids = torch.where(keep, torch.gather(si, 1, order) + int(col_offset), torch.full_like(order, -1))
+        vals = torch.where(keep, torch.gather(sv, 1, order), torch.full_like(order, float("-inf"), dtype=sv.dtype))
+        if out is None:
+            return ids, vals
+        out[0].copy_(ids)
+        out[1].copy_(vals)
+        return out
+    if scores.stride(1) != 1 or scores.stride(0) < V:
+        scores = scores.contiguous()
+    if allow is not None:
+        assert allow.is_cuda and allow.is_contiguous(), "topk_rows: allow words on the device, contiguous"
+    n_ex, ld_ex = 0, 0
+    if exclude is not None:
+        assert exclude.is_cuda, "topk_rows: exclude on the device"
+        if exclude.shape[1] and (exclude.stride(1) != 1 or exclude.stride(0) < exclude.shape[1]):
+            exclude = exclude.contiguous()
+        n_ex, ld_ex = exclude.shape[1], max(exclude.stride(0), exclude.shape[1])
+    ids, vals = out = _topk_out(scores, G, k, out)
+    if G == 0:
+        return out
+    work = _topk_work(scores, G, V, k, work)
+    check(_lib.lib().mobgt_topk_rows_masked(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
+                                            _p(exclude), _IT[exclude.dtype] if exclude is not None else I64, ld_ex, n_ex,
+                                            int(exclude_offset), _p(ids), _p(vals), _p(work), _stream()), "mobgt_topk_rows_masked")
+    return out
+
+
+def _topk_out(scores, G, k, out):
     if out is None:
         out = (torch.empty(G, k, dtype=torch.int64, device=scores.device), torch.empty(G, k, dtype=torch.float32, device=scores.device))
     ids, vals = out
     assert ids.is_cuda and vals.is_cuda and ids.dtype == torch.int64 and vals.dtype == torch.float32 and ids.is_contiguous() \
         and vals.is_contiguous() and ids.shape == (G, k) and vals.shape == (G, k), "topk_rows: out = ([G, k] int64, [G, k] f32)"
-    if G == 0:
-        return out
+    return out
+
+
+def _topk_work(scores, G, V, k, work):
     n = topk_work_bytes(G, V, k)
     if work is not None:
         assert work.is_cuda and work.numel() * work.element_size() >= n, f"topk_rows: work buffer of {n} bytes needed"
-    else:
-        key = (scores.device, torch.cuda.current_stream(scores.device).stream_id)
-        work = _TOPK_WORK.get(key)
-        if work is None or work.numel() < n:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("topk_rows: no work buffer of this size on this stream yet -- pass `work` or run the call "
-                                   "once eagerly before capturing it")
-            if work is not None:
-                _TOPK_WORK_OLD.append(work)           # (a captured graph may still name it)
-            work = _TOPK_WORK[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=scores.device)
-    check(_lib.lib().mobgt_topk_rows(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(ids), _p(vals), _p(work),
-                                     _stream()), "mobgt_topk_rows")
-    return out
+        return work
+    key = (scores.device, torch.cuda.current_stream(scores.device).stream_id)
+    work = _TOPK_WORK.get(key)
+    if work is None or work.numel() < n:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("topk_rows: no work buffer of this size on this stream yet -- pass `work` or run the call "
+                               "once eagerly before capturing it")
+        if work is not None:
+            _TOPK_WORK_OLD.append(work)           # (a captured graph may still name it)
+        work = _TOPK_WORK[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=scores.device)
+    return work
 
 
 def node_index(x, time_normal, poi2cat, rows_only, in_degree=None, out_degree=None):

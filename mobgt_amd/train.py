@@ -1362,10 +1362,14 @@ class PredictLoop(EvalLoop):
 
     A graph writes its batch's [G, k] ids / vals into buffers of its own (fixed pointers); a device-to-device copy on the same
     stream, outside the graph, then moves them to the batch's rows of the result.  Trajectories over collator.max_node, which
-    the evaluation drops, keep ids -1 and vals -inf.  Gathering the ranks' shards is left to the caller."""
+    the evaluation drops, keep ids -1 and vals -inf.  Gathering the ranks' shards is left to the caller.
+
+    A loop keeps one restriction for its lifetime: exclude_visited leaves out each trajectory's own POIs (next *new* POI lists);
+    candidates, a 1-D tensor of POI ids in y's label space, limits every list to them (packed once, here, into words the graphs
+    read at a fixed address).  Rows with fewer than k candidates end in ids -1 / vals -inf, as dropped trajectories do."""
 
     def __init__(self, model, collator, dataset, k=20, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
-                 side_collate=True):
+                 side_collate=True, exclude_visited=False, candidates=None):
         if not hasattr(model, "recommend_step"):
             raise TypeError("PredictLoop: the model has no recommend_step (the fq model, model_fqandtoyo.Graphormer)")
         V = model.out_proj.out_features
@@ -1373,6 +1377,11 @@ class PredictLoop(EvalLoop):
         if not 1 <= self.k <= min(ops.TOPK_MAX, V):
             raise ValueError(f"PredictLoop: k = {k} outside [1, {min(ops.TOPK_MAX, V)}]")
         self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
+        self.exclude_visited = bool(exclude_visited)
+        self.allow = None
+        if candidates is not None:
+            offset = 0 if getattr(model, "dataset_name", None) == "toyotagraph" else 1      # (recommend_step's label space)
+            self.allow = ops.pack_allow(torch.as_tensor(candidates).to(self.device), V, offset)
         self.captures = 0
         self.acc = self._scratch = None                     # (EvalLoop._launch passes them to _forward, which ignores them)
         self.outs = {}                                      # (G, N) -> the [G, k] buffers its graphs write
@@ -1381,7 +1390,7 @@ class PredictLoop(EvalLoop):
 
     def _forward(self, batch, _acc):
         b = self.collator.finish(batch) if isinstance(batch, dict) else batch
-        self.model.recommend_step(b, *self._out, work=self.work)
+        self.model.recommend_step(b, *self._out, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow)
 
     def _launch(self, slot, st):
         key = (slot["layout"].G, slot["layout"].N)

@@ -5,8 +5,12 @@
           CUDA-event time per call over a replayed graph of `--reps` calls, the best of 5 replays;
   loop    check-ins / s of PredictLoop.run(k = 20) and EvalLoop.run() at S-FSQ (mobgt_amd/workloads.py), batches of 16, captured
           graphs, after one warm pass that captures them.
+  masked  the restricted pair (mobgt_topk_rows_masked, k = 20) at the kernel leg's G and V: `exclude` lists as long as S-FSQ's
+          (256) and S-BIG's (784) trajectories, `allow` at 10 / 50 / 99 % density; next to mobgt_topk_rows and the torch route
+          (masked_fill(-inf) of a precomputed mask + the stable sort), timed as the kernel leg; then PredictLoop(k = 20) check-ins
+          / s with exclude_visited next to the plain loop at S-FSQ (both captured first, then the best of 5 alternated runs).
 
-  python tools/topk_bench.py [--part kernel|loop|all] [--batches N] [--reps N]
+  python tools/topk_bench.py [--part kernel|loop|masked|all] [--batches N] [--reps N]
 """
 import argparse
 import json
@@ -83,9 +87,56 @@ def bench_loop(n_batches):
     return res
 
 
+def bench_masked(G, V, k, reps):
+    gen = torch.Generator(device=DEV).manual_seed(V + k)
+    x = torch.randn(G, V, device=DEV, generator=gen)
+    out = (torch.empty(G, k, dtype=torch.int64, device=DEV), torch.empty(G, k, device=DEV))
+    work = torch.empty(ops.topk_work_bytes(G, V, k), dtype=torch.uint8, device=DEV)
+    res = dict(part="masked", G=G, V=V, k=k, topk_rows_us=_per_call_us(lambda: ops.topk_rows(x, k, work=work, out=out), reps))
+    same = True
+    for n, name in ((256, "exclude_fsq"), (784, "exclude_big")):
+        ex = torch.randint(1, V + 1, (G, n), device=DEV, generator=gen, dtype=torch.int32)
+        ex[:, n * 3 // 4:] = 0                                   # (padding, as in a bucketed batch)
+        res[name + "_us"] = _per_call_us(lambda: ops.topk_rows(x, k, col_offset=1, work=work, out=out, exclude=ex), reps)
+        want = ops.topk_rows(x.cpu(), k, col_offset=1, exclude=ex.cpu())
+        same &= bool(torch.equal(out[0].cpu(), want[0]) and torch.equal(out[1].cpu(), want[1]))
+    for d in (10, 50, 99):
+        mask = torch.rand(V, device=DEV, generator=gen) < d / 100
+        allow = ops.pack_allow(mask, V)
+        res[f"allow{d}_us"] = _per_call_us(lambda: ops.topk_rows(x, k, work=work, out=out, allow=allow), reps)
+        want = ops.topk_rows(x.cpu(), k, allow=allow.cpu())
+        same &= bool(torch.equal(out[0].cpu(), want[0]) and torch.equal(out[1].cpu(), want[1]))
+        if d == 50:
+            res["masked_fill_sort_us"] = _time(
+                lambda: torch.sort(x.masked_fill(~mask, float("-inf")), dim=1, descending=True, stable=True), reps)
+    res["same_as_torch_form"] = same
+    return res
+
+
+def bench_masked_loop(n_batches):
+    uni, model, coll = workloads.build("fsq", DEV, seed=1)
+    data = [t for trajs in workloads.make_pool("fsq", n_batches, 16, uni, seed0=4242) for t in trajs]
+    res = dict(part="masked_loop", workload="fsq", samples=len(data))
+    loops = {"predictloop": PredictLoop(model, coll, data, k=20, batch_size=16),
+             "predictloop_exclude_visited": PredictLoop(model, coll, data, k=20, batch_size=16, exclude_visited=True)}
+    for loop in loops.values():
+        loop.run()                                               # captures every bucket's graph
+    torch.cuda.synchronize()
+    best = dict.fromkeys(loops, 0.0)
+    for _ in range(5):                                           # (alternated: a loop timed right after its capture runs slow)
+        for name, loop in loops.items():
+            t0 = time.perf_counter()
+            loop.run()
+            torch.cuda.synchronize()
+            best[name] = max(best[name], len(data) / (time.perf_counter() - t0))
+    for name, v in best.items():
+        res[name + "_checkins_per_s"] = v
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=("kernel", "loop", "all"))
+    ap.add_argument("--part", default="all", choices=("kernel", "loop", "masked", "all"))
     ap.add_argument("--batches", type=int, default=32)
     ap.add_argument("--reps", type=int, default=50)
     a = ap.parse_args()
@@ -96,6 +147,12 @@ def main():
                     print(json.dumps(bench_kernel(G, V, k, a.reps)), flush=True)
     if a.part in ("loop", "all"):
         print(json.dumps(bench_loop(a.batches)), flush=True)
+    if a.part in ("masked", "all"):
+        # (the loop first: after the kernel shapes, in the same process, the exclude_visited loop read 27 % low -- DESIGN 12)
+        print(json.dumps(bench_masked_loop(a.batches)), flush=True)
+        for G in (1, 16):
+            for V in (3680, 7857, 20000, 100001):
+                print(json.dumps(bench_masked(G, V, 20, a.reps)), flush=True)
 
 
 if __name__ == "__main__":
