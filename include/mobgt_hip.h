@@ -348,6 +348,28 @@ int mobgt_rank_metrics(const float* scores, const int64_t* target, int64_t targe
                        void* work, void* stream);
 int mobgt_skinny_linear_rank_metrics(const float* x, const float* w, const float* b, const int64_t* target, int64_t target_offset,
                                      int G, int K, int V, double* acc, void* work, void* stream);
+/* mobgt_rank_metrics over each row's candidates: the ranking of the lists mobgt_topk_rows_masked returns (next new POIs, a
+ * candidate set).  Column c of row g is a candidate when
+ *   - allow is NULL, or bit c & 31 of allow[c >> 5] is set (ceil(V / 32) packed words, shared by every row), and
+ *   - MOBGT_RM_EXCLUDE_HIST is clear, or no entry p of hist[g, 0:n_hist_cols] has p != 0 && p - hist_offset == c.  hist is
+ *     [G, ld_hist] (ld_hist >= n_hist_cols) of dtype hist_dtype (MOBGT_I64 / MOBGT_I32); 0 is padding; ids mapping outside
+ *     [0, V) are ignored -- mobgt_topk_rows_masked's rule with excl = hist.
+ * A row is reachable when t = target[g] + target_offset is in [0, V) and column t is a candidate; its counts (greater, tie_lo,
+ * tie_hi) run over candidate columns only, so on finite scores a hit at k <=> the target is in mobgt_topk_rows_masked(...)[:k].
+ * An unreachable row adds to n only (no hit, no DCG, 0 to the reciprocal-rank sum).  acc holds slots of 11 f64
+ *   {n, hit@1, hit@5, hit@10, hit@20, dcg@1, dcg@5, dcg@10, dcg@20, sum 1 / (mrr_rank + 1), reachable}:
+ * one slot, or with MOBGT_RM_SPLIT three -- every row in slot 0, and in slot 1 when t is not among its hist ids (a new POI), else
+ * in slot 2 (a revisit); the split reads hist whether or not MOBGT_RM_EXCLUDE_HIST is set.  Hits and DCG stop, in every slot, at
+ * the first row of the batch whose t is 0; n, reachable and the reciprocal ranks count every row.  With allow NULL and flags 0,
+ * acc[0:10] is mobgt_rank_metrics' acc bit for bit (targets in [0, V)).  `work`: mobgt_rank_metrics_masked_work_bytes(G, V)
+ * bytes, any contents; two graph-capturable launches, no state survives a call.  Bad sizes / flags: MOBGT_EBADDIM; a bad
+ * hist_dtype: MOBGT_EDTYPE. */
+#define MOBGT_RM_EXCLUDE_HIST 1   /* a row's hist ids are not candidates (next new POIs) */
+#define MOBGT_RM_SPLIT 2          /* acc is [3][11]: all rows / target not in hist / target in hist */
+int64_t mobgt_rank_metrics_masked_work_bytes(int64_t G, int64_t V);
+int mobgt_rank_metrics_masked(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
+                              const uint32_t* allow, const void* hist, int hist_dtype, int64_t ld_hist, int64_t n_hist_cols,
+                              int64_t hist_offset, int flags, double* acc, void* work, void* stream);
 /* Row-wise top-k of stored scores: the ranked next-POI list (Graphormer.recommend_step, train.PredictLoop), replacing the
  * torch.topk a caller ran on test_step's y_pred (:1530-1544) by hand.  scores [G, V] f32 with row stride ld >= V (elements);
  * 1 <= k <= 64, k <= V, G <= 65535, else MOBGT_EBADDIM.  Writes ids [G, k] int64 = column + col_offset and vals [G, k] f32 equal to

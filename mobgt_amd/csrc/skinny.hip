@@ -9,6 +9,7 @@
 //   dW, db  : a workgroup owns 16 rows v: dW[v,k] = sum_g dy[g,v] x[g,k] with x in registers, coalesced stores.
 #include "common.h"
 #include "mobgt_hip.h"
+#include "cand_body.h"
 
 namespace {
 
@@ -748,6 +749,160 @@ __global__ __launch_bounds__(256) void rank_finish_kernel(const int32_t* __restr
     }
 }
 
+// ---- mobgt_rank_metrics_masked: the same counts over each row's candidates only (the candidate rule of mobgt_topk_rows_masked,
+// cand_body.h), so the ACC position greater + tie_lo is the target's place in the restricted top-k list.  acc holds 1 or 3
+// slots of RM_FIELDS: {n, hit@1, hit@5, hit@10, hit@20, dcg@1, dcg@5, dcg@10, dcg@20, sum 1 / rank, reachable}.
+constexpr int RM_FIELDS = 11;
+
+// grid (blocks, G): a workgroup counts one row over `per` columns (a multiple of 32), RM_CHUNK at a time with that sub-range's
+// candidate bits in LDS (per exceeds RM_CHUNK only past RM_MAXB * RM_CHUNK columns).  The scores of a sub-range are loaded before
+// its bits are built, so the two memory round trips overlap.  Whether the target itself is a candidate is the finish's business.
+constexpr int RMM_PER_T = RM_CHUNK / 256;
+
+__global__ __launch_bounds__(256) void rank_counts_masked_kernel(const float* __restrict__ scores, const int64_t* __restrict__ target,
+                                                                 int64_t target_offset, int32_t* __restrict__ slab, int G, int64_t V,
+                                                                 int64_t per, CandMask m) {
+    __shared__ int s_c[4][3];
+    __shared__ uint32_t s_ok[RM_CHUNK / 32];
+    const int g = blockIdx.y;
+    bool ok;
+    const int64_t t = rm_target(target, target_offset, g, V, ok);
+    const float* s = scores + (int64_t)g * V;
+    const int64_t c0 = (int64_t)blockIdx.x * per, c1 = c0 + per < V ? c0 + per : V;
+    int greater = 0, tie_lo = 0, tie_hi = 0;
+    if (ok) {                                         // (uniform over the workgroup)
+        const float ts = s[t];
+        for (int64_t b0 = c0; b0 < c1; b0 += RM_CHUNK) {
+            float v[RMM_PER_T];
+#pragma unroll
+            for (int i = 0; i < RMM_PER_T; ++i) {
+                const int64_t c = b0 + threadIdx.x + i * 256;
+                v[i] = c < c1 ? s[c] : 0.f;
+            }
+            cand_bits<RM_CHUNK / 32, 256>(s_ok, m, g, b0, V);
+#pragma unroll
+            for (int i = 0; i < RMM_PER_T; ++i) {
+                const int r = threadIdx.x + i * 256;
+                const int64_t c = b0 + r;
+                const bool cand = c < c1 && ((s_ok[r >> 5] >> (r & 31)) & 1u);
+                greater += cand & (v[i] > ts);
+                tie_lo += cand & (v[i] == ts) & (c < t);
+                tie_hi += cand & (v[i] == ts) & (c > t);
+            }
+            __syncthreads();                          // (s_ok read before the next sub-range rebuilds it)
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        greater += __shfl_xor(greater, o, 64);
+        tie_lo += __shfl_xor(tie_lo, o, 64);
+        tie_hi += __shfl_xor(tie_hi, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6][0] = greater; s_c[threadIdx.x >> 6][1] = tie_lo; s_c[threadIdx.x >> 6][2] = tie_hi; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int k = threadIdx.x;
+        slab[((int64_t)blockIdx.x * G + g) * 3 + k] = s_c[0][k] + s_c[1][k] + s_c[2][k] + s_c[3][k];
+    }
+}
+
+struct RmSlot {
+    double n = 0.0, hit[4] = {0.0, 0.0, 0.0, 0.0}, dcg[4] = {0.0, 0.0, 0.0, 0.0}, rr = 0.0, reach = 0.0;
+};
+
+// one row into a slot: every row counts in n; a reachable row adds its reciprocal rank, and its hits and DCG unless stopped
+__device__ __forceinline__ void rm_add(RmSlot& a, bool reach, bool stopped, int lo, int hi) {
+    const int ks[4] = {1, 5, 10, 20};
+    a.n += 1.0;
+    if (!reach) return;
+    a.reach += 1.0;
+    if (!stopped && lo < 20) {
+        const double gain = 1.0 / log2((double)lo + 2.0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (lo < ks[q]) { a.hit[q] += 1.0; a.dcg[q] += gain; }
+    }
+    a.rr += 1.0 / ((double)hi + 1.0);
+}
+
+__device__ __forceinline__ void rm_store(double* __restrict__ acc, const RmSlot& a) {
+    acc[0] += a.n;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { acc[1 + q] += a.hit[q]; acc[5 + q] += a.dcg[q]; }
+    acc[9] += a.rr;
+    acc[10] += a.reach;
+}
+
+// rank_finish_kernel's walk with the target's reachability (in [0, V), allowed, not excluded) and its membership in the row's
+// hist ids (MOBGT_RM_SPLIT's slot 1 / 2) decided here, 16 lanes per row over the hist list while the slab sums load.  The
+// order of the f64 sums is rank_finish_kernel's, so an unrestricted slot 0 is mobgt_rank_metrics' acc bit for bit.
+__global__ __launch_bounds__(256) void rank_finish_masked_kernel(const int32_t* __restrict__ slab, int nb, const int64_t* __restrict__ target,
+                                                                 int64_t target_offset, int G, int64_t V, CandMask m, int flags,
+                                                                 double* __restrict__ acc) {
+    __shared__ int s_c[RF_ROWS][3];
+    __shared__ int64_t s_t[RF_ROWS];
+    __shared__ int s_f[RF_ROWS];                      // bit 0: reachable, bit 1: the target is among the row's hist ids
+    RmSlot all, fresh, revisit;
+    bool stopped = false;
+    const bool split = flags & MOBGT_RM_SPLIT, excl = flags & MOBGT_RM_EXCLUDE_HIST;
+    const int r = threadIdx.x >> 4, l = threadIdx.x & 15;
+    for (int g0 = 0; g0 < G; g0 += RF_ROWS) {
+        const int g = g0 + r;
+        int c[3] = {0, 0, 0};
+        bool ok = false;
+        int64_t t = -1;
+        int in_hist = 0;
+        if (g < G) {
+            t = rm_target(target, target_offset, g, V, ok);
+            for (int bk = l; bk < nb; bk += 16) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) c[k] += slab[((int64_t)bk * G + g) * 3 + k];
+            }
+            if (m.excl) {
+                for (int64_t j = l; j < m.n_excl; j += 16) {
+                    const int64_t p = cand_excl_id(m, g, j);
+                    in_hist |= p != 0 && (uint64_t)p - (uint64_t)m.excl_offset == (uint64_t)t;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int o = 8; o >= 1; o >>= 1) c[k] += __shfl_xor(c[k], o, 64);
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) in_hist |= __shfl_xor(in_hist, o, 64);
+        __syncthreads();                              // (s_c of the previous rows has been read)
+        if (l == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_c[r][k] = c[k];
+            in_hist &= ok;                            // (ids outside [0, V) are ignored)
+            const bool allowed = ok && (!m.allow || ((m.allow[t >> 5] >> (t & 31)) & 1u));
+            s_t[r] = t;
+            s_f[r] = (allowed && !(excl && in_hist) ? 1 : 0) | (in_hist ? 2 : 0);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int i = 0; i < RF_ROWS && g0 + i < G; ++i) {
+                const bool reach = s_f[i] & 1;
+                const int lo = s_c[i][0] + s_c[i][1], hi = s_c[i][0] + s_c[i][2];
+                if (s_t[i] == 0) stopped = true;
+                rm_add(all, reach, stopped, lo, hi);
+                if (split) {
+                    if (s_f[i] & 2) rm_add(revisit, reach, stopped, lo, hi);
+                    else rm_add(fresh, reach, stopped, lo, hi);
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        rm_store(acc, all);
+        if (split) {
+            rm_store(acc + RM_FIELDS, fresh);
+            rm_store(acc + 2 * RM_FIELDS, revisit);
+        }
+    }
+}
+
 template <int KT>
 int launch_rank_fused(const float* x, const float* w, const float* b, const int64_t* target, int64_t target_offset, double* acc,
                       char* work, int G, int V, hipStream_t st) {
@@ -777,6 +932,35 @@ extern "C" int mobgt_rank_metrics(const float* scores, const int64_t* target, in
     const int nb = rm_blocks(V);
     hipLaunchKernelGGL(rank_counts_kernel, dim3(nb, (unsigned)G), dim3(256), 0, st, scores, target, target_offset, slab, (int)G, V);
     hipLaunchKernelGGL(rank_finish_kernel, dim3(1), dim3(256), 0, st, slab, nb, target, target_offset, (int)G, V, acc);
+    return (int)hipGetLastError();
+}
+
+extern "C" int64_t mobgt_rank_metrics_masked_work_bytes(int64_t G, int64_t V) {
+    if (G <= 0 || V <= 0) return 0;
+    return 12 * (int64_t)rm_blocks(V) * G;
+}
+
+extern "C" int mobgt_rank_metrics_masked(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
+                                         const uint32_t* allow, const void* hist, int hist_dtype, int64_t ld_hist, int64_t n_hist_cols,
+                                         int64_t hist_offset, int flags, double* acc, void* work, void* stream) {
+    if (G <= 0 || V <= 0 || G > 65535 || V > (int64_t)INT32_MAX) return MOBGT_EBADDIM;
+    if (!scores || !target || !acc || !work) return MOBGT_EBADDIM;
+    if (flags & ~(MOBGT_RM_EXCLUDE_HIST | MOBGT_RM_SPLIT)) return MOBGT_EBADDIM;
+    if (hist && (n_hist_cols < 0 || ld_hist < n_hist_cols)) return MOBGT_EBADDIM;
+    if (hist && hist_dtype != MOBGT_I64 && hist_dtype != MOBGT_I32) return MOBGT_EDTYPE;
+    const bool use_hist = hist && n_hist_cols > 0;
+    const bool i64 = hist_dtype == MOBGT_I64;
+    // the counts drop the hist ids only to exclude them; the finish reads them to exclude or to split
+    const CandMask mc{allow, use_hist && (flags & MOBGT_RM_EXCLUDE_HIST) ? hist : nullptr, ld_hist, n_hist_cols, hist_offset, i64};
+    const CandMask mf{allow, use_hist && flags ? hist : nullptr, ld_hist, n_hist_cols, hist_offset, i64};
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* slab = reinterpret_cast<int32_t*>(work);
+    const int nb = rm_blocks(V);
+    const int64_t per = ((V + nb - 1) / nb + 31) / 32 * 32;     // (sub-ranges start on an allow word)
+    hipLaunchKernelGGL(rank_counts_masked_kernel, dim3(nb, (unsigned)G), dim3(256), 0, st, scores, target, target_offset, slab, (int)G,
+                       V, per, mc);
+    hipLaunchKernelGGL(rank_finish_masked_kernel, dim3(1), dim3(256), 0, st, (const int32_t*)slab, nb, target, target_offset, (int)G, V,
+                       mf, flags, acc);
     return (int)hipGetLastError();
 }
 

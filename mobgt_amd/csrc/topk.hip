@@ -22,6 +22,7 @@
 // writes a final key 0 -- a row with fewer than k candidates -- as id -1, val -inf.  No extra launch, no [G, V / 32] buffer.
 #include "common.h"
 #include "../../include/mobgt_hip.h"
+#include "cand_body.h"
 
 namespace {
 
@@ -91,19 +92,11 @@ __device__ __forceinline__ uint64_t block_fold(uint64_t top, uint64_t* s_keys, i
     return top;
 }
 
-// The candidate restriction of mobgt_topk_rows_masked: allow bits (NULL: all) and a per-row list of excluded ids (NULL: none).
-struct TkMask {
-    const uint32_t* allow;                         // ceil(V / 32) words, bit c & 31 of word c >> 5 = column c may be listed
-    const void* excl;                              // [G, ld_excl] int32 / int64 ids; 0 = padding; id - excl_offset = column
-    int64_t ld_excl, n_excl, excl_offset;
-    int excl_i64;
-};
-
 // launch 1: grid (chunks, G); the chunk's k best keys, descending, -> work[g][chunk][0, k) (0 = no column).  MASK: columns that
 // are not candidates take the key 0 (below every real key), so they are never selected.
 template <bool MASK>
 __global__ __launch_bounds__(64 * TK_WAVES1) void topk_chunk_kernel(const float* __restrict__ scores, int64_t ld, int64_t V, int k,
-                                                                    uint64_t* __restrict__ work, TkMask m) {
+                                                                    uint64_t* __restrict__ work, CandMask m) {
     __shared__ uint64_t s_keys[TK_WAVES1 * 64];
     __shared__ uint32_t s_ok[TK_CHUNK / 32];       // MASK: the chunk's candidate bits
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -117,23 +110,7 @@ __global__ __launch_bounds__(64 * TK_WAVES1) void topk_chunk_kernel(const float*
         key[i] = c < V ? tk_key(row[c], (uint32_t)c) : 0;
     }
     if constexpr (MASK) {
-        // the chunk's allow words, then the row's excluded ids that fall inside the chunk cleared (ids outside [0, V) land
-        // outside every chunk, or on columns >= V whose key is 0 already)
-        const int64_t base = (int64_t)blockIdx.x * TK_CHUNK;
-        if (threadIdx.x < TK_CHUNK / 32) {
-            const int64_t wi = base / 32 + threadIdx.x;
-            s_ok[threadIdx.x] = !m.allow ? ~0u : wi < (V + 31) / 32 ? m.allow[wi] : 0u;
-        }
-        __syncthreads();
-        if (m.excl) {
-            for (int64_t j = threadIdx.x; j < m.n_excl; j += 64 * TK_WAVES1) {
-                const int64_t p = m.excl_i64 ? reinterpret_cast<const int64_t*>(m.excl)[g * m.ld_excl + j]
-                                             : (int64_t)reinterpret_cast<const int32_t*>(m.excl)[g * m.ld_excl + j];
-                const uint64_t r = (uint64_t)p - (uint64_t)m.excl_offset - (uint64_t)base;     // (unsigned: no overflow)
-                if (p != 0 && r < (uint64_t)TK_CHUNK) atomicAnd(&s_ok[r >> 5], ~(1u << (r & 31)));
-            }
-            __syncthreads();
-        }
+        cand_bits<TK_CHUNK / 32, 64 * TK_WAVES1>(s_ok, m, g, (int64_t)blockIdx.x * TK_CHUNK, V);   // (cand_body.h)
 #pragma unroll
         for (int i = 0; i < TK_ITERS; ++i) {
             const int r = w * 64 + lane + i * 64 * TK_WAVES1;
@@ -191,7 +168,7 @@ extern "C" int64_t mobgt_topk_work_bytes(int64_t G, int64_t V, int64_t k) {
 namespace {
 
 int topk_launch(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, int64_t* ids, float* vals,
-                void* work, const TkMask& m, bool masked, void* stream) {
+                void* work, const CandMask& m, bool masked, void* stream) {
     if (G <= 0 || G > 65535 || V <= 0 || V >= (int64_t)INT32_MAX || k < 1 || k > TK_MAXK || k > V || ld < V) return MOBGT_EBADDIM;
     if (!scores || !ids || !vals || !work) return MOBGT_EBADDIM;
     hipStream_t st = (hipStream_t)stream;
@@ -215,7 +192,7 @@ int topk_launch(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k
 
 extern "C" int mobgt_topk_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, int64_t* ids,
                                float* vals, void* work, void* stream) {
-    return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, TkMask{}, false, stream);
+    return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, CandMask{}, false, stream);
 }
 
 extern "C" int mobgt_topk_rows_masked(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset,
@@ -224,6 +201,6 @@ extern "C" int mobgt_topk_rows_masked(const float* scores, int64_t ld, int64_t G
     if (excl && (n_excl_cols < 0 || ld_excl < n_excl_cols)) return MOBGT_EBADDIM;
     if (excl && excl_dtype != MOBGT_I64 && excl_dtype != MOBGT_I32) return MOBGT_EDTYPE;
     const bool use_excl = excl && n_excl_cols > 0;
-    const TkMask m{allow, use_excl ? excl : nullptr, ld_excl, n_excl_cols, excl_offset, excl_dtype == MOBGT_I64};
+    const CandMask m{allow, use_excl ? excl : nullptr, ld_excl, n_excl_cols, excl_offset, excl_dtype == MOBGT_I64};
     return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, m, allow || use_excl, stream);
 }

@@ -90,3 +90,79 @@ def finalize(acc):
                                               ("acc@20", 4), ("ndcg@20", 8), ("mrr", 9))}
     out["n"] = int(n)
     return out
+
+
+# ---- restricted and split evaluation (ops.rank_metrics_masked, train.EvalLoop(exclude_visited=, candidates=, split_revisits=)) ---
+# Slots of 11 f64: ACC_FIELDS, then the rows whose target can be listed at all.  One slot, or three with the split: every row /
+# rows whose target is not among the trajectory's POIs (new) / rows whose target is (revisit).
+RACC_FIELDS = ACC_FIELDS + ("reachable",)
+SPLIT_SLOTS = ("all", "new", "revisit")
+
+
+def new_restricted_accumulator(device, split=False):
+    return torch.zeros(3 if split else 1, len(RACC_FIELDS), dtype=torch.float64, device=device)
+
+
+def _finalize_slot(a):
+    out = finalize(a[:len(ACC_FIELDS)])
+    out["reachable"] = int(a[len(ACC_FIELDS)])
+    return out
+
+
+def finalize_restricted(acc):
+    """finalize's dict of slot 0 plus "reachable"; with the split also "new" and "revisit", dicts of the same keys over their
+    rows.  Averages are over each slot's n (every row, reachable or not: the reference's denominator)."""
+    a = np.asarray(torch.as_tensor(acc).detach().double().cpu().numpy(), dtype=np.float64).reshape(-1, len(RACC_FIELDS))
+    assert a.shape[0] in (1, 3), "acc: new_restricted_accumulator's [1, 11] or [3, 11]"
+    out = _finalize_slot(a[0])
+    if a.shape[0] == 3:
+        out["new"], out["revisit"] = _finalize_slot(a[1]), _finalize_slot(a[2])
+    return out
+
+
+def restricted_sums(scores, target, target_offset=0, allow=None, hist=None, hist_offset=0, exclude_hist=False, split=False):
+    """The contract of mobgt_rank_metrics_masked in torch, on the scores' device: one batch's f64 [1 or 3, 11] slot sums.
+
+    Per row g, t = target[g] + target_offset.  Column c is a candidate when its bit of `allow` (ops.pack_allow words; None: every
+    column) is set and, with exclude_hist, no entry p != 0 of hist[g] has p - hist_offset == c (0 is padding, ids outside [0, V)
+    are ignored).  The row is reachable when t is in [0, V) and a candidate; its ACC / NDCG position is the number of candidates
+    scoring above s[t] plus the equal-scored candidates at lower columns, its MRR position the same with higher columns.  An
+    unreachable row adds to n only.  Hits and DCG stop at the batch's first row with t == 0 (get_acc).  split: slot 1 takes the
+    rows whose t is not among their hist ids, slot 2 the others (hist read whether or not exclude_hist is set)."""
+    from . import ops
+    G, V = scores.shape
+    dev = scores.device
+    t = target.reshape(-1)[:G].to(device=dev, dtype=torch.int64) + int(target_offset)
+    ok = (t >= 0) & (t < V)
+    tc = t.clamp(0, V - 1)
+    rows = torch.arange(G, device=dev)
+    use_hist = hist is not None and hist.numel() > 0
+    cand = ops._candidates(G, V, allow, hist if exclude_hist and use_hist else None, hist_offset, dev)
+    reach = ok & cand[rows, tc]
+    if use_hist:
+        h = hist.to(device=dev, dtype=torch.int64)
+        in_hist = ok & ((h != 0) & (h - int(hist_offset) == t[:, None])).any(1)
+    else:
+        in_hist = torch.zeros(G, dtype=torch.bool, device=dev)
+    s = scores
+    ts = s[rows, tc][:, None]
+    cols = torch.arange(V, device=dev)[None, :]
+    greater = ((s > ts) & cand).sum(1)
+    lo = greater + ((s == ts) & cand & (cols < tc[:, None])).sum(1)
+    hi = greater + ((s == ts) & cand & (cols > tc[:, None])).sum(1)
+    zero = (t == 0).nonzero()
+    live = rows < (int(zero[0]) if zero.numel() else G)
+    gain = 1.0 / torch.log2(lo.double() + 2.0)
+    rr = 1.0 / (hi.double() + 1.0)
+    out = torch.zeros(3 if split else 1, len(RACC_FIELDS), dtype=torch.float64, device=dev)
+    sels = (torch.ones(G, dtype=torch.bool, device=dev), ~in_hist, in_hist)[:3 if split else 1]
+    for i, sel in enumerate(sels):
+        r = sel & reach
+        out[i, 0] = sel.sum()
+        for q, k in enumerate((1, 5, 10, 20)):
+            h = r & live & (lo < k)
+            out[i, 1 + q] = h.sum()
+            out[i, 5 + q] = gain[h].sum()
+        out[i, 9] = rr[r].sum()
+        out[i, 10] = r.sum()
+    return out

@@ -664,7 +664,7 @@ class Graphormer(nn.Module):
             return ops.cross_entropy(logits, y, ignore_index=0)           # value + gradient in one launch (csrc/layer.hip)
         return F.cross_entropy(logits.float(), y.long(), ignore_index=0)
 
-    def metric_step(self, batched_data, acc, work=None):
+    def metric_step(self, batched_data, acc, work=None, exclude_visited=False, allow=None, split_revisits=False):
         """The fq model's device evaluation (model_fqandtoyo.Graphormer.metric_step) has no counterpart in this variant: the
         reference's model.py evaluates through Lightning's generic metric hooks, not test_epoch_end's ACC / NDCG / MRR."""
         raise NotImplementedError("metric_step / train.EvalLoop: the fq model (model_fqandtoyo.Graphormer) only")

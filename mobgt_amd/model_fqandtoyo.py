@@ -538,12 +538,21 @@ class Graphormer(nn.Module):
         if m_head is not None:
             # metric_step: the classifier ends in the ranking metrics of test_epoch_end (:1546-1597) added to a device
             # accumulator; cat_decoder's output (read by nobody there) is not produced
-            y_m, acc, work = m_head
+            y_m, acc, work, restrict = m_head
             W, b = self.out_proj.weight, self.out_proj.bias
             # (the logits are stored and ranked by mobgt_rank_metrics: measured faster than the fused classifier-ranking form,
             #  ops.skinny_linear_rank_metrics, at every width from 3 680 to 100 001 classes -- 15.1 against 23.4 us at S-FSQ's
             #  7 857, 49 against 75 us at S-BIG's 100 001 (tools/eval_bench.py); both give the same bits)
             logits = ops.skinny_linear(tok, W, b) if ops.skinny_linear_ok(tok, W) else self.out_proj(tok)
+            if restrict is not None:
+                # restricted / split: recommend_step's scores, candidates and label space (x holds the trajectory's POI ids as
+                # y does, 0 = padding; column = y - 1 = x - 1, or y = x for toyotagraph)
+                exclude_visited, allow, split = restrict
+                scores = torch.log_softmax(logits.float(), dim=1) if toyota else logits
+                hist = batched_data.x.reshape(batched_data.x.shape[0], -1)
+                ops.rank_metrics_masked(scores, y_m, acc, target_offset=0 if toyota else -1, allow=allow, hist=hist,
+                                        hist_offset=0 if toyota else 1, exclude_hist=exclude_visited, split=split, work=work)
+                return [None, None]
             if toyota:
                 # :1484-1495: toyotagraph is not in the y - 1 list -- unshifted y, and the POI head's log-probabilities (:1417-1428)
                 ops.rank_metrics(torch.log_softmax(logits.float(), dim=1), y_m, acc, target_offset=0, work=work)
@@ -620,15 +629,23 @@ class Graphormer(nn.Module):
         """model_fqandtoyo.py:1530-1544"""
         return {"y_pred": self(batched_data), "y_true": batched_data.y.long() - 1, "idx": batched_data.idx}
 
-    def metric_step(self, batched_data, acc, work=None):
+    def metric_step(self, batched_data, acc, work=None, exclude_visited=False, allow=None, split_revisits=False):
         """validation_step / test_step + test_epoch_end's per-batch bookkeeping in one pass: the batch's ACC / NDCG @1/5/10/20
         and MRR sums (metrics.evaluate_outputs, quirks included) are ADDED to `acc` (metrics.new_accumulator) on the device --
         no category head, no host read.  Eval mode, under no_grad.  toyotagraph ranks log_softmax(logits) against
-        the UNSHIFTED y, as the reference's validation / test step does (:1484-1495).  `work`: ops.rank_metrics' buffer."""
+        the UNSHIFTED y, as the reference's validation / test step does (:1484-1495).  `work`: ops.rank_metrics' buffer.
+
+        Restricted and split (ops.rank_metrics_masked; acc = metrics.new_restricted_accumulator(device, split_revisits), work of
+        ops.rank_metrics_masked_work_bytes): the ranking of the lists recommend_step returns with the same exclude_visited /
+        allow, so a hit at k <=> y is in that list's first k; a row whose y cannot be listed counts in n only.  split_revisits
+        adds the rows whose y is not among the trajectory's POIs (batched_data.x) to slot 1, the others to slot 2."""
         if self.training:
             raise RuntimeError("metric_step: the model is in training mode (call .eval() first)")
+        restrict = None
+        if exclude_visited or allow is not None or split_revisits:
+            restrict = (bool(exclude_visited), allow, bool(split_revisits))
         with torch.no_grad():
-            self._metrics_in_head = (batched_data.y, acc, work)
+            self._metrics_in_head = (batched_data.y, acc, work, restrict)
             try:
                 self(batched_data)
             finally:
@@ -663,11 +680,13 @@ class Graphormer(nn.Module):
         return PredictLoop(self, collator, dataset, k=k, exclude_visited=exclude_visited, candidates=candidates,
                            **kw).run(max_batches=max_batches)
 
-    def evaluate(self, dataset, collator, **kw):
-        """train.EvalLoop(self, collator, dataset, **kw).run(): the reference's validation / test protocol over a whole split."""
+    def evaluate(self, dataset, collator, exclude_visited=False, candidates=None, split_revisits=False, **kw):
+        """train.EvalLoop(self, collator, dataset, exclude_visited=..., candidates=..., split_revisits=..., **kw).run(): the
+        reference's validation / test protocol over a whole split, optionally over restricted lists and split by revisits."""
         from .train import EvalLoop
         max_batches = kw.pop("max_batches", None)
-        return EvalLoop(self, collator, dataset, **kw).run(max_batches=max_batches)
+        return EvalLoop(self, collator, dataset, exclude_visited=exclude_visited, candidates=candidates,
+                        split_revisits=split_revisits, **kw).run(max_batches=max_batches)
 
     def test_epoch_end(self, outputs):
         """model_fqandtoyo.py:1546-1597: ACC / NDCG @1/5/10/20 and MRR over all test samples."""

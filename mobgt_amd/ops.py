@@ -929,8 +929,12 @@ def rank_metrics_work_bytes(G, V):
     return int(_lib.lib().mobgt_rank_metrics_work_bytes(G, V))
 
 
-def _rank_work(device, G, V, work=None):
-    n = rank_metrics_work_bytes(G, V)
+def rank_metrics_masked_work_bytes(G, V):
+    return int(_lib.lib().mobgt_rank_metrics_masked_work_bytes(G, V))
+
+
+def _rank_work(device, G, V, work=None, nbytes=None):
+    n = rank_metrics_work_bytes(G, V) if nbytes is None else nbytes
     if work is not None:
         assert work.is_cuda and work.numel() * work.element_size() >= n, f"rank metrics: work buffer of {n} bytes needed"
         return work
@@ -963,6 +967,57 @@ def rank_metrics(scores, target, acc, target_offset=0, work=None):
     work = _rank_work(scores.device, G, V, work)
     check(_lib.lib().mobgt_rank_metrics(_p(scores), _p(target), int(target_offset), G, V, _p(acc), _p(work), _stream()),
           "mobgt_rank_metrics")
+    return acc
+
+
+RM_EXCLUDE_HIST, RM_SPLIT = 1, 2          # include/mobgt_hip.h: MOBGT_RM_*
+
+
+def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=None, hist_offset=None, exclude_hist=False,
+                        split=False, work=None):
+    """rank_metrics over each row's candidates, optionally split by whether the target is a revisit: adds one batch's sums to
+    `acc`, metrics.new_restricted_accumulator(device, split) -- [1, 11] f64, or [3, 11] with split (all rows / target not among
+    the row's hist ids / target among them).  The contract is metrics.restricted_sums: candidates are the columns whose `allow`
+    bit is set (pack_allow words; None: every column) and, with exclude_hist, that no id p != 0 of hist[g] names (column
+    p - hist_offset; hist_offset defaults to -target_offset, the target's label space); a row whose target is not a candidate
+    counts in n only.  The ranking is that of topk_rows(scores, allow=, exclude=hist): a hit at k <=> y is in its first k.
+    CUDA f32 scores: mobgt_rank_metrics_masked, two launches, no host read.  Other inputs: restricted_sums itself.
+    `work`: a device buffer of rank_metrics_masked_work_bytes(G, V) bytes (default: one per stream)."""
+    G, V = scores.shape
+    hist_offset = -int(target_offset) if hist_offset is None else int(hist_offset)
+    if (exclude_hist or split) and hist is None:
+        raise ValueError("rank_metrics_masked: exclude_hist / split need the rows' hist ids")
+    S = 3 if split else 1
+    assert acc.dtype == torch.float64 and acc.shape == (S, 11) and acc.is_contiguous(), \
+        f"rank_metrics_masked: acc = metrics.new_restricted_accumulator(device, split={bool(split)}), f64 [{S}, 11]"
+    if allow is not None:
+        assert allow.dtype == torch.int32 and allow.dim() == 1 and allow.numel() >= (V + 31) // 32, \
+            f"rank_metrics_masked: allow = pack_allow(..., {V}) words, int32 [{(V + 31) // 32}]"
+    if hist is not None:
+        assert hist.dim() == 2 and hist.shape[0] == G and hist.dtype in (torch.int32, torch.int64), \
+            f"rank_metrics_masked: hist = [{G}, n] int32 / int64 ids"
+    target = target.reshape(-1)
+    assert target.numel() >= G
+    if not (scores.is_cuda and scores.dtype == torch.float32):
+        from .metrics import restricted_sums
+        acc += restricted_sums(scores, target, target_offset, allow, hist, hist_offset, exclude_hist, split).to(acc.device)
+        return acc
+    _require_cuda(scores, target, acc)
+    scores = scores.contiguous()
+    target = target.long().contiguous()
+    if allow is not None:
+        assert allow.is_cuda and allow.is_contiguous(), "rank_metrics_masked: allow words on the device, contiguous"
+    n_h, ld_h = 0, 0
+    if hist is not None:
+        assert hist.is_cuda, "rank_metrics_masked: hist on the device"
+        if hist.shape[1] and (hist.stride(1) != 1 or hist.stride(0) < hist.shape[1]):
+            hist = hist.contiguous()
+        n_h, ld_h = hist.shape[1], max(hist.stride(0), hist.shape[1])
+    work = _rank_work(scores.device, G, V, work, rank_metrics_masked_work_bytes(G, V))
+    flags = (RM_EXCLUDE_HIST if exclude_hist else 0) | (RM_SPLIT if split else 0)
+    check(_lib.lib().mobgt_rank_metrics_masked(_p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), _p(hist),
+                                               _IT[hist.dtype] if hist is not None else I64, ld_h, n_h, hist_offset, flags,
+                                               _p(acc), _p(work), _stream()), "mobgt_rank_metrics_masked")
     return acc
 
 

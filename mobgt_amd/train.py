@@ -1187,6 +1187,15 @@ class EpochLoop(_StagedBatches):
         return dict(steps=steps, graphs=len(self.slots), sample_ids=seen)
 
 
+def _pack_candidates(model, candidates, V, device):
+    """EvalLoop's / PredictLoop's candidate set: POI ids in y's label space -> ops.pack_allow words on the device, packed once
+    so that a loop's graphs read them at one fixed address (None: no candidate set)."""
+    if candidates is None:
+        return None
+    offset = 0 if getattr(model, "dataset_name", None) == "toyotagraph" else 1          # (recommend_step's label space)
+    return ops.pack_allow(torch.as_tensor(candidates).to(device), V, offset)
+
+
 class EvalLoop(_StagedBatches):
     """The validation / test loop (Lightning's `trainer.validate` / `trainer.test` over the reference's eval DataLoader,
     entry.py:120-161, with test_epoch_end's bookkeeping, model_fqandtoyo.py:1484-1597) on the device data path of EpochLoop.
@@ -1199,20 +1208,35 @@ class EvalLoop(_StagedBatches):
     * per (G, bucket, ops.SAFE_FORMS[0]) ONE captured graph = eval forward + the fused classifier-ranking launches
       (Graphormer.metric_step) adding into ONE f64 accumulator; `use_graph=False` runs the same launches eagerly, and so do
       collators whose finish needs torch ops (coordinate bins, S-BIG: see _launch);
-    * `run()` reads the accumulator once (after one all-reduce of its 10 doubles when world > 1: every rank's samples pooled).
+    * `run()` reads the accumulator once (after one all-reduce of all its doubles when world > 1: every rank's samples pooled).
     The weights are read as they are when `run()` starts (bf16 shadows and MFMA packs re-derived there, outside any graph), so an
-    evaluation between training epochs sees the current model; it leaves no state behind that the trainer's next step reads."""
+    evaluation between training epochs sees the current model; it leaves no state behind that the trainer's next step reads.
+
+    Restricted and split evaluation (Graphormer.metric_step's restricted form, ops.rank_metrics_masked) measures the lists
+    PredictLoop returns with the same restriction, kept for the loop's lifetime: exclude_visited ranks each target among the
+    POIs its trajectory has not visited, candidates (POI ids in y's label space, packed once here) among those only.
+    split_revisits also reports the rows whose target is a new POI and those whose target is a revisit.  run() then returns
+    metrics.finalize_restricted's dict: today's keys, "n", "reachable" (targets that can be listed at all) and, with the split,
+    "new" / "revisit" dicts of the same keys.  The defaults run today's launches and return today's dict."""
 
     def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
-                 side_collate=True):
+                 side_collate=True, exclude_visited=False, candidates=None, split_revisits=False):
         from . import metrics
         if not hasattr(model, "metric_step"):
             raise TypeError("EvalLoop: the model has no metric_step (the fq model, model_fqandtoyo.Graphormer)")
         self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
         self.captures = 0                                   # graphs captured so far (a replayed run captures none)
+        V = model.out_proj.out_features
+        self.exclude_visited, self.split_revisits = bool(exclude_visited), bool(split_revisits)
+        self.allow = _pack_candidates(model, candidates, V, self.device)
+        self.restricted = self.exclude_visited or self.allow is not None or self.split_revisits
+        if self.restricted:
+            self.acc = metrics.new_restricted_accumulator(self.device, self.split_revisits)
+            self._scratch = metrics.new_restricted_accumulator(self.device, self.split_revisits)     # warm-ups count nowhere
+            self.work = torch.empty(ops.rank_metrics_masked_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
+            return
         self.acc = metrics.new_accumulator(self.device)
         self._scratch = metrics.new_accumulator(self.device)                          # warm-up passes count nowhere
-        V = model.out_proj.out_features
         self.work = torch.empty(ops.rank_metrics_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
 
     def _setup(self, model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate):
@@ -1239,6 +1263,10 @@ class EvalLoop(_StagedBatches):
 
     def _forward(self, batch, acc):
         b = self.collator.finish(batch) if isinstance(batch, dict) else batch      # (raw views: the in-graph collate)
+        if self.restricted:
+            self.model.metric_step(b, acc, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow,
+                                   split_revisits=self.split_revisits)
+            return
         self.model.metric_step(b, acc, work=self.work)
 
     def _weights_ptrs(self):
@@ -1351,7 +1379,7 @@ class EvalLoop(_StagedBatches):
                     self.acc.copy_(host)
                 else:
                     dist.all_reduce(self.acc)
-            out = metrics.finalize(self.acc)              # the one host read
+            out = metrics.finalize_restricted(self.acc) if self.restricted else metrics.finalize(self.acc)    # the one host read
         return out
 
 
@@ -1378,10 +1406,7 @@ class PredictLoop(EvalLoop):
             raise ValueError(f"PredictLoop: k = {k} outside [1, {min(ops.TOPK_MAX, V)}]")
         self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
         self.exclude_visited = bool(exclude_visited)
-        self.allow = None
-        if candidates is not None:
-            offset = 0 if getattr(model, "dataset_name", None) == "toyotagraph" else 1      # (recommend_step's label space)
-            self.allow = ops.pack_allow(torch.as_tensor(candidates).to(self.device), V, offset)
+        self.allow = _pack_candidates(model, candidates, V, self.device)
         self.captures = 0
         self.acc = self._scratch = None                     # (EvalLoop._launch passes them to _forward, which ignores them)
         self.outs = {}                                      # (G, N) -> the [G, k] buffers its graphs write

@@ -8,8 +8,12 @@
           metric_step runs) and the classifier + 2 x mobgt_target_rank (the eager path's device work); CUDA-event time per call
           over a replayed graph of `--reps` calls.  Run the `kernel` part alone under `rocprofv3 --kernel-trace --stats` for the
           per-kernel split.
+  masked  restricted and split evaluation (mobgt_rank_metrics_masked) next to mobgt_rank_metrics on the same stored scores,
+          G = 1 / 16, V = 3 680 .. 100 001: no restriction, exclude_visited (64 visited ids per row), and exclude_visited +
+          split_revisits + a candidate set of half the columns; per-call time over a replayed graph.  Then EvalLoop's
+          check-ins / s at S-FSQ, plain and with exclude_visited + split_revisits, timed alternately (best of --loop-reps runs).
 
-  python tools/eval_bench.py [--part loop|kernel|all] [--batches N] [--reps N]
+  python tools/eval_bench.py [--part loop|kernel|masked|all] [--batches N] [--reps N] [--loop-reps N]
 """
 import argparse
 import json
@@ -107,12 +111,61 @@ def bench_kernel(V, K, reps, G=16):
                 fwd_plus_rank_metrics_us=_per_call_us(stored, reps), fwd_plus_2_target_rank_us=_per_call_us(unfused, reps))
 
 
+def bench_masked(V, G, reps):
+    gen = torch.Generator(device=DEV).manual_seed(V + G)
+    s = torch.randn(G, V, device=DEV, generator=gen)
+    t = torch.randint(1, V + 1, (G,), device=DEV, generator=gen)             # label space: column = y - 1
+    hist = torch.randint(0, V + 1, (G, 64), device=DEV, generator=gen)
+    allow = ops.pack_allow(torch.rand(V, device=DEV, generator=gen) < 0.5, V)
+    acc = metrics.new_accumulator(DEV)
+    one, three = metrics.new_restricted_accumulator(DEV), metrics.new_restricted_accumulator(DEV, True)
+    work = torch.empty(max(ops.rank_metrics_work_bytes(G, V), ops.rank_metrics_masked_work_bytes(G, V)), dtype=torch.uint8,
+                       device=DEV)
+    return dict(part="masked", V=V, G=G,
+                rank_metrics_us=_per_call_us(lambda: ops.rank_metrics(s, t, acc, -1, work=work), reps),
+                masked_plain_us=_per_call_us(lambda: ops.rank_metrics_masked(s, t, one, -1, work=work), reps),
+                masked_exclude_us=_per_call_us(lambda: ops.rank_metrics_masked(s, t, one, -1, hist=hist, exclude_hist=True,
+                                                                               work=work), reps),
+                masked_exclude_split_allow_us=_per_call_us(lambda: ops.rank_metrics_masked(s, t, three, -1, allow, hist,
+                                                                                           exclude_hist=True, split=True,
+                                                                                           work=work), reps))
+
+
+def bench_loop_masked(name, n_batches, loop_reps):
+    uni, model, coll = workloads.build(name, DEV, seed=1)
+    data = [t for trajs in workloads.make_pool(name, n_batches, 16, uni, seed0=4242) for t in trajs]
+    loops = {"plain": EvalLoop(model, coll, data, batch_size=16),
+             "exclude_visited_split": EvalLoop(model, coll, data, batch_size=16, exclude_visited=True, split_revisits=True)}
+    best, res = {}, {}
+    for lp in loops.values():
+        lp.run()                                                 # captures
+    for _ in range(loop_reps):
+        for k, lp in loops.items():                              # (alternately: drift hits both alike)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res[k] = lp.run()
+            best[k] = min(best.get(k, float("inf")), time.perf_counter() - t0)
+    n = len(data)
+    r = res["exclude_visited_split"]
+    return dict(part="masked_loop", workload=name, samples=n, plain_checkins_per_s=n / best["plain"],
+                restricted_checkins_per_s=n / best["exclude_visited_split"], ratio=best["plain"] / best["exclude_visited_split"],
+                acc20_plain=res["plain"]["acc@20"], acc20_new_poi=r["acc@20"], reachable=r["reachable"],
+                revisit_share=r["revisit"]["n"] / max(r["n"], 1))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=("loop", "kernel", "all"))
+    ap.add_argument("--part", default="all", choices=("loop", "kernel", "masked", "all"))
     ap.add_argument("--batches", type=int, default=32)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--loop-reps", type=int, default=3)
     a = ap.parse_args()
+    if a.part == "masked":
+        for G in (1, 16):
+            for V in (3680, 7857, 20000, 100001):
+                print(json.dumps(bench_masked(V, G, a.reps)), flush=True)
+        print(json.dumps(bench_loop_masked("fsq", a.batches, a.loop_reps)), flush=True)
+        return
     if a.part in ("kernel", "all"):
         for V, K in ((3680, 320), (7857, 320), (20000, 320), (40000, 448), (100001, 448)):
             print(json.dumps(bench_kernel(V, K, a.reps)), flush=True)
