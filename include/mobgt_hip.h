@@ -624,6 +624,34 @@ int mobgt_adamw_flat(float* params, const float* grads, float* exp_avg, float* e
                      const float* lr_dev, const float* sched, const int64_t* step_dev, int64_t step_base, float beta1,
                      float beta2, float eps, float weight_decay, void* stream);
 
+/* Gradient accumulation and global-norm clipping of the train step (TrainStep(accumulate=k, clip_norm=c)); all three are
+ * single launches without atomics, tickets or waits between workgroups, so they can be captured and identical input gives
+ * identical bits.  acc, g: f32, n elements, 16-byte aligned.
+ *
+ * mobgt_grad_accumulate: acc[i] += g[i] (plain f32 adds; g is only read).  g = NULL: acc is left as it is.  partials
+ * (may be NULL unless g is NULL): OVERWRITTEN with one f32 per block of mobgt_grad_norm_block() consecutive elements,
+ * ceil(n / block) values, the sum of the squares of that block's acc elements AFTER the add, summed in a fixed order.
+ * Accumulator contract of the trainer: acc is ALL ZEROS at the start of a window and all zeros again once
+ * mobgt_adamw_flat_scaled(zero_grads = 1) has consumed it -- nothing zero-fills it in between. */
+int64_t mobgt_grad_norm_block(void);
+int mobgt_grad_accumulate(float* acc, const float* g, int64_t n, float* partials, void* stream);
+/* One workgroup ends the window: with partials (device, n_partials >= 1 values) it sums them in f64 in a fixed order and writes
+ *   *grad_norm = total = inv_k * sqrt(sum)          -- the L2 norm of g = inv_k * acc, BEFORE clipping
+ *   *scale     = inv_k * min(1, clip_norm / (total + 1e-6))     -- torch.nn.utils.clip_grad_norm_, norm_type 2; a non-finite
+ *                                                                   total propagates (error_if_nonfinite=False)
+ * with partials = NULL (no clipping; clip_norm and grad_norm are ignored): *scale = inv_k.  Either way it then adds 1 to
+ * *update_counter (may be NULL).  grad_norm, scale, update_counter are DEVICE pointers; inv_k, clip_norm (> 0) host values. */
+int mobgt_grad_norm_finish(const float* partials, int64_t n_partials, float inv_k, float clip_norm, float* grad_norm,
+                           float* scale, int64_t* update_counter, void* stream);
+/* mobgt_adamw_flat on the gradient *scale_dev * grads[i] (scale_dev: device f32), with the step count
+ * t = *update_counter - step_base >= 1 taken from the per-UPDATE device counter mobgt_grad_norm_finish advances.
+ * zero_grads != 0: grads (the window's accumulator) is OVERWRITTEN with zeros behind the pass; 0: grads is only read.
+ * With *scale_dev == 1.0f the parameters, moments and shadow are bit-identical to mobgt_adamw_flat's (one kernel body). */
+int mobgt_adamw_flat_scaled(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
+                            const float* lr_dev, const float* sched, const int64_t* update_counter, int64_t step_base,
+                            const float* scale_dev, int zero_grads, float beta1, float beta2, float eps, float weight_decay,
+                            void* stream);
+
 /* Small f32 GEMMs of the GCN / FuseEmbeddings / head path (graphormer/modelGNN.py:38-44; model_fqandtoyo.py:444-456 and
  * the data gradients autograd derives from them): c[M,N] = a[M,K] x B (+ bias[N]), all f32, full-f32 products on the
  * matrix core, one wave per 16-row output tile.  b_is_nk = 0: b is [K,N] (x @ W, adj @ support, g @ W);

@@ -102,6 +102,10 @@ SIGNATURES = {
     "mobgt_head_act_fwd": (_i, [_vp] * 6 + [_i, _i, _f, _f, _f, _u64, _vp, _c.c_uint32, _vp]),
     "mobgt_head_act_bwd": (_i, [_vp] * 9 + [_i, _i, _f, _f, _f, _u64, _vp, _c.c_uint32, _vp]),
     "mobgt_adamw_flat": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp]),
+    "mobgt_grad_norm_block": (_i64, []),
+    "mobgt_grad_accumulate": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "mobgt_grad_norm_finish": (_i, [_vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
+    "mobgt_adamw_flat_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i, _f, _f, _f, _f, _vp]),
     "mobgt_small_gemm_f32": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "mobgt_small_gemm_f32_act": (_i, [_vp, _i64, _vp, _f, _f, _f, _vp, _i64, _i, _vp, _i, _f, _f, _u64, _vp, _c.c_uint32, _vp, _i64, _i, _vp, _i64, _vp, _i, _i, _i, _i, _vp]),
     "mobgt_layer_gemm": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _vp]),

@@ -11,6 +11,7 @@
 // f32 atomic per column.  Residual stream and statistics are f32; GEMM-facing tensors are f32 or bf16.
 // Dropout uses the same counter hash as the attention kernels (common.h), regenerated in the backward.
 #include <cstdlib>
+#include <type_traits>
 #include "common.h"
 #include "mobgt_hip.h"
 #include "front_body.h"
@@ -1155,12 +1156,20 @@ extern "C" int mobgt_dropout(const float* x, float* y, int64_t n, int row_len, f
 // decoupled weight decay, bias-corrected moments, eps outside the square root), one pass that also refreshes the
 // bf16 shadow copy the layer GEMMs read.  lr and the step count are DEVICE scalars, so a captured graph sees new
 // values on every replay: t = *step_dev - step_base (the trainer's per-step counter, advanced once per step).
+// SCALED (mobgt_adamw_flat_scaled, the accumulating / clipping train step): the gradient is *scale_dev * g (1 / k and the
+// clipping coefficient, written by grad_norm_finish_kernel), step_dev is the per-UPDATE counter, and with zero_g the
+// gradient buffer -- the window's accumulator -- is left all zeros behind the pass.  One body for both: with a scale of
+// exactly 1 the products are the operands, so the two instantiations give the same bits.
 namespace {
-__global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+template <bool SCALED>
+__global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p,
+                                                         typename std::conditional<SCALED, float*, const float*>::type __restrict__ g,
+                                                         float* __restrict__ m,
                                                          float* __restrict__ v, bf16_t* __restrict__ shadow, int64_t n,
                                                          const float* __restrict__ lr_dev, const float* __restrict__ sched,
                                                          const int64_t* __restrict__ step_dev,
-                                                         int64_t step_base, float beta1, float beta2, float eps, float wd) {
+                                                         int64_t step_base, float beta1, float beta2, float eps, float wd,
+                                                         const float* __restrict__ scale_dev, int zero_g) {
     const float t = (float)(*step_dev - step_base);
     float lr;
     if (sched) {            // PolynomialDecayLR (lr.py:17-31, power = 1) evaluated at its step_count = t + offset
@@ -1169,14 +1178,20 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
     } else {
         lr = *lr_dev;
     }
+    float scale = 1.f;
+    if constexpr (SCALED) scale = *scale_dev;
     const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(beta2, t);
     const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2), decay = 1.f - lr * wd;
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
     if (i + 4 <= n) {
         float4 pp = *reinterpret_cast<float4*>(p + i);
-        const float4 gg = *reinterpret_cast<const float4*>(g + i);
+        float4 gg = *reinterpret_cast<const float4*>(g + i);
         float4 mm = *reinterpret_cast<float4*>(m + i), vv = *reinterpret_cast<float4*>(v + i);
+        if constexpr (SCALED) {
+            gg.x *= scale; gg.y *= scale; gg.z *= scale; gg.w *= scale;
+            if (zero_g) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         float* P = &pp.x; const float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1196,7 +1211,11 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
         }
     } else {
         for (int64_t j = i; j < n; ++j) {
-            const float gj = g[j];
+            float gj = g[j];
+            if constexpr (SCALED) {
+                gj *= scale;
+                if (zero_g) g[j] = 0.f;
+            }
             const float mj = beta1 * m[j] + (1.f - beta1) * gj;
             const float vj = beta2 * v[j] + (1.f - beta2) * gj * gj;
             const float pj = p[j] * decay - step_size * mj / (sqrtf(vj) * inv_sqrt_bc2 + eps);
@@ -1215,9 +1234,124 @@ extern "C" int mobgt_adamw_flat(float* params, const float* grads, float* exp_av
     if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return MOBGT_EALIGN;
     if (shadow_bf16 && ((uintptr_t)shadow_bf16 & 7)) return MOBGT_EALIGN;
     const int64_t blocks = (n + 1023) / 1024;
-    hipLaunchKernelGGL(adamw_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+    hipLaunchKernelGGL(adamw_flat_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
                        exp_avg_sq, reinterpret_cast<bf16_t*>(shadow_bf16), n, lr_dev, sched, step_dev, step_base, beta1, beta2, eps,
-                       weight_decay);
+                       weight_decay, (const float*)nullptr, 0);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mobgt_adamw_flat_scaled(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                       int64_t n, const float* lr_dev, const float* sched, const int64_t* update_counter,
+                                       int64_t step_base, const float* scale_dev, int zero_grads, float beta1, float beta2,
+                                       float eps, float weight_decay, void* stream) {
+    if (n <= 0) return 0;
+    if ((!lr_dev && !sched) || !scale_dev || !update_counter) return MOBGT_EBADDIM;
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return MOBGT_EALIGN;
+    if (shadow_bf16 && ((uintptr_t)shadow_bf16 & 7)) return MOBGT_EALIGN;
+    const int64_t blocks = (n + 1023) / 1024;
+    hipLaunchKernelGGL(adamw_flat_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, reinterpret_cast<bf16_t*>(shadow_bf16), n, lr_dev, sched, update_counter, step_base, beta1, beta2,
+                       eps, weight_decay, scale_dev, zero_grads);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gradient accumulation and the global L2 norm of the accumulated gradient (train.TrainStep(accumulate=, clip_norm=)).
+// One workgroup owns GRAD_NORM_BLOCK consecutive elements: 16-byte loads and stores, a scalar tail in the last workgroup.
+//   ADD : acc += g (plain f32 adds, element by element);
+//   NORM: the f32 sum of the squares of the workgroup's (new) acc elements -- per lane in element order, the wave by
+//         shuffles, the four waves through LDS, all in a fixed order -- as ONE plain store into partials[blockIdx.x].
+// grad_norm_finish_kernel (one workgroup) sums the slab in f64 in a fixed order.  No atomics, no ticket, no workgroup
+// waits for another: identical input gives identical bits, and every launch can be captured.
+namespace {
+constexpr int GRAD_NORM_BLOCK = 4096;            // elements behind one f32 partial (mobgt_grad_norm_block)
+
+template <bool ADD, bool NORM>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n,
+                                                              float* __restrict__ partials) {
+    const int64_t base = (int64_t)blockIdx.x * GRAD_NORM_BLOCK;
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < GRAD_NORM_BLOCK / 1024; ++j) {
+        const int64_t i = base + j * 1024 + (int64_t)threadIdx.x * 4;
+        if (i + 4 <= n) {
+            float4 a = *reinterpret_cast<const float4*>(acc + i);
+            if constexpr (ADD) {
+                const float4 b = *reinterpret_cast<const float4*>(g + i);
+                a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+                *reinterpret_cast<float4*>(acc + i) = a;
+            }
+            if constexpr (NORM) { ss += a.x * a.x; ss += a.y * a.y; ss += a.z * a.z; ss += a.w * a.w; }
+        } else if (i < n) {
+            for (int64_t e = i; e < n; ++e) {
+                float a = acc[e];
+                if constexpr (ADD) { a += g[e]; acc[e] = a; }
+                if constexpr (NORM) ss += a * a;
+            }
+        }
+    }
+    if constexpr (NORM) {
+        __shared__ float part[4];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) ss += __shfl_down(ss, o, 64);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = ss;
+        __syncthreads();
+        if (threadIdx.x == 0) partials[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const float* __restrict__ partials, int64_t n_partials, float inv_k,
+                                                               float clip, float* __restrict__ grad_norm, float* __restrict__ scale,
+                                                               int64_t* __restrict__ counter) {
+    __shared__ double sh[256];
+    if (partials) {          // (uniform)
+        double a = 0.0;
+        for (int64_t i = threadIdx.x; i < n_partials; i += 256) a += (double)partials[i];
+        sh[threadIdx.x] = a;
+        __syncthreads();
+        for (int o = 128; o >= 1; o >>= 1) {
+            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) {
+        float s = inv_k;
+        if (partials) {
+            // torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite=False) on g = inv_k * acc: a non-finite norm
+            // propagates (NaN > 1 is false, so a NaN coefficient stays)
+            const float total = (float)(sqrt(sh[0]) * (double)inv_k);
+            float coef = clip / (total + 1e-6f);
+            if (coef > 1.f) coef = 1.f;
+            *grad_norm = total;
+            s = inv_k * coef;
+        }
+        *scale = s;
+        if (counter) *counter += 1;
+    }
+}
+}  // namespace
+
+extern "C" int64_t mobgt_grad_norm_block(void) { return GRAD_NORM_BLOCK; }
+
+extern "C" int mobgt_grad_accumulate(float* acc, const float* g, int64_t n, float* partials, void* stream) {
+    if (n <= 0) return 0;
+    if (!acc || (!g && !partials)) return MOBGT_EBADDIM;
+    if (((uintptr_t)acc | (uintptr_t)g) & 15) return MOBGT_EALIGN;
+    if ((uintptr_t)partials & 3) return MOBGT_EALIGN;
+    const dim3 grid((unsigned)((n + GRAD_NORM_BLOCK - 1) / GRAD_NORM_BLOCK)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (g && partials) hipLaunchKernelGGL((grad_accumulate_kernel<true, true>), grid, block, 0, st, acc, g, n, partials);
+    else if (g)        hipLaunchKernelGGL((grad_accumulate_kernel<true, false>), grid, block, 0, st, acc, g, n, partials);
+    else               hipLaunchKernelGGL((grad_accumulate_kernel<false, true>), grid, block, 0, st, acc, g, n, partials);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mobgt_grad_norm_finish(const float* partials, int64_t n_partials, float inv_k, float clip_norm, float* grad_norm,
+                                      float* scale, int64_t* update_counter, void* stream) {
+    if (!scale || n_partials < 0) return MOBGT_EBADDIM;
+    if (partials && (n_partials < 1 || !grad_norm || !(clip_norm > 0.f))) return MOBGT_EBADDIM;
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, inv_k, clip_norm,
+                       grad_norm, scale, update_counter);
     return (int)hipGetLastError();
 }
 

@@ -24,6 +24,7 @@ import torch.distributed as dist
 from . import ops
 from .model import sync_external_shadows
 from .lr import polynomial_decay_lr
+from .accum import UpdateWindow, check_accum_args, scheduled_lr
 
 
 def flat_offsets(params, align=8):
@@ -240,11 +241,14 @@ def choose_ddp_form(model, batches, steps=20, warmup=5, candidates=None, **ts_kw
     model's parameters are put back after each, and all ranks agree on the choice (`assert_same_across_ranks`).
     -> (name, TrainStep constructor arguments incl. the environment to set, {name: ms per step}).  With one rank or no process
     group: the default form, nothing timed.  No multi-GPU node has run this yet: the forms' order there is the measurement this
-    function exists to make (the one-rank figures of rounds 4-5 cannot show what an overlap hides)."""
+    function exists to make (the one-rank figures of rounds 4-5 cannot show what an overlap hides).  With `accumulate > 1` or
+    `clip_norm` among the TrainStep arguments the overlap forms are not candidates (TrainStep does not build them)."""
     import time
     forms = candidates or [("one_graph", dict(overlap=False), {}),
                            ("overlap_2", dict(overlap="force"), {"MOBGT_DDP_PARTS": "1"}),
                            ("overlap_3", dict(overlap="force"), {"MOBGT_DDP_PARTS": "3"})]
+    if candidates is None and (ts_kw.get("accumulate", 1) != 1 or ts_kw.get("clip_norm") is not None):
+        forms = forms[:1]
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() <= 1:
         return forms[0][0], forms[0][1], {}
     dev = next(model.parameters()).device
@@ -288,11 +292,22 @@ def choose_ddp_form(model, batches, steps=20, warmup=5, candidates=None, **ts_kw
 
 class TrainStep:
     def __init__(self, model, batches, autocast_dtype=None, use_graph=True, seed=1, overlap=True, batch_fn=None,
-                 grad_comm_dtype=None, keep_head_rows=False):
+                 grad_comm_dtype=None, keep_head_rows=False, accumulate=1, clip_norm=None):
         """`batches`: pre-collated batches resident on the device (their tensors are the static inputs of the captured
         graphs).  `batch_fn`: optional callable applied to a batch INSIDE the step (and so inside its graph) before the model
         sees it -- `EpochLoop` passes raw, un-collated arrays + `DeviceCollator.finish`, so that collating a fresh batch is
-        part of the replayed step.  More batches can be added after `prepare()` with `add_batch`."""
+        part of the replayed step.  More batches can be added after `prepare()` with `add_batch`.
+
+        `accumulate=k` (Lightning's `accumulate_grad_batches`): every `step(i)` is a micro-step -- forward, loss, backward, add
+        into the window -- and the k-th one of a window also updates, from `sum / k`; `flush()` ends a short window (divisor
+        still k).  `clip_norm=c` (Lightning's `gradient_clip_val`, norm clipping): the update's gradient is scaled by
+        `min(1, c / (||g||_2 + 1e-6))` on the device (`torch.nn.utils.clip_grad_norm_`); `grad_norm` holds `||g||_2` before
+        clipping.  The dropout stream advances per micro-step; AdamW's t and the schedule advance per UPDATE (`updates_done`).
+        Data parallel: ONE exchange per window, of the accumulated gradient, before the norm -- built for the captured
+        (`one_graph`) and the host-exchange forms; the `overlap` form raises NotImplementedError with `accumulate > 1` or
+        `clip_norm`.  `accumulate=1, clip_norm=None` (the default) is the plain step: no accumulator, no extra launch."""
+        self.accumulate, self.clip_norm = check_accum_args(accumulate, clip_norm)
+        self._accum = self.accumulate > 1 or self.clip_norm is not None
         self.model = model
         self.batches = list(batches)
         self.batch_fn = batch_fn
@@ -374,6 +389,7 @@ class TrainStep:
         # (5th entry: offset between the kernel's step count t and the schedule's step_count; both start at 1)
         self.sched_dev = torch.tensor([float(s["warmup"]), float(s["tot"]), float(s["lr"]), float(s["end_lr"]), 0.0],
                                       dtype=torch.float32, device=dev) if s["power"] == 1.0 and s["warmup"] > 0 else None
+        self.window = UpdateWindow(self.accumulate)
         self._set_lr()
         self.use_graph = use_graph
         self.graphs = {}
@@ -398,6 +414,9 @@ class TrainStep:
         want_overlap = overlap == "force" or (bool(overlap) and os.environ.get("MOBGT_DDP_OVERLAP") == "1")
         self.overlap = bool(want_overlap and use_graph and (self.ddp or overlap == "force") and self.n_head > 0
                             and hasattr(model, "_enc_out"))
+        if self.overlap and self._accum:
+            raise NotImplementedError("TrainStep: accumulate > 1 / clip_norm are not built for the `overlap` form of the data-parallel "
+                                      "step (its exchange runs beside the backward of every micro-step); use the default form")
         self.graphs_b, self._g_enc, self._loss_slots, self.enc_outs = {}, {}, {}, {}
         self._loss_slots_nocomm = {}
         self._plan_buckets()
@@ -408,7 +427,34 @@ class TrainStep:
         self._prepared = False
         self.comm_buf = (torch.empty(self.flat.flat.numel(), dtype=grad_comm_dtype, device=dev)
                          if (grad_comm_dtype is not None and self.ddp) else None)
+        # Accumulation / clipping: the window's accumulator (all zeros between windows: the scaled AdamW pass zeroes
+        # it behind itself), the slab of per-block sums of squares, and the device scalars of an update -- its gradient norm,
+        # the scale 1/k * coef the optimizer applies, and the per-UPDATE counter AdamW's t and the in-kernel schedule read.
+        # With k = 1 (clipping only) the flat gradient buffer itself is what the update consumes.
+        self.acc = self.partials = self.grad_norm = self.scale_dev = self.upd_dev = None
+        self.upd_graph, self.upd_graph_nocomm, self.exchanges_done = None, None, 0
+        if self._accum:
+            n = self.flat.flat.numel()
+            from . import _lib
+            self.acc = torch.zeros(n, dtype=torch.float32, device=dev) if self.accumulate > 1 else None
+            self._gsrc = self.acc if self.acc is not None else self.flat.flat
+            if self.clip_norm is not None:
+                blk = int(_lib.lib().mobgt_grad_norm_block())
+                self.partials = torch.zeros((n + blk - 1) // blk, dtype=torch.float32, device=dev)
+                self.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+            self.scale_dev = torch.full((), 1.0 / self.accumulate, dtype=torch.float32, device=dev)
+            self.upd_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.check_layout_across_ranks()
+
+    @property
+    def updates_done(self):
+        """Optimizer updates issued so far (host integer)."""
+        return self.window.updates_done
+
+    @property
+    def window_pos(self):
+        """Micro-steps in the open accumulation window (0 right after an update)."""
+        return self.window.window_pos
 
     def _plan_buckets(self):
         """Layer-wise gradient buckets (data parallel; VERDICT r3 next #3a).  `flat_order` lays the buffers out as
@@ -554,8 +600,7 @@ class TrainStep:
 
     # learning rate of lr.py:17-31, kept in a device scalar so captured optimizer graphs see it
     def _set_lr(self):
-        s = self.sched_state
-        self.lr = polynomial_decay_lr(s["step_count"], s["warmup"], s["tot"], s["lr"], s["end_lr"], s["power"])
+        self.lr = scheduled_lr(self.sched_state)
         if self.sched_dev is None:
             self.lr_dev.fill_(self.lr)
 
@@ -742,24 +787,31 @@ class TrainStep:
         self.graphs_b[i] = [gb]
         return g
 
-    def _exchange(self):
-        """Sum of the flat gradient buffer over the ranks and the average, issued on the CURRENT stream (eager, or as nodes of the
-        step graph being captured): through the bf16 exchange buffer when there is one (half the bytes on the wire; the widening
-        pass applies 1 / world), else in place."""
+    def _exchange(self, buf=None):
+        """Sum of the flat gradient buffer (`buf`: the window's accumulator instead) over the ranks and the average, issued on the
+        CURRENT stream (eager, or as nodes of the step graph being captured): through the bf16 exchange buffer when there is one
+        (half the bytes on the wire; the widening pass applies 1 / world), else in place."""
+        if buf is None:
+            buf = self.flat.flat
         if self.comm_buf is not None:
-            self.comm_buf.copy_(self.flat.flat)
+            self.comm_buf.copy_(buf)
             dist.all_reduce(self.comm_buf, op=dist.ReduceOp.SUM)
-            torch.mul(self.comm_buf, 1.0 / self.world, out=self.flat.flat)
-        elif self.world > 1:
+            torch.mul(self.comm_buf, 1.0 / self.world, out=buf)
+        elif self.world > 1 and buf is self.flat.flat:
             self.flat.all_reduce_mean()
+        elif self.world > 1:
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+            buf.div_(self.world)
         else:                                  # (one forced rank: the collective itself, no division)
-            dist.all_reduce(self.flat.flat, op=dist.ReduceOp.SUM)
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM)
 
     def prepare(self):
         """Capture one forward/backward graph per batch and one optimizer graph."""
         if not self.use_graph:
             return
         self.pool = torch.cuda.graph_pool_handle()
+        if self._accum:
+            return self._prepare_accum()
         for i in range(len(self.batches)):
             self.graphs[i] = self._capture(i)
         # One eager optimizer call before the capture (first-launch initialisation must not happen inside a capture),
@@ -817,6 +869,124 @@ class TrainStep:
             if kept is not None:
                 self._loss_slots[i] = kept
 
+    # ---- accumulation windows and global-norm clipping ----------------------------------------------------------
+    # A micro-step is [prologue, forward, backward, accumulate]: ONE graph per batch whatever its position in the window (the
+    # accumulator is zero at a window's start, so the first micro-step adds like every other).  The update -- [exchange],
+    # [norm], finish, scaled AdamW -- is a small graph of its own, replayed after the window's last micro-step: one replay
+    # boundary per window, and a flushed short window needs no second form of any batch's graph.
+    def _accumulate(self):
+        """Tail of a micro-step: acc += the micro-batch's gradient.  On a single rank with clipping the same launch leaves the
+        per-block sums of squares of the new accumulator (after the window's last micro-step they are the update's); with an
+        exchange in between, the norm pass of `_update_kernels` computes them from the exchanged bytes instead."""
+        from . import _lib
+        from .ops import _p, _stream
+        part = self.partials if not self.ddp else None
+        n = self.flat.flat.numel()
+        if self.acc is not None:
+            _lib.check(_lib.lib().mobgt_grad_accumulate(_p(self.acc), _p(self.flat.flat), n, _p(part), _stream()),
+                       "mobgt_grad_accumulate")
+        elif part is not None:                       # (k = 1: nothing to add, the norm of the flat gradient buffer itself)
+            _lib.check(_lib.lib().mobgt_grad_accumulate(_p(self.flat.flat), None, n, _p(part), _stream()), "mobgt_grad_accumulate")
+
+    def _update_kernels(self):
+        """[norm of the exchanged gradient,] finish (grad_norm, scale = coef / k, update counter + 1), AdamW on scale * acc (which
+        leaves the accumulator zero)."""
+        from . import _lib
+        from .ops import _p, _stream
+        lib, n, g = _lib.lib(), self.flat.flat.numel(), self._gsrc
+        if self.partials is not None and self.ddp:
+            _lib.check(lib.mobgt_grad_accumulate(_p(g), None, n, _p(self.partials), _stream()), "mobgt_grad_accumulate")
+        _lib.check(lib.mobgt_grad_norm_finish(_p(self.partials), 0 if self.partials is None else self.partials.numel(),
+                                              1.0 / self.accumulate, self.clip_norm or 0.0, _p(self.grad_norm), _p(self.scale_dev),
+                                              _p(self.upd_dev), _stream()), "mobgt_grad_norm_finish")
+        _lib.check(lib.mobgt_adamw_flat_scaled(_p(self.flat_params.tensor), _p(g), _p(self.exp_avg), _p(self.exp_avg_sq),
+                                               _p(self.shadow_flat), n, _p(self.lr_dev), _p(self.sched_dev), _p(self.upd_dev), 0,
+                                               _p(self.scale_dev), 1 if self.acc is not None else 0, self.betas[0], self.betas[1],
+                                               self.eps, float(self.model.weight_decay), _stream()), "mobgt_adamw_flat_scaled")
+
+    def _capture_micro(self, i, warm=True):
+        if warm:
+            self._warmup(i)
+        g = torch.cuda.CUDAGraph()
+        with self._capturing(g):
+            self._fwd_bwd(self.batches[i], slot=i)
+            self._accumulate()
+        return g
+
+    def _capture_update(self, comm):
+        g = torch.cuda.CUDAGraph()
+        with self._capturing(g):
+            if comm:
+                self._exchange(self._gsrc)
+            self._update_kernels()
+        return g
+
+    def _prepare_accum(self):
+        # one eager pass over the new launches (and the collective on these buffers) before ANY capture that holds them (first
+        # launches must not happen inside a capture), made side-effect free: parameters, moments, accumulator and the update
+        # counter are put back -- the first update is AdamW's t = 1
+        with self._on_stream():
+            with torch.no_grad():
+                saved = self.flat_params.tensor.detach().clone()
+                if self.one_graph:
+                    self._exchange(self._gsrc)
+                self._accumulate()
+                self._update_kernels()
+                self.flat_params.tensor.copy_(saved)
+                self.exp_avg.zero_()
+                self.exp_avg_sq.zero_()
+                self.flat.flat.zero_()
+                if self.acc is not None:
+                    self.acc.zero_()
+                self.upd_dev.zero_()
+                self.sync_shadows()
+        self._join()
+        for i in range(len(self.batches)):
+            self.graphs[i] = self._capture_micro(i)
+        self.fused_opt = False
+        self.upd_graph = self._capture_update(comm=self.one_graph)
+        self.upd_graph_nocomm = None
+        self._prepared = True
+
+    def _update(self):
+        """The optimizer update that ends a window (the host bookkeeping -- `self.window` -- has been done by the caller)."""
+        comm = self.ddp and self.comm
+        if comm:
+            self.exchanges_done += 1
+        if self.use_graph and self.one_graph:
+            if comm:
+                self.upd_graph.replay()                          # (the captured exchange, norm, finish, AdamW)
+            else:
+                if self.upd_graph_nocomm is None:
+                    self.upd_graph_nocomm = self._capture_update(comm=False)
+                self.upd_graph_nocomm.replay()
+        else:
+            if comm:
+                self._exchange(self._gsrc)                       # (issued by the host: gloo, MOBGT_DDP_HOST_EXCHANGE, eager)
+            if self.use_graph:
+                self.upd_graph.replay()
+            else:
+                self._update_kernels()
+        self._set_lr()
+
+    def _step_accum(self, i):
+        j = i % len(self.batches)
+        if self.use_graph:
+            self._loss_ref = self._loss_slots[j]
+            self.graphs[j].replay()
+        else:
+            self._fwd_bwd(self.batches[j])
+            self._accumulate()
+        if self.window.step(self.sched_state):
+            self._update()
+        return self.loss_out
+
+    def flush(self):
+        """End an incomplete accumulation window with an update now (its gradient is still `sum / accumulate`: Lightning divides
+        every micro-loss by k whatever the window's length).  No-op on an empty window, and always without accumulation."""
+        if self._accum and self.window.flush(self.sched_state):
+            self._update()
+
     # ---- several steps per graph replay (round 6) -----------------------------------------------------------------------
     # Between two replayed step graphs the device idles (~60 us of a 0.595 ms S-FSQ step in round 5: 0.534 ms of graph wall
     # time): the replay that follows cannot start before the runtime has retired the one in front of it.  Nothing of a step
@@ -839,6 +1009,8 @@ class TrainStep:
     def step_group(self, i, k):
         """Steps i, i + 1, ... i + k - 1 (batches taken cyclically from the pre-collated pool, like k calls of `step`) as ONE
         graph replay; -> the last step's loss tensor.  Same arithmetic, same counters, same order as k single steps."""
+        if self._accum:
+            raise NotImplementedError("TrainStep.step_group is not built for accumulate > 1 / clip_norm: call step() per micro-step")
         nb = len(self.batches)
         key = (i % nb, int(k))
         if not hasattr(self, "graphs_group"):
@@ -847,7 +1019,7 @@ class TrainStep:
             self._capture_group(*key)
         self._loss_ref = self._loss_slots[("group", key[0], key[1], key[1] - 1)]
         self.graphs_group[key].replay()
-        self.sched_state["step_count"] += key[1]
+        self.window.updated(self.sched_state, key[1])
         self._set_lr()
         return self.loss_out
 
@@ -858,6 +1030,12 @@ class TrainStep:
         if not (self.use_graph and self._prepared):
             return
         self.graphs_nocomm.clear()
+        if self._accum:                                  # (every micro-step graph, and the update graphs with them)
+            for i in range(len(self.batches)):
+                self.graphs[i] = self._capture_micro(i)
+            self.upd_graph = self._capture_update(comm=self.one_graph)
+            self.upd_graph_nocomm = None
+            return
         for i in range(len(self.batches)):
             self.graphs[i] = self._capture(i)
             if self.fused_opt:
@@ -885,7 +1063,11 @@ class TrainStep:
         synchronisation per step: meant for runs that share the device with other streams' persistent kernels."""
         with torch.no_grad():
             snap = (self.flat_params.tensor.detach().clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.seed_dev.clone())
-        sched = dict(self.sched_state)
+            # (accumulation: the open window -- accumulator, its sums of squares, the update counter -- so that the re-run
+            #  micro-step is added once and counted once)
+            snap_acc = [(t, t.clone()) for t in (self.acc, self.partials, self.upd_dev, self.scale_dev, self.grad_norm)
+                        if t is not None]
+        sched, win = dict(self.sched_state), self.window.state()
         loss = self.step(i)
         if not self.check_faults(on_fault="return"):
             return loss
@@ -894,8 +1076,11 @@ class TrainStep:
             self.exp_avg.copy_(snap[1])
             self.exp_avg_sq.copy_(snap[2])
             self.seed_dev.copy_(snap[3])
+            for t, saved in snap_acc:
+                t.copy_(saved)
             self.sync_shadows()
         self.sched_state = sched
+        self.window.restore(win)
         self._set_lr()
         ops.SAFE_FORMS[0] = True
         ops.set_peer_wait_limit(0, 0)
@@ -916,14 +1101,19 @@ class TrainStep:
             self.batches.pop()
             raise
         if self.use_graph and self._prepared:
-            if self.fused_opt:
+            if self._accum:
+                self.graphs[i] = self._capture_micro(i, warm=False)     # (the update graphs do not depend on the batch)
+            elif self.fused_opt:
                 self._capture_with_opt(i)               # (the whole step as one graph: no forward / backward-only graph beside it)
             else:
                 self.graphs[i] = self._capture(i, warm=False)
         return i
 
     def step(self, i):
-        """One optimizer step on pre-collated batch i (model_fqandtoyo.py:1434-1478 + optimizer + scheduler)."""
+        """One optimizer step on pre-collated batch i (model_fqandtoyo.py:1434-1478 + optimizer + scheduler).  With
+        `accumulate` / `clip_norm`: one micro-step; the window's last one also updates.  -> this batch's loss."""
+        if self._accum:
+            return self._step_accum(i)
         if self.use_graph:
             self._loss_ref = self._loss_slots[i % len(self.batches)]
         if self.one_graph and self.use_graph and getattr(self, "fused_opt", False):
@@ -935,7 +1125,7 @@ class TrainStep:
                     self._capture_with_opt(j, comm=False)
                 self._loss_ref = self._loss_slots_nocomm[j]     # (the loss of the graph that is replayed)
                 self.graphs_nocomm[j].replay()
-            self.sched_state["step_count"] += 1
+            self.window.updated(self.sched_state)
             self._set_lr()
             return self.loss_out
         if self.overlap:
@@ -977,7 +1167,7 @@ class TrainStep:
                 self.opt_graph.replay()
         else:
             self._opt_step()
-        self.sched_state["step_count"] += 1
+        self.window.updated(self.sched_state)
         self._set_lr()
         return self.loss_out
 
@@ -1089,8 +1279,11 @@ class EpochLoop(_StagedBatches):
     """
 
     def __init__(self, model, collator, dataset, batch_size=16, seed=1, use_graph=True, overlap=True, buckets=None, rank=None,
-                 world=None, shuffle=True, autocast_dtype=None, side_collate=True, balance=None, balance_window=32):
-        """`balance`: deal every step's batches by length over the ranks (`data.balanced_batches`: neighbouring shape buckets on
+                 world=None, shuffle=True, autocast_dtype=None, side_collate=True, balance=None, balance_window=32,
+                 accumulate=1, clip_norm=None):
+        """`accumulate`, `clip_norm`: passed to `TrainStep` (Lightning's `accumulate_grad_batches` / `gradient_clip_val`); every
+        batch is then a micro-step and `run_epoch` flushes the window after the epoch's last batch (an epoch's last batch
+        always steps).  `balance`: deal every step's batches by length over the ranks (`data.balanced_batches`: neighbouring shape buckets on
         all ranks in every synchronous step, the epoch's sample set still DistributedSampler's).  Default: on when there is more
         than one rank; with one rank the order is the reference's (DistributedSampler order, consecutive batches).
         `balance_window`: the length sort runs inside windows of that many steps of the permuted epoch (default 32: a
@@ -1112,6 +1305,9 @@ class EpochLoop(_StagedBatches):
         self.slots = {}
         self.ts = None
         self._ts_args = dict(autocast_dtype=autocast_dtype, use_graph=use_graph, seed=seed, overlap=overlap)
+        check_accum_args(accumulate, clip_norm)          # (fail at construction, not at the first batch)
+        if accumulate != 1 or clip_norm is not None:
+            self._ts_args.update(accumulate=accumulate, clip_norm=clip_norm)
         self.steps_done = 0
         self.limits = None
         self.side_collate = bool(side_collate)
@@ -1183,6 +1379,7 @@ class EpochLoop(_StagedBatches):
         # peer waits that gave up during the epoch (the kernels count and carry on, csrc/chain.hip WS_FAULT): raise here, once
         # per epoch, rather than train on silently (one device synchronisation; every rank takes the same decision)
         if self.ts is not None:
+            self.ts.flush()                              # (accumulation: the epoch's last window updates, however short)
             self.ts.check_faults(on_fault="raise")
         return dict(steps=steps, graphs=len(self.slots), sample_ids=seen)
 
