@@ -1109,7 +1109,11 @@ __global__ __launch_bounds__(ONE_NW * 64) void attn_bwd_one_kernel(const AttnPar
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const bool ok = k_ok && (ks * 16 + 8 * hi < D);
-        load_frag(K + (int64_t)kc * p.ldk + ks * 16 + 8 * hi, ok, p.scale, kf[ks]);
+        // (the softmax scale rides on the staged Q rows, as on the forward's Q fragment: S is then formed from the forward's very
+        //  operands bf16(q scale) and k.  On the K fragment -- bf16(k scale), as in the dK / dV pass above -- the re-formed P_b
+        //  differ from the forward's wherever scale is not a power of two (d = 24, 32), while l' and delta belong to the forward's:
+        //  sum_j dS_j != 0, and dQ lost the cancellation of what all keys share -- tests/test_gpu_attn_matrix.py, family "common")
+        load_frag(K + (int64_t)kc * p.ldk + ks * 16 + 8 * hi, ok, 1.f, kf[ks]);
         load_frag(V + (int64_t)kc * p.ldv + ks * 16 + 8 * hi, ok, DROP ? p.inv_keep : 1.f, vf[ks]);
     }
     uint64_t seed = 0;
@@ -1168,11 +1172,11 @@ __global__ __launch_bounds__(ONE_NW * 64) void attn_bwd_one_kernel(const AttnPar
     const int my_half = (wave >> 1) & 1;
     auto stage_store = [&](const int c) {
         (void)c;
-        bf16x8 b = sreg.as_bf16();
-        float mq = 0.f, il = 1.f;
-        if (!is_q) {                                     // (wave-uniform: waves 4 .. 7)
+        bf16x8 b;
+        float mq = 0.f, il = p.scale;                    // Q rows: bf16(q scale), the forward's Q operand (and dK = sum_i dS_i of it)
+        if (!is_q) row_norm(lse_s, mq, il);              // (wave-uniform: waves 4 .. 7)  dO rows: dO~ = bf16(dO / l')
+        {
             float a8[8];
-            row_norm(lse_s, mq, il);
             sreg.get(a8);
 #pragma unroll
             for (int i = 0; i < 8; ++i) a8[i] *= il;
@@ -1407,7 +1411,7 @@ __global__ __launch_bounds__(ONE_NW * 64) void attn_bwd_one_kernel(const AttnPar
             if (16 * hi + 8 * j < D) {
                 float a[8], b[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) { a[i] = dk[8 * j + i] * p.scale; b[i] = DROP ? dv[8 * j + i] * p.inv_keep : dv[8 * j + i]; }
+                for (int i = 0; i < 8; ++i) { a[i] = dk[8 * j + i]; b[i] = DROP ? dv[8 * j + i] * p.inv_keep : dv[8 * j + i]; }   // (scale: inside the staged Q)
                 store8(DK + 8 * j, a);
                 store8(DV + 8 * j, b);
             }
