@@ -686,7 +686,7 @@ def test_chain_cluster_form_equals_the_one_workgroup_form(C, R, p):
     are added in 4 / 2 parts before the same bf16 rounding point, so values agree to one bf16 ulp of the rounded
     intermediate.  Runs every launch twice (the hand-over counters must carry over) and at R = 1040 / 1500 the 2-member
     form."""
-    import ctypes
+    from chain_abi import pack
     from mobgt_amd import _lib
     from mobgt_amd.fused_layer import chain_workspace
     from mobgt_amd.ops import _p, _stream
@@ -696,13 +696,6 @@ def test_chain_cluster_form_equals_the_one_workgroup_form(C, R, p):
     bf = lambda *s, k=1.0: (torch.randn(*s, generator=g) * k).to(DEV).bfloat16()
     f32 = lambda *s, k=1.0: (torch.randn(*s, generator=g) * k).to(DEV)
 
-    def pack(w, transposed=False):
-        out = torch.empty(w.numel(), dtype=torch.bfloat16, device=DEV)
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        N, K = (w.shape[1], w.shape[0]) if transposed else w.shape
-        _lib.check(lib.mobgt_pack_mfma_b(1, (vp * 1)(w.data_ptr()), (vp * 1)(out.data_ptr()), (ci * 1)(N), (ci * 1)(K),
-                                         (ci * 1)(1 if transposed else 0), _stream()), "mobgt_pack_mfma_b")
-        return out
     wo, w1, w2, wq = bf(C, C, k=C ** -0.5), bf(F, C, k=C ** -0.5), bf(C, F, k=F ** -0.5), bf(3 * C, C, k=C ** -0.5)
     bo, b1, b2, bq = bf(C, k=0.1), bf(F, k=0.1), bf(C, k=0.1), bf(3 * C, k=0.1)
     n1w, n1b, nxw, nxb = 1 + f32(C, k=0.1), f32(C, k=0.1), 1 + f32(C, k=0.1), f32(C, k=0.1)
@@ -771,7 +764,7 @@ def test_chain_64_row_backward_entry_equals_the_16_row_form(C, R, p):
     saved tensors of a 16-row forward, at ragged R (one to six row blocks): df is bit-identical up to the norm's summation
     order, everything behind it to bf16 round-off; db1 against the column sums of du.  And the dispatch rule: past 4 096 rows
     mobgt_layer_chain_bwd takes the 64-row form, which has no guests -- a hosted tail is refused (MOBGT_EBADDIM)."""
-    import ctypes
+    from chain_abi import pack
     from mobgt_amd import _lib
     from mobgt_amd.ops import _p, _stream
     lib = _lib.lib()
@@ -780,13 +773,6 @@ def test_chain_64_row_backward_entry_equals_the_16_row_form(C, R, p):
     bf = lambda *s, k=1.0: (torch.randn(*s, generator=g) * k).to(DEV).bfloat16()
     f32 = lambda *s, k=1.0: (torch.randn(*s, generator=g) * k).to(DEV)
 
-    def pack(w, transposed=False):
-        out = torch.empty(w.numel(), dtype=torch.bfloat16, device=DEV)
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        N, K = (w.shape[1], w.shape[0]) if transposed else w.shape
-        _lib.check(lib.mobgt_pack_mfma_b(1, (vp * 1)(w.data_ptr()), (vp * 1)(out.data_ptr()), (ci * 1)(N), (ci * 1)(K),
-                                         (ci * 1)(1 if transposed else 0), _stream()), "mobgt_pack_mfma_b")
-        return out
     wo, w1, w2 = bf(C, C, k=C ** -0.5), bf(F, C, k=C ** -0.5), bf(C, F, k=F ** -0.5)
     bo, b1, b2 = bf(C, k=0.1), bf(F, k=0.1), bf(C, k=0.1)
     n1w, n1b, nxw, nxb = 1 + f32(C, k=0.1), f32(C, k=0.1), 1 + f32(C, k=0.1), f32(C, k=0.1)
