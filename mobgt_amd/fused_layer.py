@@ -14,7 +14,7 @@ import ctypes
 
 import torch
 
-from . import _lib, ops
+from . import _lib, forms, ops
 from ._lib import check
 from .ops import _p, _stream, _DT
 
@@ -43,7 +43,6 @@ def _wgrad_hip(dtype, M, N, R):
     return dtype == torch.bfloat16 and M % 2 == 0 and N % 2 == 0 and (M * N <= _WGRAD_HIP_MN[0] or R <= 4096)
 
 
-import os as _os_wg
 _WGRAD_HIP_MN = [131072]      # outputs up to which long batches stay on csrc/wgrad.hip
 
 
@@ -152,12 +151,8 @@ def _mm_tn_f32(g, x, sink=None):
 
 
 _ADDMM_OUT_DTYPE = [None]
-import os as _os
-_os_ln = _os
-_TAIL = [True]
-# (round 4 measured and round 5 removed: the 16-row chain kernels also past 4 096 rows -- S-BIG 9.53 -> 10.93 ms: a 16-row
+# (forms "chain_big"; round 4 measured and round 5 removed: the 16-row chain kernels also past 4 096 rows -- S-BIG 9.53 -> 10.93 ms: a 16-row
 #  workgroup re-streams the layer's weights from L2 785 times and loses against the library's tiles there)
-_OWN_GEMM = [True]            # (False: the layer's GEMMs through torch -- tests flip it)
 
 
 def _addmm_f32(c, a, b, inplace=False):
@@ -181,20 +176,13 @@ def _k1_fwd(x, y, x1, w, b, z, z32, mean, rstd, R, C, p, seed, seed_dev, salt, a
                                               p, seed, _p(seed_dev), salt, act, _stream()), "mobgt_dropout_add_ln_fwd")
 
 
-_LN_GEMM = [True]                                               # False: the two-launch form (tests)
-# Measured on the S-FSQ step (608 rows, C = 192), kernel durations inside the replayed graph:
+# forms "ln_gemm" / "ln_gemm_bwd" (csrc/lngemm.hip).  Measured on the S-FSQ step (608 rows, C = 192), kernel durations inside the replayed graph:
 #   forward   dropout_add_ln 4.8 us + FFN-1 GEMM 5.2 us  ->  fused 9.1 us
 #   backward  dropout_add_ln' 5.7 us + GEMM 5.7 us       ->  fused 12.9 - 14.4 us (the first column tile of every row block
 #             also reduces dgamma / dbeta / dbias and is the last workgroup to finish)
 # i.e. the gaps between dependent launches of a replayed graph are ~0.1 us; what a stage costs is its own ramp-up + one
 # memory round trip, and fusing two stages saves only the intermediate's round trip.  The forward fusion is on by
 # default, the two backward ones only with MOBGT_LN_GEMM_BWD=1 (kept: parity-tested, and the better trade at other sizes).
-_LN_GEMM_BWD = [_os_ln.environ.get("MOBGT_LN_GEMM_BWD") == "1"]
-# csrc/chain.hip: out-proj -> LN -> FFN -> LN -> the next layer's QKV in one launch (MOBGT_NO_CHAIN=1: the separate launches)
-_CHAIN = [_os_ln.environ.get("MOBGT_NO_CHAIN") != "1"]
-_CHAIN_BIG = [_os_ln.environ.get("MOBGT_NO_CHAIN_BIG") != "1"]      # ... past 4 096 rows: the 64-row forward chain (else the library's GEMMs)
-_CHAIN_BWD = [True]
-_WGRAD_BIG = [True]      # past 4 096 rows: the layer's weight gradients as one launch (csrc/wgradbig.hip)      # ... and the same chain backwards (d(out) -> d(attention out))
 
 
 # ---- what a layer's backward may leave to the backward of the layer BELOW it --------------------------------------------------
@@ -204,8 +192,7 @@ _WGRAD_BIG = [True]      # past 4 096 rows: the layer's weight gradients as one 
 # chain_bwd (its forward produced this layer's qkv), this layer returns dx1 as its input gradient, parks (dqkv, Wqkv^T, the
 # four problems) under that tensor's address, and the lower layer's chain launch finishes dx per row block in front of its
 # first norm and runs the weight gradients as extra workgroups (csrc/chain.hip).  A parked entry that no layer picks up is
-# an error, raised when the backward pass ends -- never a silently incomplete gradient.
-_DEFER = [_os_ln.environ.get("MOBGT_NO_DEFER_TAIL") != "1"]
+# an error, raised when the backward pass ends -- never a silently incomplete gradient.  (forms "defer_tail")
 _DEFER_MAX_R = [4096]      # S-GOW: 1024 / 2048 / 4096 / 16384 -> 18.96 / 19.33 / 19.65 / 19.5 k check-ins/s
 _PENDING_TAIL = {}          # (graph task id, device index, address of dx1) -> parked work; see _pending_key
 _PENDING_CB = [None]        # graph task id for which the end-of-backward check is queued
@@ -278,8 +265,8 @@ def chain_workspace(dev, C=192, R=None):
     geometry (model width C, cluster size 4 / 2 -- csrc/chain.hip: pick_ncl): a row block's exchange area is addressed as
     block x members x 16 x C, so launches of different geometry on one workspace would poll words another block wrote, and
     a stale packet whose generation happens to match would be accepted.  Must exist before a graph capture starts
-    (an eager warm-up step creates it).  ops.SAFE_FORMS -> None (one-workgroup form)."""
-    if ops.SAFE_FORMS[0]:
+    (an eager warm-up step creates it).  forms "safe_forms" -> None (one-workgroup form)."""
+    if forms.on("safe_forms"):
         return None
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     nblk = (int(R) + 15) // 16 if R is not None else 1
@@ -294,13 +281,13 @@ def chain_workspace(dev, C=192, R=None):
 
 
 def _chain_ok(C, F, *ts):
-    return (_CHAIN[0] and (C, F) in ((128, 1024), (192, 1024), (256, 1024))
+    return (forms.on("chain") and (C, F) in ((128, 1024), (192, 1024), (256, 1024))
             and all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in ts))
 
 
 def _ln_gemm_ok(C, *ts):
     """csrc/lngemm.hip: bf16 activations, model width a multiple of 32 up to 256, contiguous operands."""
-    return (_LN_GEMM[0] and C % 32 == 0 and C <= 256
+    return (forms.on("ln_gemm") and C % 32 == 0 and C <= 256
             and all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in ts))
 
 
@@ -383,8 +370,8 @@ class _FusedLayerFn(torch.autograd.Function):
         elif stock:                                                   # y = self_attention_norm(x)  (model.py:480)
             xa = torch.empty(R, C, dtype=A, device=dev)
             # (the first layer of a stack: norm + QKV projection as one launch when the own-GEMM path takes the layer -- below)
-            norm_in_gemm = (A == torch.bfloat16 and qkv_pre is None and _OWN_GEMM[0] and ops.layer_gemm_ok(xa, s_wqkv)
-                            and _ln_gemm_ok(C, x, s_wqkv, s_bqkv, nxw, nxb) and _os_ln.environ.get("MOBGT_NO_STOCK_LN_QKV") != "1")
+            norm_in_gemm = (A == torch.bfloat16 and qkv_pre is None and forms.on("own_gemm") and ops.layer_gemm_ok(xa, s_wqkv)
+                            and _ln_gemm_ok(C, x, s_wqkv, s_bqkv, nxw, nxb) and forms.on("stock_ln_qkv"))
             if not norm_in_gemm:
                 _k1_fwd(x, None, None, nxw, nxb, xa, None, stats[0], stats[1], R, C, 0.0, seed, sd, salt, act)
         else:
@@ -396,7 +383,7 @@ class _FusedLayerFn(torch.autograd.Function):
                 xa = x.view(R, C).to(A)
         # bf16 configuration at MobGT's sizes: the split-K MFMA kernel of csrc/gemm.hip (GELU fused after FFN layer 1);
         # otherwise the library
-        own = _OWN_GEMM[0] and ops.layer_gemm_ok(xa, s_wqkv) and ops.layer_gemm_ok(xa, s_w1) and C % 32 == 0 \
+        own = forms.on("own_gemm") and ops.layer_gemm_ok(xa, s_wqkv) and ops.layer_gemm_ok(xa, s_w1) and C % 32 == 0 \
             and s_w1.shape[0] % 32 == 0
         ctx.own_gemm = own
         if qkv_pre is not None and qkv_pre.dtype == A and qkv_pre.numel() == 3 * R * C and (not stock or chained_in):
@@ -415,12 +402,12 @@ class _FusedLayerFn(torch.autograd.Function):
         cfg.out_qkv = None
         # (past 4 096 rows `own` is off -- the library's GEMMs take the layer's products -- but the forward chain has its 64-row
         #  form there: csrc/chain.hip, layer_chain_fwd_big_kernel; the backward then runs the library's launches)
-        use_chain = (not stock and (own or (R > 4096 and _CHAIN_BIG[0])) and A == torch.bfloat16 and cfg.packed is not None
+        use_chain = (not stock and (own or (R > 4096 and forms.on("chain_big"))) and A == torch.bfloat16 and cfg.packed is not None
                      and _chain_ok(C, F, x, a, s_bo, s_b1, s_b2, n1w, n1b, nxw, nxb, *cfg.packed))
         # pre-LN chain (round 4): out-projection ... second residual add in one launch, + the NEXT layer's self_attention_norm
         # and QKV projection when the model named that layer (cfg.next_norm / next_qkv); the backward is the chain's too
         need_bwd = any(ctx.needs_input_grad)
-        bwd_ok = bool(_CHAIN_BWD[0] and cfg.packed_t is not None and len(cfg.packed_t) > 3
+        bwd_ok = bool(forms.on("chain_bwd") and cfg.packed_t is not None and len(cfg.packed_t) > 3
                       and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in cfg.packed_t))
         stock_chain = (stock and own and A == torch.bfloat16 and cfg.packed is not None and (bwd_ok or not need_bwd)
                        and _wgrad_hip(A, F, C, R) and _chain_ok(C, F, x, a, s_bo, s_b1, s_b2, n1w, n1b, *cfg.packed))
@@ -430,7 +417,7 @@ class _FusedLayerFn(torch.autograd.Function):
             raise RuntimeError("mobgt fused layer (pre-LN): the layer below chained into this one, which cannot run its chain kernels")
         ctx.fuse_ln = use_chain and own
         # (past 4 096 rows both chains are the 64-row kernels of csrc/chain.hip; the backward hosts the upper layer's tail only)
-        ctx.chain_bwd = bool(use_chain and _CHAIN_BWD[0] and cfg.packed_t is not None and (R <= 4096 or _CHAIN_BIG[0])
+        ctx.chain_bwd = bool(use_chain and forms.on("chain_bwd") and cfg.packed_t is not None and (R <= 4096 or forms.on("chain_big"))
                              and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in cfg.packed_t))
         # the layer below produced this layer's qkv in ITS chain launch and will run chain_bwd: it can host what this layer's
         # backward leaves undone (see _PENDING_TAIL)
@@ -549,7 +536,7 @@ class _FusedLayerFn(torch.autograd.Function):
         seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
         k_qkv, k_wo, k_w1, k_w2 = ctx.sinks
         df = torch.empty(R, C, dtype=A, device=dev)
-        fuse_ln = ctx.fuse_ln and _LN_GEMM_BWD[0]
+        fuse_ln = ctx.fuse_ln and forms.on("ln_gemm_bwd")
         du = None
         if stock:
             dx2 = dout                                                # grad at x2 = x1 + dropout(f)
@@ -669,7 +656,7 @@ class _FusedLayerFn(torch.autograd.Function):
                     check(_lib.lib().mobgt_colsum(_p(du), _p(db1), R, F, act, _stream()), "mobgt_colsum")
             da = da.view(G, T, C)
             big_items = None
-            if R > 4096 and _WGRAD_BIG[0] and A == torch.bfloat16 and not db1_in_wgrad:
+            if R > 4096 and forms.on("wgrad_big") and A == torch.bfloat16 and not db1_in_wgrad:
                 # past 4 096 rows: all four weight gradients of the layer (and dbqkv) as ONE launch behind the attention backward
                 # (csrc/wgradbig.hip, round 6; before: three library split-K GEMMs, the grouped kernel for dWo, a column-sum launch)
                 big_items = [(df, h, None, k_w2), (du, z, None, k_w1), (dy, a.view(R, C), None, k_wo)]
@@ -695,10 +682,10 @@ class _FusedLayerFn(torch.autograd.Function):
             if big_items is not None:
                 dw2, dw1, dwo = ops.layer_wgrad_big(big_items, R)
             dwqkv = wb.add(dqkv2, xa, db=dbqkv, sink=k_qkv)
-        defer = (_DEFER[0] and getattr(ctx, "below_hosts", False) and own and not stock and _TAIL[0] and len(wb.items) == 4
+        defer = (forms.on("defer_tail") and getattr(ctx, "below_hosts", False) and own and not stock and forms.on("tail") and len(wb.items) == 4
                  and R <= _DEFER_MAX_R[0] and dx1.data_ptr() % 16 == 0 and dqkv2.is_contiguous() and ctx.small_sink is not None
                  and all(k is not None for k in ctx.sinks))
-        big_defer = (not defer and _DEFER[0] and getattr(ctx, "below_hosts", False) and not stock and _TAIL[0] and R > 4096
+        big_defer = (not defer and forms.on("defer_tail") and getattr(ctx, "below_hosts", False) and not stock and forms.on("tail") and R > 4096
                      and dx1.data_ptr() % 16 == 0 and dqkv2.is_contiguous() and dqkv2.data_ptr() % 16 == 0)
         if big_defer:
             # past 4 096 rows: the 64-row chain of the layer below finishes dx = dx1 + dqkv Wqkv in front of its first norm (a
@@ -733,7 +720,7 @@ class _FusedLayerFn(torch.autograd.Function):
             rode = False
         else:
             # fq variant, own GEMMs: dx = dx1 + dqkv Wqkv rides in the weight-gradient launch
-            rode = wb.flush(tail=(dqkv2, s_wqkv, dx1) if (own and not stock and _TAIL[0]) else None)
+            rode = wb.flush(tail=(dqkv2, s_wqkv, dx1) if (own and not stock and forms.on("tail")) else None)
         if rode:
             dx = dx1
         elif stock:                                                     # back through self_attention_norm

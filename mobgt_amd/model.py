@@ -14,14 +14,13 @@ Graphormer), so reference checkpoints load unchanged.  What differs is where the
 Lightning glue, FLAG, ogb/ZINC branches of the reference are out of scope.
 """
 import math
-import os
 import weakref
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import forms, ops
 
 
 def init_bert_params(module, n_layers):
@@ -245,9 +244,8 @@ def fused_layer_forward(layer, variant, x, attn_bias, n1, nx, next_layer=None):
             # pre-LN (model.py:479-489): the next layer's self_attention_norm AND its QKV projection ride in this layer's chain
             # launch; that layer then has no norm / projection of its own and leaves the norm's backward to this layer's chain
             # (fused_layer._PENDING_TAIL) -- so not across a cut of the trainer's backward pass, and not without deferral
-            from . import fused_layer as _fl
             bwd_ok = (not torch.is_grad_enabled()) or (getattr(nxt, "_packed_t_fresh", False) and getattr(layer, "_packed_t_fresh", False))
-            if _fl._DEFER[0] and not getattr(nxt, "_mobgt_cut", False) and getattr(layer, "_packed_fresh", False) and bwd_ok:
+            if forms.on("defer_tail") and not getattr(nxt, "_mobgt_cut", False) and getattr(layer, "_packed_fresh", False) and bwd_ok:
                 cfg.next_qkv = (nxt._packed[0], nxt._shadows[1])
                 cfg.next_norm = (nxt.self_attention_norm.weight, nxt.self_attention_norm.bias)
     if getattr(layer, "_packed_fresh", False) is True and act != torch.float32 and not amp:
@@ -398,18 +396,17 @@ def pack_layer_weights(layers, defer=False, rows=None):
     """MFMA-operand-order copies of the fused layers' (fq post-LN and, since round 4, model.py's pre-LN) bf16 GEMM weights (csrc/chain.hip reads a wave's B operand as one
     contiguous KB), all layers in one launch (up to 96 weights): `layer._packed` = (wqkv, wo, w1, w2) packed for the
     forward chain and, when gradients are enabled, `layer._packed_t` = (w2^T, w1^T, wo^T, wqkv^T) for the backward chain."""
-    from . import fused_layer
     flush_pending_pack()                                     # (a pack deferred earlier and never picked up)
-    if not fused_layer._CHAIN[0]:
+    if not forms.on("chain"):
         return
-    want_t = torch.is_grad_enabled() and fused_layer._CHAIN_BWD[0]
+    want_t = torch.is_grad_enabled() and forms.on("chain_bwd")
     # `rows`: the batch's token rows, when the caller knows them.  Past 4 096 rows the FORWARD runs the 64-row chain kernel
     # (csrc/chain.hip: layer_chain_fwd_big_kernel / layer_chain_bwd_big_kernel, round 5): the same packs as below them.
     # MOBGT_NO_CHAIN_BIG=1: the library's GEMMs forward as well -- nothing reads a pack then but the token-assembly launch, which
     # multiplies by the FIRST layer's QKV weight.
     big = rows is not None and rows > 4096
-    qkv0_only = big and not fused_layer._CHAIN_BIG[0]
-    if big and not fused_layer._CHAIN_BIG[0]:
+    qkv0_only = big and not forms.on("chain_big")
+    if big and not forms.on("chain_big"):
         want_t = False
     jobs = []
     for li, layer in enumerate(layers):
@@ -455,11 +452,10 @@ def pack_layer_weights(layers, defer=False, rows=None):
             layer._packed_ver = (ver, what, want_t_l)
         layer._packed_fresh = True
         layer._packed_t_fresh = want_t_l
-    import os
     # (as a passenger only while the pack is short next to the 26 us host launch: 6.5 M elements at S-FSQ = 11.7 us alone.  At
     #  S-BIG -- 18.9 M -- the passengers outlasted the network: 102 us for 28 + 37, measured)
     small = sum(j[2] * j[3] for j in jobs) <= (8 << 20)
-    if defer and jobs and len(jobs) <= 96 and small and os.environ.get("MOBGT_NO_PACK_PASSENGER") != "1":
+    if defer and jobs and len(jobs) <= 96 and small and forms.on("pack_passenger"):
         _PENDING_PACK.extend(jobs)
     else:
         _launch_pack(jobs)
@@ -605,7 +601,7 @@ class Graphormer(nn.Module):
         deg_raw = in_degree.reshape(xi.shape)
         one_launch = (ops.stock_tokens_ok(xi, *tabs, self.graph_token.weight)
                       and deg_raw.dtype in (torch.int64, torch.int32, torch.int16))
-        if one_launch and os.environ.get("MOBGT_NO_STOCK_FRONT") != "1":
+        if one_launch and forms.on("stock_front"):
             # round 4: the hop table's forward and the layers' weight pack are left as jobs and ride in the launch of the encoder
             # input (three independent front launches as one grid); the bias build follows it
             ops.front_deferral(True)

@@ -9,12 +9,13 @@ names and init match the reference.  Two MI355X-minded changes in HOW the same m
   workgroups (measured 153 us each), so they are evaluated split-K as a batched GEMM + a sum.
 """
 import math
-import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn import Parameter
+
+from . import forms
 
 
 def mm_tn_splitk(x, g, max_chunks=32, bf16_operands=False, dw=None):
@@ -54,7 +55,6 @@ def _mm_f32(a, b, bias=None):
     return out + bias if bias is not None else out
 
 
-import os as _os
 _SMALL_GEMM = True
 
 
@@ -293,7 +293,7 @@ class _ConvActFn(torch.autograd.Function):
 
 
 def _conv_act_ok(t_cols, weight, bias):
-    return (os.environ.get("MOBGT_NO_CONV_ACT") != "1" and weight.is_cuda and weight.dtype == torch.float32 and bias is not None
+    return (forms.on("conv_act") and weight.is_cuda and weight.dtype == torch.float32 and bias is not None
             and weight.shape[0] == t_cols and t_cols <= 64 and t_cols % 2 == 0 and weight.shape[1] % 2 == 0
             and weight.is_contiguous())
 
@@ -338,8 +338,6 @@ def spmm(adj, b, bias=None, rows=None, transposed=False):
     return out
 
 
-import os as _os_sp
-_SP_GATHER = [True]                                                # False: the atomic scatter (tests)
 
 
 class _SpConvFn(torch.autograd.Function):
@@ -364,7 +362,7 @@ class _SpConvFn(torch.autograd.Function):
         g = g.contiguous()
         if rows is None:
             d_support = spmm(adj, g, transposed=True)                   # adj^T @ g: a gather over the stored transpose
-        elif _SP_GATHER[0] and g.shape[1] % 4 == 0 and g.shape[1] <= 512:
+        elif forms.on("sp_gather") and g.shape[1] % 4 == 0 and g.shape[1] <= 512:
             # adj[rows]^T @ g as a gather over the stored transpose (no atomics, every row written: no zero fill)
             P = adj.shape[1]
             head = getattr(adj, "_rows_head", None)
@@ -439,8 +437,7 @@ class GraphConvolution(nn.Module):
 def _small_gcn_ok(gcn, x, adj, adj_x, adj_t):
     """The whole network as one launch each way (csrc/smallgcn.hip): a 3-layer GCN on a small dense f32 graph whose
     constant first product adj @ x and transpose are supplied."""
-    from . import ops as _ops
-    if os.environ.get("MOBGT_NO_SMALL_GCN") == "1" or _ops.SAFE_FORMS[0] or len(gcn.gcn) != 3:
+    if not forms.on("small_gcn") or forms.on("safe_forms") or len(gcn.gcn) != 3:
         return False
     if not (torch.is_tensor(adj) and adj.is_cuda and adj.dtype == torch.float32 and adj.dim() == 2 and adj.is_contiguous()):
         return False
@@ -640,7 +637,7 @@ class _DistGcnFn(torch.autograd.Function):
 
 def _dist_gcn_ok(gcn, adj_x_pad, rows, mask_adj):
     """The shapes / layouts _DistGcnFn's kernels take (anything else keeps the launch-per-product path)."""
-    if os.environ.get("MOBGT_NO_DIST_GCN_FUSED") == "1" or adj_x_pad is None or rows is None or mask_adj is None or len(gcn.gcn) != 3:
+    if not forms.on("dist_gcn_fused") or adj_x_pad is None or rows is None or mask_adj is None or len(gcn.gcn) != 3:
         return False
     g0, g1, g2 = gcn.gcn
     if not (adj_x_pad.is_cuda and adj_x_pad.dtype == torch.float32 and adj_x_pad.is_contiguous() and adj_x_pad.shape[1] % 16 == 0
@@ -727,7 +724,7 @@ class GCN(nn.Module):
                 if (pre_pad is not None and mask_adj is not None and not isinstance(adj, CsrAdj) and i + 1 < n_hidden
                         and pre_pad.dtype == torch.float32 and pre_pad.is_contiguous() and pre_pad.shape[1] % 16 == 0
                         and 0 <= pre_pad.shape[1] - gc.in_features < 16 and gc.bias is not None and gc.out_features in (16, 32, 48, 64)
-                        and gc.weight.is_contiguous() and os.environ.get("MOBGT_NO_CONV_ACT") != "1"
+                        and gc.weight.is_contiguous() and forms.on("conv_act")
                         and _conv_act_ok(gc.out_features, self.gcn[i + 1].weight, self.gcn[i + 1].bias)):
                     seed, seed_dev = ops.dropout_seed(p_drop)
                     yt = xt_workspace(pre_pad.device, pre_pad.shape[0], gc.out_features, slot=0)

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import forms, ops
 from .lr import PolynomialDecayLR
 from .model import (FeedForwardNetwork, MultiHeadAttention, hop_table_from, no_grad_row0, fused_layer_forward,
                     refresh_shadows, flush_pending_pack)
@@ -329,7 +329,7 @@ class Graphormer(nn.Module):
         # the table is read at <= G*N rows (:1264): compute only those.  The row gather of the dense adjacency pays below P/2
         # rows; the bitmask-rows form of round 4 (modelGNN._DistGcnFn: 1 KB per row, K-split) up to P rows
         mask_rows = (getattr(self, "D_mask", None) is not None and not self.sparse_adj
-                     and os.environ.get("MOBGT_NO_DIST_GCN_FUSED") != "1")
+                     and forms.on("dist_gcn_fused"))
         rows_only = G * N * 2 <= self.X.shape[0] or (mask_rows and G * N <= min(self.X.shape[0], 4096))
         idx, real = ops.node_index(x, batched_data.time_normal[:, :, 0].float(), self.poi2cat, rows_only,
                                    batched_data.in_degree, batched_data.out_degree)

@@ -21,7 +21,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import forms, ops
 from .model import sync_external_shadows
 from .lr import polynomial_decay_lr
 from .accum import UpdateWindow, check_accum_args, scheduled_lr
@@ -244,18 +244,18 @@ def choose_ddp_form(model, batches, steps=20, warmup=5, candidates=None, **ts_kw
     function exists to make (the one-rank figures of rounds 4-5 cannot show what an overlap hides).  With `accumulate > 1` or
     `clip_norm` among the TrainStep arguments the overlap forms are not candidates (TrainStep does not build them)."""
     import time
-    forms = candidates or [("one_graph", dict(overlap=False), {}),
+    cands = candidates or [("one_graph", dict(overlap=False), {}),
                            ("overlap_2", dict(overlap="force"), {"MOBGT_DDP_PARTS": "1"}),
                            ("overlap_3", dict(overlap="force"), {"MOBGT_DDP_PARTS": "3"})]
     if candidates is None and (ts_kw.get("accumulate", 1) != 1 or ts_kw.get("clip_norm") is not None):
-        forms = forms[:1]
+        cands = cands[:1]
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() <= 1:
-        return forms[0][0], forms[0][1], {}
+        return cands[0][0], cands[0][1], {}
     dev = next(model.parameters()).device
     sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    saved_env = {k: os.environ.get(k) for _, _, env in forms for k in env}
+    saved_env = {k: os.environ.get(k) for _, _, env in cands for k in env}
     timings = {}
-    for name, kw, env in forms:
+    for name, kw, env in cands:
         for k, v in env.items():
             os.environ[k] = v
         try:
@@ -286,7 +286,7 @@ def choose_ddp_form(model, batches, steps=20, warmup=5, candidates=None, **ts_kw
         del ts
     best = min(timings, key=lambda n: (timings[n], n))
     assert_same_across_ranks(best.encode().ljust(16, b" "), "the chosen data-parallel step form", dev)
-    kw, env = next((kw, env) for n, kw, env in forms if n == best)
+    kw, env = next((kw, env) for n, kw, env in cands if n == best)
     return best, dict(kw, _env=env), timings
 
 
@@ -397,7 +397,7 @@ class TrainStep:
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # MOBGT_FORCE_COMM=1 (tests): a process group of ONE rank takes the data-parallel path -- buckets, exchange on the
         # collective's stream, bf16 exchange buffer -- so that the RCCL ("nccl") branch executes on a one-GPU box
-        self.force_comm = (os.environ.get("MOBGT_FORCE_COMM") == "1" and dist.is_available() and dist.is_initialized())
+        self.force_comm = (forms.on("force_comm") and dist.is_available() and dist.is_initialized())
         self.ddp = self.world > 1 or self.force_comm
         # Data parallel, three forms of one step:
         #  * default over RCCL -- `one_graph`: the WHOLE step is one hipGraph per batch: forward, backward, the gradient
@@ -411,7 +411,7 @@ class TrainStep:
         #    of the flat buffer all-reduced asynchronously on RCCL's stream beside the next replay;
         #  * gloo (host collectives are not capturable) or MOBGT_DDP_HOST_EXCHANGE=1: forward + backward graph, all-reduce
         #    issued by the host, optimizer graph.
-        want_overlap = overlap == "force" or (bool(overlap) and os.environ.get("MOBGT_DDP_OVERLAP") == "1")
+        want_overlap = overlap == "force" or (bool(overlap) and forms.on("ddp_overlap"))
         self.overlap = bool(want_overlap and use_graph and (self.ddp or overlap == "force") and self.n_head > 0
                             and hasattr(model, "_enc_out"))
         if self.overlap and self._accum:
@@ -421,7 +421,7 @@ class TrainStep:
         self._loss_slots_nocomm = {}
         self._plan_buckets()
         self.one_graph = bool(self.ddp and use_graph and not self.overlap and dist.get_backend() == "nccl"
-                              and os.environ.get("MOBGT_DDP_HOST_EXCHANGE") != "1")
+                              and not forms.on("ddp_host_exchange"))
         self.graphs_nocomm = {}
         self.comm = True        # False: skip the gradient exchange (bench.py measures the exposed all-reduce time that way)
         self._prepared = False
@@ -1025,7 +1025,7 @@ class TrainStep:
 
     # ---- peer waits that gave up (csrc/chain.hip WS_FAULT, head.hip, smallgcn.hip): detection and recovery ---------------
     def recapture(self):
-        """Capture every step graph again (after ops.SAFE_FORMS changed which kernels a step launches).  Parameters,
+        """Capture every step graph again (after forms "safe_forms" changed which kernels a step launches).  Parameters,
         optimizer state and the step counter are left as they are."""
         if not (self.use_graph and self._prepared):
             return
@@ -1058,7 +1058,7 @@ class TrainStep:
     def guarded_step(self, i):
         """step(i) with the promise that no peer-wait fault goes unnoticed: state snapshot -> step -> device sync + fault check;
         on a fault the snapshot is restored, every launch switches to its form WITHOUT cross-workgroup waits
-        (ops.SAFE_FORMS: one workgroup per row block, the head as three launches, the GCN layer by layer), the graphs are
+        (forms "safe_forms": one workgroup per row block, the head as three launches, the GCN layer by layer), the graphs are
         captured again and the step is re-run with the same dropout counter.  Costs three buffer copies and a host
         synchronisation per step: meant for runs that share the device with other streams' persistent kernels."""
         with torch.no_grad():
@@ -1082,7 +1082,7 @@ class TrainStep:
         self.sched_state = sched
         self.window.restore(win)
         self._set_lr()
-        ops.SAFE_FORMS[0] = True
+        forms.set("safe_forms", True)
         ops.set_peer_wait_limit(0, 0)
         self.recapture()
         self.faults_recovered = getattr(self, "faults_recovered", 0) + 1
@@ -1402,7 +1402,7 @@ class EvalLoop(_StagedBatches):
       length: which rows share a batch decides where get_acc's stop at the first target 0 applies;
     * shapes and staging: EpochLoop's buckets (one static batch per (G, bucket)), pinned buffers, device collate on the copy
       stream, host index checks; trajectories over `collator.max_node` are dropped;
-    * per (G, bucket, ops.SAFE_FORMS[0]) ONE captured graph = eval forward + the fused classifier-ranking launches
+    * per (G, bucket, forms.on("safe_forms")) ONE captured graph = eval forward + the fused classifier-ranking launches
       (Graphormer.metric_step) adding into ONE f64 accumulator; `use_graph=False` runs the same launches eagerly, and so do
       collators whose finish needs torch ops (coordinate bins, S-BIG: see _launch);
     * `run()` reads the accumulator once (after one all-reduce of all its doubles when world > 1: every rank's samples pooled).
@@ -1492,7 +1492,7 @@ class EvalLoop(_StagedBatches):
             # pass ran (fw_kernel: 75 ms per call, rocprofv3).  Why it gives up only there is not known.
             self._forward(slot["batch"], self.acc)
             return
-        key = (slot["layout"].G, slot["layout"].N, bool(ops.SAFE_FORMS[0]))
+        key = (slot["layout"].G, slot["layout"].N, forms.on("safe_forms"))
         g = self.graphs.get(key)
         if g is None:
             self.stream.wait_stream(cur)
@@ -1582,7 +1582,7 @@ class EvalLoop(_StagedBatches):
 
 class PredictLoop(EvalLoop):
     """Top-k next-POI recommendations over a whole split (Graphormer.recommend_step) on EvalLoop's device data path: the eval
-    loader's order and sharding, EpochLoop's buckets and staging, one captured graph per (G, bucket, ops.SAFE_FORMS[0]) -- eager
+    loader's order and sharding, EpochLoop's buckets and staging, one captured graph per (G, bucket, forms.on("safe_forms")) -- eager
     for collators whose finish needs torch ops (S-BIG) -- and the weights as they are when run() starts.
 
     A graph writes its batch's [G, k] ids / vals into buffers of its own (fixed pointers); a device-to-device copy on the same

@@ -444,7 +444,7 @@ def test_guarded_step_rerun_counts_the_micro_step_once(monkeypatch):
     """A fault report (simulated: ops.peer_wait_faults patched to return one, once) on the micro-step that ends a window:
     guarded_step restores parameters, moments, accumulator, window position and update counter, re-captures and re-runs -- the
     counters read what an undisturbed run reads and the update moved the parameters once."""
-    from mobgt_amd import ops, workloads
+    from mobgt_amd import forms, ops, workloads
     from mobgt_amd.train import TrainStep
     runs = {}
     try:
@@ -473,10 +473,10 @@ def test_guarded_step_rerun_counts_the_micro_step_once(monkeypatch):
             monkeypatch.setattr(ops, "peer_wait_faults", real)
             assert getattr(ts, "faults_recovered", 0) == (1 if tag == "faulted" else 0)
             runs[tag] = (trace, (ts.flat_params.tensor.detach() - p0).double(), ts.acc.clone(), float(ts.grad_norm))
-            ops.SAFE_FORMS[0] = False
+            forms.set("safe_forms", None)
             ops.set_peer_wait_limit(0)
     finally:
-        ops.SAFE_FORMS[0] = False
+        forms.set("safe_forms", None)
         ops.set_peer_wait_limit(0)
     (ta, da, acca, na), (tb, db, accb, nb) = runs["undisturbed"], runs["faulted"]
     print("counters", ta, tb, "norms", na, nb)

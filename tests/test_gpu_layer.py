@@ -382,7 +382,7 @@ def test_ln_prologue_gemms_match_the_two_launch_form(variant):
     """csrc/lngemm.hip: dropout_add_ln as the prologue of the GEMM that consumes it (FFN layer 1 forward, the GELU'
     GEMM and the output-projection data gradient backward) against the separate launches -- same arithmetic and the
     same dropout masks, so outputs and every gradient agree to bf16 round-off (the row reductions run in another order)."""
-    from mobgt_amd import fused_layer
+    from mobgt_amd import forms
     from mobgt_amd.model import EncoderLayer as StockLayer
     from mobgt_amd.model_fqandtoyo import EncoderLayer as FqLayer
     torch.manual_seed(3)
@@ -397,9 +397,7 @@ def test_ln_prologue_gemms_match_the_two_launch_form(variant):
     gy = torch.randn(G, T, C, device=DEV)
     res = {}
     for on in (True, False):
-        fused_layer._LN_GEMM[0] = on
-        fused_layer._LN_GEMM_BWD[0] = on
-        try:
+        with forms.using(ln_gemm=on, ln_gemm_bwd=on):
             for p in layer.parameters():
                 p.grad = None
             x = x0.clone().requires_grad_(True)
@@ -407,9 +405,6 @@ def test_ln_prologue_gemms_match_the_two_launch_form(variant):
             y.backward(gy)
             torch.cuda.synchronize()
             res[on] = (y.detach().clone(), x.grad.clone(), {n: p.grad.clone() for n, p in layer.named_parameters() if p.grad is not None})
-        finally:
-            fused_layer._LN_GEMM[0] = True
-            fused_layer._LN_GEMM_BWD[0] = False
     (ya, dxa, ga), (yb, dxb, gb) = res[True], res[False]
 
     def close(a, b, name):
@@ -497,7 +492,7 @@ def test_layer_chain_kernel_matches_the_separate_launches(C, G, T, p):
     """csrc/chain.hip: out-proj -> LN -> FFN -> LN -> the NEXT layer's QKV projection as one launch per layer, against the
     separate launches (MOBGT_NO_CHAIN path) on a 3-layer fq stack: same rounding points, same dropout masks, so outputs
     and every gradient agree to bf16 round-off (full-K accumulation here, split-K there)."""
-    from mobgt_amd import fused_layer
+    from mobgt_amd import forms
     from mobgt_amd.model import refresh_shadows
     from mobgt_amd.model_fqandtoyo import EncoderLayer as FqLayer
     torch.manual_seed(5)
@@ -513,9 +508,7 @@ def test_layer_chain_kernel_matches_the_separate_launches(C, G, T, p):
     gy = torch.randn(G, T, C, device=DEV)
     res = {}
     for mode in ("both", "forward", "off"):                # chain kernels forward + backward / forward only / neither
-        fused_layer._CHAIN[0] = mode != "off"
-        fused_layer._CHAIN_BWD[0] = mode == "both"
-        try:
+        with forms.using(chain=mode != "off", chain_bwd=mode == "both"):
             for q in layers.parameters():
                 q.grad = None
             x = x0.clone().requires_grad_(True)
@@ -530,8 +523,6 @@ def test_layer_chain_kernel_matches_the_separate_launches(C, G, T, p):
             y.backward(gy)
             torch.cuda.synchronize()
             res[mode] = (y.detach().clone(), x.grad.clone(), {n: q.grad.clone() for n, q in layers.named_parameters() if q.grad is not None})
-        finally:
-            fused_layer._CHAIN[0] = fused_layer._CHAIN_BWD[0] = True
 
     def close(a, b, name):
         scale = float(b.abs().max()) + 1e-12
@@ -557,7 +548,7 @@ def test_long_batch_forward_chain_matches_the_library_launches(C, G, T, p):
     tile).  Against MOBGT_NO_CHAIN_BIG=1 (library GEMMs + csrc/layer.hip glue) on a 3-layer fq stack: same
     rounding points, same dropout masks -- outputs, input gradient and every parameter gradient to bf16 round-off.  The
     last row block is full in the first case (4 480 = 70 x 64) and ragged in the others (4 500, 4 710, 4 411 rows)."""
-    from mobgt_amd import fused_layer
+    from mobgt_amd import forms
     from mobgt_amd.model import refresh_shadows
     from mobgt_amd.model_fqandtoyo import EncoderLayer as FqLayer
     torch.manual_seed(6)
@@ -573,8 +564,7 @@ def test_long_batch_forward_chain_matches_the_library_launches(C, G, T, p):
     gy = torch.randn(G, T, C, device=DEV)
     res = {}
     for mode in ("big", "off"):
-        fused_layer._CHAIN_BIG[0] = mode == "big"
-        try:
+        with forms.using(chain_big=mode == "big"):
             for q in layers.parameters():
                 q.grad = None
             x = x0.clone().requires_grad_(True)
@@ -589,8 +579,6 @@ def test_long_batch_forward_chain_matches_the_library_launches(C, G, T, p):
             y.backward(gy)
             torch.cuda.synchronize()
             res[mode] = (y.detach().clone(), x.grad.clone(), {n: q.grad.clone() for n, q in layers.named_parameters() if q.grad is not None})
-        finally:
-            fused_layer._CHAIN_BIG[0] = True
 
     def close(a, b, name):
         scale = float(b.abs().max()) + 1e-12
@@ -1226,7 +1214,7 @@ def test_preln_layer_chain_kernel_matches_the_separate_launches(C, G, T, p):
     (MOBGT_NO_CHAIN path: 7 + 7 launches per layer) on a 3-layer stock stack with dropout on: same rounding points, same
     masks, so outputs and every gradient agree to bf16 round-off.  Both cluster sizes and the one-workgroup form (R = 608 ->
     4 members, 390 -> 4, 17 -> 4, 1170 -> 2)."""
-    from mobgt_amd import fused_layer
+    from mobgt_amd import forms
     from mobgt_amd.model import EncoderLayer as StockLayer, refresh_shadows
     torch.manual_seed(5)
     H = 8
@@ -1245,8 +1233,7 @@ def test_preln_layer_chain_kernel_matches_the_separate_launches(C, G, T, p):
     gy = torch.randn(G, T, C, device=DEV)
     res = {}
     for mode in ("chain", "off"):
-        fused_layer._CHAIN[0] = mode != "off"
-        try:
+        with forms.using(chain=mode != "off"):
             for q in layers.parameters():
                 q.grad = None
             x = x0.clone().requires_grad_(True)
@@ -1261,8 +1248,6 @@ def test_preln_layer_chain_kernel_matches_the_separate_launches(C, G, T, p):
             y.backward(gy)
             torch.cuda.synchronize()
             res[mode] = (y.detach().clone(), x.grad.clone(), {n: q.grad.clone() for n, q in layers.named_parameters() if q.grad is not None})
-        finally:
-            fused_layer._CHAIN[0] = True
 
     def close(a, b, name):
         scale = float(b.abs().max()) + 1e-12

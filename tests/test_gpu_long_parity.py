@@ -268,17 +268,16 @@ def test_long_batch_train_step_vs_oracle_with_replayed_masks(monkeypatch):
 
 def test_long_batch_step_forms_agree():
     """The two round-6 forms of the long-batch step against the forms they replaced, on the same model and batch (dropout off, so
-    nothing but the summation order differs): the layer's weight gradients as ONE launch (csrc/wgradbig.hip; fused_layer._WGRAD_BIG off:
+    nothing but the summation order differs): the layer's weight gradients as ONE launch (csrc/wgradbig.hip; forms "wgrad_big" off:
     library split-K products + `wgrad_group` + parked partial sums) and the bias tables' backward on the side stream beside the
-    tail of the backward pass (ops._bias_bwd_beside; ops._BIAS_BWD_BESIDE off: where autograd reaches it).  One captured
+    tail of the backward pass (ops._bias_bwd_beside; forms "bias_bwd_beside" off: where autograd reaches it).  One captured
     `TrainStep` each; every parameter gradient of the model."""
     import gc
-    from mobgt_amd import fused_layer
+    from mobgt_amd import forms
     from mobgt_amd.train import TrainStep
     grads, losses = {}, {}
     for mode in ("round6", "before"):
-        fused_layer._WGRAD_BIG[0] = ops._BIAS_BWD_BESIDE[0] = mode == "round6"
-        try:
+        with forms.using(wgrad_big=mode == "round6", bias_bwd_beside=mode == "round6"):
             uni, model, batch = _build(192, dropout_rate=0.0, intput_dropout_rate=0.0, attention_dropout_rate=0.0)
             sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
             ts = TrainStep(model, [batch], use_graph=True, seed=5)
@@ -292,8 +291,6 @@ def test_long_batch_step_forms_agree():
             grads[mode] = {n: q.grad.detach().float().clone() for n, q in model.named_parameters() if q.grad is not None}
             del ts, model, batch, uni
             gc.collect()
-        finally:
-            fused_layer._WGRAD_BIG[0] = ops._BIAS_BWD_BESIDE[0] = True
     assert losses["round6"] == pytest.approx(losses["before"], rel=1e-5)
     a, b = grads["round6"], grads["before"]
     assert a.keys() == b.keys() and len(a) > 60

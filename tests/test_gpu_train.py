@@ -295,8 +295,9 @@ def test_bench_launches_two_ranks_and_reports_them(tmp_path):
 def test_encoder_input_backward_as_one_launch_equals_the_three_launches(monkeypatch):
     """csrc/tokbwd.hip (assemble_tokens' backward + the data gradients of FuseEmbeddings-4 / -2, parked across three autograd
     nodes and run as ONE launch inside the trainer's backward) against the three launches (MOBGT_NO_TOKEN_BWD_CHAIN=1): every
-    parameter gradient of one dropout-on S-FSQ batch, same masks; f32 products in another summation order."""
-    from mobgt_amd import ops, workloads
+    parameter gradient of one dropout-on S-FSQ batch, same masks; f32 products in another summation order.  The first pass
+    takes the one launch (mobgt_token_bwd_chain is called once), the second never."""
+    from mobgt_amd import _lib, ops, workloads
     uni, model, coll = workloads.build("fsq", "cuda", seed=1, model_overrides=dict(n_layers=2))
     batch = coll(workloads.make_pool("fsq", 1, 16, uni)[0])
     model.train()
@@ -306,9 +307,19 @@ def test_encoder_input_backward_as_one_launch_equals_the_three_launches(monkeypa
         if hasattr(m, "seed_dev"):
             m.seed_dev = sd
     res = []
+    launches = []
+    real = _lib.lib()
+
+    class _Spy:
+        def __getattr__(self, name):
+            if name == "mobgt_token_bwd_chain":
+                launches.append(name)
+            return getattr(real, name)
+    monkeypatch.setattr(_lib, "lib", lambda: _Spy())
     try:
         for off in ("0", "1"):
             monkeypatch.setenv("MOBGT_NO_TOKEN_BWD_CHAIN", off)
+            del launches[:]
             for p in model.parameters():
                 p.grad = None
             ops.wgrad_deferral(True)
@@ -323,6 +334,8 @@ def test_encoder_input_backward_as_one_launch_equals_the_three_launches(monkeypa
             torch.cuda.synchronize()
             res.append({n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None})
             assert parked_before == 0
+            print("MOBGT_NO_TOKEN_BWD_CHAIN=%s: %d mobgt_token_bwd_chain launch(es)" % (off, len(launches)))
+            assert len(launches) == (1 if off == "0" else 0), (off, launches)
     finally:
         ops.set_dropout_state(None, 0)
     a, b = res
@@ -643,13 +656,13 @@ def test_step_graph_beside_another_streams_persistent_kernel_never_gives_up():
     64 (then 150) workgroups that hold compute units on a second stream (mobgt_debug_occupy) while the S-FSQ step graph replays
     2 000 times.  No workgroup may give up (they used to trap), and a step taken from a fixed state beside the occupier must
     produce the gradients of the undisturbed step."""
-    from mobgt_amd import _lib, ops, workloads
+    from mobgt_amd import _lib, forms, ops, workloads
     from mobgt_amd.train import TrainStep
     uni, model, coll = workloads.build("fsq", DEV, seed=1)
     batches = [coll(t) for t in workloads.make_pool("fsq", 2, 16, uni)]
     ts = TrainStep(model, batches, use_graph=True, seed=1)
     ts.prepare()
-    assert not ops.SAFE_FORMS[0]
+    assert not forms.on("safe_forms")
     ops.peer_wait_faults(reset=True)
     state = _state_of(ts)
     g_ref, loss_ref = _fixed_step_grads(ts, state)
@@ -685,9 +698,9 @@ def test_step_graph_beside_another_streams_persistent_kernel_never_gives_up():
 
 def test_injected_peer_wait_fault_is_detected_and_the_step_rerun_in_the_safe_forms():
     """A peer wait that gives up sets a fault word instead of trapping; `TrainStep.guarded_step` finds it, restores the
-    snapshot, switches every launch to its form without cross-workgroup waits (ops.SAFE_FORMS), captures the graphs again and
+    snapshot, switches every launch to its form without cross-workgroup waits (forms "safe_forms"), captures the graphs again and
     re-runs the step.  Fault injection: limit word 0xffffffff makes every cluster wait report a fault and leave at once."""
-    from mobgt_amd import ops, workloads
+    from mobgt_amd import forms, ops, workloads
     from mobgt_amd.train import TrainStep
     uni, model, coll = workloads.build("fsq", DEV, seed=1, model_overrides=dict(n_layers=2))
     batches = [coll(t) for t in workloads.make_pool("fsq", 1, 16, uni)]
@@ -710,7 +723,7 @@ def test_injected_peer_wait_fault_is_detected_and_the_step_rerun_in_the_safe_for
             ts.sync_shadows()
         loss = float(ts.guarded_step(0))
         torch.cuda.synchronize()
-        assert ts.faults_recovered == 1 and ops.SAFE_FORMS[0]
+        assert ts.faults_recovered == 1 and forms.on("safe_forms")
         assert ops.peer_wait_faults() == {}
         g = ts.flat.flat.detach()
         rel = float((g - g_ref).norm() / g_ref.norm())
@@ -721,7 +734,7 @@ def test_injected_peer_wait_fault_is_detected_and_the_step_rerun_in_the_safe_for
         assert dp <= 2.5 * float(ts.lr)             # one AdamW step from the snapshot, as in the undisturbed run
         assert int(ts.seed_dev.item()) == int(state[3].item()) + 1
     finally:
-        ops.SAFE_FORMS[0] = False
+        forms.set("safe_forms", None)
         ops.set_peer_wait_limit(0)
 
 

@@ -22,13 +22,20 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from mobgt_amd import ops, workloads                                     # noqa: E402
+from mobgt_amd import forms, ops, workloads                              # noqa: E402
 from oracle import model_oracle as mo                                     # noqa: E402
 from gradcheck import assert_replay_bounded, device_head_pattern, n_flipped, replay_head                  # noqa: E402
 from test_gpu_bench_parity import GRAD_PARAMS, LOSS_SCALE, bad_rows, check_grad, cpu_batch, oracle_consts   # noqa: E402,F401
 
 DEV = "cuda"
 M64 = (1 << 64) - 1
+
+
+@pytest.fixture
+def set_form():
+    """forms.set for the length of one test."""
+    with forms.using():
+        yield forms.set
 
 
 def _inv_keep(p):
@@ -56,15 +63,14 @@ def layer_masks(prefix, mha, step, G, T, C, H, p, p_att):
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16_launches", "bf16_lngemm_bwd", "bf16_chain"])
-def test_fq_layer_with_dropout_on_vs_oracle_with_replayed_masks(mode, monkeypatch):
+def test_fq_layer_with_dropout_on_vs_oracle_with_replayed_masks(mode, set_form):
     """(bf16_lngemm_bwd: the opt-in MOBGT_LN_GEMM_BWD=1 form, LayerNorm' / dropout' as the prologue of the backward GEMMs)"""
-    from mobgt_amd import fused_layer
     from mobgt_amd.model import refresh_shadows
     from mobgt_amd.model_fqandtoyo import EncoderLayer
     G, H, T, C, F, p, p_att = 4, 8, 53, 192, 1024, 0.1, 0.1
-    monkeypatch.setattr(fused_layer, "_CHAIN", [mode == "bf16_chain"])
-    monkeypatch.setattr(fused_layer, "_CHAIN_BWD", [mode == "bf16_chain"])
-    monkeypatch.setattr(fused_layer, "_LN_GEMM_BWD", [mode == "bf16_lngemm_bwd"])
+    set_form("chain", mode == "bf16_chain")
+    set_form("chain_bwd", mode == "bf16_chain")
+    set_form("ln_gemm_bwd", mode == "bf16_lngemm_bwd")
     torch.manual_seed(0)
     layer = EncoderLayer(C, F, p, p_att, H)
     layer.self_attention.set_layer_index(1)       # (stand-alone layers count process-wide: pin it, so that the masks -- and with
@@ -130,15 +136,14 @@ def test_fq_layer_with_dropout_on_vs_oracle_with_replayed_masks(mode, monkeypatc
 
 
 @pytest.mark.parametrize("mode", ["bf16_launches", "bf16_chain"])
-def test_stock_two_layer_stack_with_dropout_on_vs_oracle_with_replayed_masks(mode, monkeypatch):
+def test_stock_two_layer_stack_with_dropout_on_vs_oracle_with_replayed_masks(mode, set_form):
     """graphormer/model.py:463-489 -- the pre-LN EncoderLayer north_star names -- twice in a row (C 128, d 16, ffn 1024, 8 heads),
     dropout ON, against oracle.encoder_layer_stock with the device's masks replayed: as separate launches and as the round-4
     chain kernels (layer 0's launch applies layer 1's self_attention_norm and QKV projection; layer 1's norm backward is
     finished in layer 0's backward launch).  Outputs, dx, dbias and EVERY parameter gradient of both layers."""
-    from mobgt_amd import fused_layer
     from mobgt_amd.model import EncoderLayer, refresh_shadows
     G, H, T, C, F, p, p_att = 4, 8, 53, 128, 1024, 0.1, 0.1
-    monkeypatch.setattr(fused_layer, "_CHAIN", [mode == "bf16_chain"])
+    set_form("chain", mode == "bf16_chain")
     torch.manual_seed(0)
     layers = torch.nn.ModuleList([EncoderLayer(C, F, p, p_att, H) for _ in range(2)])
     for li, layer in enumerate(layers):

@@ -3,11 +3,11 @@ hipGraph and eager: profiles/r6_backward_run_to_run.txt.  Dropout off, same mode
 import os, sys, gc
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 import torch
-from mobgt_amd import fused_layer, ops
+from mobgt_amd import forms
 from mobgt_amd.train import TrainStep
 from test_gpu_long_parity import _build
 def run(w, b, graph=True):
-    fused_layer._WGRAD_BIG[0], ops._BIAS_BWD_BESIDE[0] = w, b
+    forms.set("wgrad_big", w); forms.set("bias_bwd_beside", b)
     uni, model, batch = _build(192, dropout_rate=0.0, intput_dropout_rate=0.0, attention_dropout_rate=0.0)
     ts = TrainStep(model, [batch], use_graph=graph, seed=5)
     ts.prepare(); loss = float(ts.step(0)); torch.cuda.synchronize()

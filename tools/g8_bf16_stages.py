@@ -98,17 +98,16 @@ for name in ("f32", "bf16"):
     m.load_state_dict(sd, strict=True)
     m = m.cuda().eval()
     b = DeviceCollator("cuda", bin_table=table)(real_trajs(z, "a"))
-    from mobgt_amd import fused_layer
-    fused_layer._CHAIN[0] = False              # separate launches: every intermediate is materialised
+    from mobgt_amd import forms
     from mobgt_amd.model import refresh_shadows
     pack = m.assemble_bias(b)
     x0 = stages["f32"]["tokens x0"].cuda().requires_grad_(True)       # the SAME input for both
-    refresh_shadows(m.layers)
-    out = m.layers[0](x0, pack)
+    with forms.using(chain=False):             # separate launches: every intermediate is materialised
+        refresh_shadows(m.layers)
+        out = m.layers[0](x0, pack)
     names = ("x", "xa", "qkv", "a", "lse", "x1", "z", "u", "h", "x2")
     saved[name] = {k: (None if t is None else t.detach().float().cpu()) for k, t in zip(names, out.grad_fn.saved_tensors)}
     saved[name]["out"] = out.detach().float().cpu()
-    fused_layer._CHAIN[0] = True
 for k, w in saved["f32"].items():
     v = saved["bf16"].get(k)
     if w is None or v is None or k == "lse" or v.shape != w.shape:
