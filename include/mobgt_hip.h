@@ -370,6 +370,14 @@ int64_t mobgt_rank_metrics_masked_work_bytes(int64_t G, int64_t V);
 int mobgt_rank_metrics_masked(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
                               const uint32_t* allow, const void* hist, int hist_dtype, int64_t ld_hist, int64_t n_hist_cols,
                               int64_t hist_offset, int flags, double* acc, void* work, void* stream);
+/* mobgt_rank_metrics_masked with allow words per row (a radius around each row's anchor, mobgt_near_words): allow is
+ * [G, ld_allow] words, ld_allow >= ceil(V / 32), and row g's candidates and its target's reachability are read from
+ * allow + g * ld_allow -- a target outside its row's allow bits is unreachable and counts in n only.  ld_allow == 0 (or allow
+ * NULL) is mobgt_rank_metrics_masked exactly; 0 < ld_allow < ceil(V / 32) is MOBGT_EBADDIM.  Everything else -- `work`, the two
+ * graph-capturable launches, flags, the tie rules, the slots -- is the sibling's. */
+int mobgt_rank_metrics_masked_rows(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
+                                   const uint32_t* allow, int64_t ld_allow, const void* hist, int hist_dtype, int64_t ld_hist,
+                                   int64_t n_hist_cols, int64_t hist_offset, int flags, double* acc, void* work, void* stream);
 /* Row-wise top-k of stored scores: the ranked next-POI list (Graphormer.recommend_step, train.PredictLoop), replacing the
  * torch.topk a caller ran on test_step's y_pred (:1530-1544) by hand.  scores [G, V] f32 with row stride ld >= V (elements);
  * 1 <= k <= 64, k <= V, G <= 65535, else MOBGT_EBADDIM.  Writes ids [G, k] int64 = column + col_offset and vals [G, k] f32 equal to
@@ -393,6 +401,32 @@ int mobgt_topk_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64
 int mobgt_topk_rows_masked(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset, const uint32_t* allow,
                            const void* excl, int excl_dtype, int64_t ld_excl, int64_t n_excl_cols, int64_t excl_offset, int64_t* ids,
                            float* vals, void* work, void* stream);
+/* mobgt_topk_rows_masked with allow words per row: allow is [G, ld_allow] words, ld_allow >= ceil(V / 32), and row g reads
+ * allow + g * ld_allow.  ld_allow == 0 (or allow NULL) is mobgt_topk_rows_masked exactly; 0 < ld_allow < ceil(V / 32) is
+ * MOBGT_EBADDIM.  `work`, the launches, the order and the -1 / -inf filler are the sibling's. */
+int mobgt_topk_rows_masked_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset,
+                                const uint32_t* allow, int64_t ld_allow, const void* excl, int excl_dtype, int64_t ld_excl,
+                                int64_t n_excl_cols, int64_t excl_offset, int64_t* ids, float* vals, void* work, void* stream);
+/* Per-row allow words from coordinates: the POIs within a radius of where a row's user is (within_km= of train.PredictLoop /
+ * train.EvalLoop).  pos is [V, 4] f32 in column space, 16-byte rows: x, y, z the unit vector of the column's POI, w unused (0);
+ * a column with no POI (the pad id, ids beyond the table) holds x = y = z = +inf.  hist is [G, ld_hist] ids (ld_hist >=
+ * n_hist_cols) of dtype hist_dtype (MOBGT_I64 / MOBGT_I32) with the masked kernels' meaning: 0 is padding, id - hist_offset is
+ * a column, ids mapping outside [0, V) are skipped.  The row's anchors are, by mode, its last such id (MOBGT_NEAR_LAST) or every
+ * one of them (MOBGT_NEAR_ANY).  Column c of row g is near when some anchor a of the row satisfies, in f32 with every operation
+ * rounded on its own (no FMA) and in exactly this order,
+ *     dx = pos[c].x - pos[a].x  (dy, dz alike);   ((dx*dx) + (dy*dy)) + (dz*dz) <= chord2_max
+ * -- the squared chord between unit vectors, (2 sin(d / 2R))^2 for a great-circle distance d.  inf and NaN compare false: a
+ * column without a POI is never near, a row without a valid anchor has no candidates.  words[g * ld_words + w] (ld_words >=
+ * ceil(V / 32)) receives bit c & 31 for column c = 32 w + (c & 31), ANDed with allow_and[w] when allow_and is not NULL (a shared
+ * candidate set); bits of columns >= V are 0; every word of [0, ceil(V / 32)) of every row is written and no other, so the
+ * buffer needs no clearing (n_hist_cols == 0, where hist may be NULL: zeros).  One graph-capturable launch, plain stores, no
+ * state between calls.  G <= 65535; bad sizes or mode: MOBGT_EBADDIM; a bad hist_dtype: MOBGT_EDTYPE; pos not 16-byte aligned:
+ * MOBGT_EALIGN. */
+#define MOBGT_NEAR_LAST 0
+#define MOBGT_NEAR_ANY 1
+int mobgt_near_words(const float* pos, int64_t V, const void* hist, int hist_dtype, int64_t ld_hist, int64_t n_hist_cols,
+                     int64_t hist_offset, int mode, float chord2_max, const uint32_t* allow_and, uint32_t* words, int64_t ld_words,
+                     int64_t G, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused elementwise / normalisation pieces of EncoderLayer.forward between the library GEMMs

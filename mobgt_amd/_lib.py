@@ -84,9 +84,12 @@ SIGNATURES = {
     "mobgt_skinny_linear_rank_metrics": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "mobgt_rank_metrics_masked_work_bytes": (_i64, [_i64, _i64]),
     "mobgt_rank_metrics_masked": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
+    "mobgt_rank_metrics_masked_rows": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
     "mobgt_topk_work_bytes": (_i64, [_i64, _i64, _i64]),
     "mobgt_topk_rows": (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mobgt_topk_rows_masked": (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mobgt_topk_rows_masked_rows": (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mobgt_near_words": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i64, _i, _f, _vp, _vp, _i64, _i64, _vp]),
     "mobgt_skinny_linear_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mobgt_skinny_linear_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mobgt_skinny_linear_dx": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

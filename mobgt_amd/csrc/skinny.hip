@@ -759,6 +759,7 @@ constexpr int RM_FIELDS = 11;
 // its bits are built, so the two memory round trips overlap.  Whether the target itself is a candidate is the finish's business.
 constexpr int RMM_PER_T = RM_CHUNK / 256;
 
+template <bool ROWS>
 __global__ __launch_bounds__(256) void rank_counts_masked_kernel(const float* __restrict__ scores, const int64_t* __restrict__ target,
                                                                  int64_t target_offset, int32_t* __restrict__ slab, int G, int64_t V,
                                                                  int64_t per, CandMask m) {
@@ -779,7 +780,7 @@ __global__ __launch_bounds__(256) void rank_counts_masked_kernel(const float* __
                 const int64_t c = b0 + threadIdx.x + i * 256;
                 v[i] = c < c1 ? s[c] : 0.f;
             }
-            cand_bits<RM_CHUNK / 32, 256>(s_ok, m, g, b0, V);
+            cand_bits<RM_CHUNK / 32, 256, ROWS>(s_ok, m, g, b0, V);
 #pragma unroll
             for (int i = 0; i < RMM_PER_T; ++i) {
                 const int r = threadIdx.x + i * 256;
@@ -836,6 +837,7 @@ __device__ __forceinline__ void rm_store(double* __restrict__ acc, const RmSlot&
 // rank_finish_kernel's walk with the target's reachability (in [0, V), allowed, not excluded) and its membership in the row's
 // hist ids (MOBGT_RM_SPLIT's slot 1 / 2) decided here, 16 lanes per row over the hist list while the slab sums load.  The
 // order of the f64 sums is rank_finish_kernel's, so an unrestricted slot 0 is mobgt_rank_metrics' acc bit for bit.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void rank_finish_masked_kernel(const int32_t* __restrict__ slab, int nb, const int64_t* __restrict__ target,
                                                                  int64_t target_offset, int G, int64_t V, CandMask m, int flags,
                                                                  double* __restrict__ acc) {
@@ -876,7 +878,7 @@ __global__ __launch_bounds__(256) void rank_finish_masked_kernel(const int32_t* 
 #pragma unroll
             for (int k = 0; k < 3; ++k) s_c[r][k] = c[k];
             in_hist &= ok;                            // (ids outside [0, V) are ignored)
-            const bool allowed = ok && (!m.allow || ((m.allow[t >> 5] >> (t & 31)) & 1u));
+            const bool allowed = ok && (!m.allow || ((cand_allow_row<ROWS>(m, g)[t >> 5] >> (t & 31)) & 1u));
             s_t[r] = t;
             s_f[r] = (allowed && !(excl && in_hist) ? 1 : 0) | (in_hist ? 2 : 0);
         }
@@ -940,28 +942,45 @@ extern "C" int64_t mobgt_rank_metrics_masked_work_bytes(int64_t G, int64_t V) {
     return 12 * (int64_t)rm_blocks(V) * G;
 }
 
-extern "C" int mobgt_rank_metrics_masked(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
-                                         const uint32_t* allow, const void* hist, int hist_dtype, int64_t ld_hist, int64_t n_hist_cols,
-                                         int64_t hist_offset, int flags, double* acc, void* work, void* stream) {
+extern "C" int mobgt_rank_metrics_masked_rows(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
+                                              const uint32_t* allow, int64_t ld_allow, const void* hist, int hist_dtype,
+                                              int64_t ld_hist, int64_t n_hist_cols, int64_t hist_offset, int flags, double* acc,
+                                              void* work, void* stream) {
     if (G <= 0 || V <= 0 || G > 65535 || V > (int64_t)INT32_MAX) return MOBGT_EBADDIM;
     if (!scores || !target || !acc || !work) return MOBGT_EBADDIM;
     if (flags & ~(MOBGT_RM_EXCLUDE_HIST | MOBGT_RM_SPLIT)) return MOBGT_EBADDIM;
     if (hist && (n_hist_cols < 0 || ld_hist < n_hist_cols)) return MOBGT_EBADDIM;
     if (hist && hist_dtype != MOBGT_I64 && hist_dtype != MOBGT_I32) return MOBGT_EDTYPE;
+    if (ld_allow < 0 || (allow && ld_allow > 0 && ld_allow < (V + 31) / 32)) return MOBGT_EBADDIM;
+    if (!allow) ld_allow = 0;
     const bool use_hist = hist && n_hist_cols > 0;
     const bool i64 = hist_dtype == MOBGT_I64;
     // the counts drop the hist ids only to exclude them; the finish reads them to exclude or to split
-    const CandMask mc{allow, use_hist && (flags & MOBGT_RM_EXCLUDE_HIST) ? hist : nullptr, ld_hist, n_hist_cols, hist_offset, i64};
-    const CandMask mf{allow, use_hist && flags ? hist : nullptr, ld_hist, n_hist_cols, hist_offset, i64};
+    const CandMask mc{allow, use_hist && (flags & MOBGT_RM_EXCLUDE_HIST) ? hist : nullptr, ld_hist, n_hist_cols, hist_offset, i64, ld_allow};
+    const CandMask mf{allow, use_hist && flags ? hist : nullptr, ld_hist, n_hist_cols, hist_offset, i64, ld_allow};
     hipStream_t st = (hipStream_t)stream;
     int32_t* slab = reinterpret_cast<int32_t*>(work);
     const int nb = rm_blocks(V);
     const int64_t per = ((V + nb - 1) / nb + 31) / 32 * 32;     // (sub-ranges start on an allow word)
-    hipLaunchKernelGGL(rank_counts_masked_kernel, dim3(nb, (unsigned)G), dim3(256), 0, st, scores, target, target_offset, slab, (int)G,
-                       V, per, mc);
-    hipLaunchKernelGGL(rank_finish_masked_kernel, dim3(1), dim3(256), 0, st, (const int32_t*)slab, nb, target, target_offset, (int)G, V,
-                       mf, flags, acc);
+    if (ld_allow > 0) {                                         // (allow words per row)
+        hipLaunchKernelGGL(rank_counts_masked_kernel<true>, dim3(nb, (unsigned)G), dim3(256), 0, st, scores, target, target_offset, slab,
+                           (int)G, V, per, mc);
+        hipLaunchKernelGGL(rank_finish_masked_kernel<true>, dim3(1), dim3(256), 0, st, (const int32_t*)slab, nb, target, target_offset,
+                           (int)G, V, mf, flags, acc);
+        return (int)hipGetLastError();
+    }
+    hipLaunchKernelGGL(rank_counts_masked_kernel<false>, dim3(nb, (unsigned)G), dim3(256), 0, st, scores, target, target_offset, slab,
+                       (int)G, V, per, mc);
+    hipLaunchKernelGGL(rank_finish_masked_kernel<false>, dim3(1), dim3(256), 0, st, (const int32_t*)slab, nb, target, target_offset,
+                       (int)G, V, mf, flags, acc);
     return (int)hipGetLastError();
+}
+
+extern "C" int mobgt_rank_metrics_masked(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
+                                         const uint32_t* allow, const void* hist, int hist_dtype, int64_t ld_hist, int64_t n_hist_cols,
+                                         int64_t hist_offset, int flags, double* acc, void* work, void* stream) {
+    return mobgt_rank_metrics_masked_rows(scores, target, target_offset, G, V, allow, 0, hist, hist_dtype, ld_hist, n_hist_cols,
+                                          hist_offset, flags, acc, work, stream);
 }
 
 extern "C" int mobgt_skinny_linear_rank_metrics(const float* x, const float* w, const float* b, const int64_t* target, int64_t target_offset,

@@ -16,8 +16,8 @@
 // reversed, folded in by a lane-wise max (the best 64 of both lists, as a bitonic sequence) and re-sorted by a 6-stage merge.
 // The waves of a workgroup then fold their lists pairwise through LDS.
 //
-// mobgt_topk_rows_masked restricts each row to its candidates (an allow bitmap shared by the rows, a per-row list of excluded
-// ids).  A non-candidate takes the key 0, which is below every real key, so the same selection never picks it: launch 1 builds
+// mobgt_topk_rows_masked restricts each row to its candidates (an allow bitmap shared by the rows -- or one per row, through
+// mobgt_topk_rows_masked_rows -- and a per-row list of excluded ids).  A non-candidate takes the key 0, which is below every real key, so the same selection never picks it: launch 1 builds
 // its chunk's 32 candidate words in LDS (the allow words with the row's excluded ids cleared) before the ballot, and launch 2
 // writes a final key 0 -- a row with fewer than k candidates -- as id -1, val -inf.  No extra launch, no [G, V / 32] buffer.
 #include "common.h"
@@ -93,8 +93,8 @@ __device__ __forceinline__ uint64_t block_fold(uint64_t top, uint64_t* s_keys, i
 }
 
 // launch 1: grid (chunks, G); the chunk's k best keys, descending, -> work[g][chunk][0, k) (0 = no column).  MASK: columns that
-// are not candidates take the key 0 (below every real key), so they are never selected.
-template <bool MASK>
+// are not candidates take the key 0 (below every real key), so they are never selected; ROWS: allow words per row (cand_body.h).
+template <bool MASK, bool ROWS = false>
 __global__ __launch_bounds__(64 * TK_WAVES1) void topk_chunk_kernel(const float* __restrict__ scores, int64_t ld, int64_t V, int k,
                                                                     uint64_t* __restrict__ work, CandMask m) {
     __shared__ uint64_t s_keys[TK_WAVES1 * 64];
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64 * TK_WAVES1) void topk_chunk_kernel(const float*
         key[i] = c < V ? tk_key(row[c], (uint32_t)c) : 0;
     }
     if constexpr (MASK) {
-        cand_bits<TK_CHUNK / 32, 64 * TK_WAVES1>(s_ok, m, g, (int64_t)blockIdx.x * TK_CHUNK, V);   // (cand_body.h)
+        cand_bits<TK_CHUNK / 32, 64 * TK_WAVES1, ROWS>(s_ok, m, g, (int64_t)blockIdx.x * TK_CHUNK, V);   // (cand_body.h)
 #pragma unroll
         for (int i = 0; i < TK_ITERS; ++i) {
             const int r = w * 64 + lane + i * 64 * TK_WAVES1;
@@ -174,7 +174,12 @@ int topk_launch(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k
     hipStream_t st = (hipStream_t)stream;
     const int64_t nch = tk_chunks(V);
     uint64_t* wk = reinterpret_cast<uint64_t*>(work);
-    if (masked) {
+    if (masked && m.ld_allow > 0) {
+        hipLaunchKernelGGL((topk_chunk_kernel<true, true>), dim3((unsigned)nch, (unsigned)G), dim3(64 * TK_WAVES1), 0, st, scores, ld, V,
+                           (int)k, wk, m);
+        hipLaunchKernelGGL(topk_finish_kernel<true>, dim3((unsigned)G), dim3(64 * TK_WAVES2), 0, st, scores, ld, nch, (int)k,
+                           (const uint64_t*)wk, col_offset, ids, vals);
+    } else if (masked) {
         hipLaunchKernelGGL(topk_chunk_kernel<true>, dim3((unsigned)nch, (unsigned)G), dim3(64 * TK_WAVES1), 0, st, scores, ld, V,
                            (int)k, wk, m);
         hipLaunchKernelGGL(topk_finish_kernel<true>, dim3((unsigned)G), dim3(64 * TK_WAVES2), 0, st, scores, ld, nch, (int)k,
@@ -195,12 +200,21 @@ extern "C" int mobgt_topk_rows(const float* scores, int64_t ld, int64_t G, int64
     return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, CandMask{}, false, stream);
 }
 
+extern "C" int mobgt_topk_rows_masked_rows(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset,
+                                           const uint32_t* allow, int64_t ld_allow, const void* excl, int excl_dtype, int64_t ld_excl,
+                                           int64_t n_excl_cols, int64_t excl_offset, int64_t* ids, float* vals, void* work,
+                                           void* stream) {
+    if (excl && (n_excl_cols < 0 || ld_excl < n_excl_cols)) return MOBGT_EBADDIM;
+    if (excl && excl_dtype != MOBGT_I64 && excl_dtype != MOBGT_I32) return MOBGT_EDTYPE;
+    if (ld_allow < 0 || (allow && ld_allow > 0 && ld_allow < (V + 31) / 32)) return MOBGT_EBADDIM;
+    const bool use_excl = excl && n_excl_cols > 0;
+    const CandMask m{allow, use_excl ? excl : nullptr, ld_excl, n_excl_cols, excl_offset, excl_dtype == MOBGT_I64, allow ? ld_allow : 0};
+    return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, m, allow || use_excl, stream);
+}
+
 extern "C" int mobgt_topk_rows_masked(const float* scores, int64_t ld, int64_t G, int64_t V, int64_t k, int64_t col_offset,
                                       const uint32_t* allow, const void* excl, int excl_dtype, int64_t ld_excl, int64_t n_excl_cols,
                                       int64_t excl_offset, int64_t* ids, float* vals, void* work, void* stream) {
-    if (excl && (n_excl_cols < 0 || ld_excl < n_excl_cols)) return MOBGT_EBADDIM;
-    if (excl && excl_dtype != MOBGT_I64 && excl_dtype != MOBGT_I32) return MOBGT_EDTYPE;
-    const bool use_excl = excl && n_excl_cols > 0;
-    const CandMask m{allow, use_excl ? excl : nullptr, ld_excl, n_excl_cols, excl_offset, excl_dtype == MOBGT_I64};
-    return topk_launch(scores, ld, G, V, k, col_offset, ids, vals, work, m, allow || use_excl, stream);
+    return mobgt_topk_rows_masked_rows(scores, ld, G, V, k, col_offset, allow, 0, excl, excl_dtype, ld_excl, n_excl_cols, excl_offset,
+                                       ids, vals, work, stream);
 }

@@ -547,9 +547,11 @@ class Graphormer(nn.Module):
             if restrict is not None:
                 # restricted / split: recommend_step's scores, candidates and label space (x holds the trajectory's POI ids as
                 # y does, 0 = padding; column = y - 1 = x - 1, or y = x for toyotagraph)
-                exclude_visited, allow, split = restrict
+                exclude_visited, allow, split, near = restrict
                 scores = torch.log_softmax(logits.float(), dim=1) if toyota else logits
                 hist = batched_data.x.reshape(batched_data.x.shape[0], -1)
+                if near is not None:
+                    allow = self._near_allow(hist, near, allow, toyota)
                 ops.rank_metrics_masked(scores, y_m, acc, target_offset=0 if toyota else -1, allow=allow, hist=hist,
                                         hist_offset=0 if toyota else 1, exclude_hist=exclude_visited, split=split, work=work)
                 return [None, None]
@@ -563,12 +565,15 @@ class Graphormer(nn.Module):
         if r_head is not None:
             # recommend_step: the classifier's scores ranked into the caller's [G, k] buffers, ids in y's label space (the scores
             # and shift metric_step ranks: log_softmax and unshifted for toyotagraph, logits and column + 1 otherwise)
-            ids, vals, work, exclude_visited, allow = r_head
+            ids, vals, work, exclude_visited, allow, near = r_head
             W, b = self.out_proj.weight, self.out_proj.bias
             logits = ops.skinny_linear(tok, W, b) if ops.skinny_linear_ok(tok, W) else self.out_proj(tok)
             scores = torch.log_softmax(logits.float(), dim=1) if toyota else logits
             # (exclude_visited: x holds the trajectory's POI ids in y's label space, 0 = padding)
-            excl = batched_data.x.reshape(batched_data.x.shape[0], -1) if exclude_visited else None
+            hist = batched_data.x.reshape(batched_data.x.shape[0], -1)
+            excl = hist if exclude_visited else None
+            if near is not None:
+                allow = self._near_allow(hist, near, allow, toyota)
             ops.topk_rows(scores, ids.shape[1], col_offset=0 if toyota else 1, work=work, out=(ids, vals), allow=allow, exclude=excl)
             return [None, None]
         if y_head is not None and not toyota and ops.skinny_linear_gtl_ok(tok, self.out_proj.weight):
@@ -589,6 +594,13 @@ class Graphormer(nn.Module):
         if getattr(self, "_poi_logits_only", False):     # training_step reads logits[0] only (:1446-1460)
             return [logits, None]
         return [logits, self.cat_decoder(tok)]                                                 # :1394-1396
+
+    @staticmethod
+    def _near_allow(hist, near, allow, toyota):
+        """metric_step's / recommend_step's near=: the rows' candidate words (ops.near_words on the trajectory's POI ids, the hist
+        and offset exclude_visited uses; a shared allow ANDed in) written into the caller's buffer -> the 2-D allow"""
+        pos, chord2_max, mode, words = near
+        return ops.near_words(pos, hist, 0 if toyota else 1, chord2_max, mode, allow=allow, out=words[:hist.shape[0]])
 
     # modules whose parameters only receive gradient from the part of the graph ABOVE the encoder output: their
     # gradients are complete after the first ~20 kernels of the backward pass (61 % of all gradient bytes: out_proj)
@@ -629,7 +641,7 @@ class Graphormer(nn.Module):
         """model_fqandtoyo.py:1530-1544"""
         return {"y_pred": self(batched_data), "y_true": batched_data.y.long() - 1, "idx": batched_data.idx}
 
-    def metric_step(self, batched_data, acc, work=None, exclude_visited=False, allow=None, split_revisits=False):
+    def metric_step(self, batched_data, acc, work=None, exclude_visited=False, allow=None, split_revisits=False, near=None):
         """validation_step / test_step + test_epoch_end's per-batch bookkeeping in one pass: the batch's ACC / NDCG @1/5/10/20
         and MRR sums (metrics.evaluate_outputs, quirks included) are ADDED to `acc` (metrics.new_accumulator) on the device --
         no category head, no host read.  Eval mode, under no_grad.  toyotagraph ranks log_softmax(logits) against
@@ -638,12 +650,13 @@ class Graphormer(nn.Module):
         Restricted and split (ops.rank_metrics_masked; acc = metrics.new_restricted_accumulator(device, split_revisits), work of
         ops.rank_metrics_masked_work_bytes): the ranking of the lists recommend_step returns with the same exclude_visited /
         allow, so a hit at k <=> y is in that list's first k; a row whose y cannot be listed counts in n only.  split_revisits
-        adds the rows whose y is not among the trajectory's POIs (batched_data.x) to slot 1, the others to slot 2."""
+        adds the rows whose y is not among the trajectory's POIs (batched_data.x) to slot 1, the others to slot 2.
+        near: recommend_step's radius restriction (see there); a y outside its row's radius counts in n only."""
         if self.training:
             raise RuntimeError("metric_step: the model is in training mode (call .eval() first)")
         restrict = None
-        if exclude_visited or allow is not None or split_revisits:
-            restrict = (bool(exclude_visited), allow, bool(split_revisits))
+        if exclude_visited or allow is not None or split_revisits or near is not None:
+            restrict = (bool(exclude_visited), allow, bool(split_revisits), near)
         with torch.no_grad():
             self._metrics_in_head = (batched_data.y, acc, work, restrict)
             try:
@@ -652,7 +665,7 @@ class Graphormer(nn.Module):
                 self._metrics_in_head = None
         return acc
 
-    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None):
+    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None, near=None):
         """The batch's top-k next POIs, best first, into ids [G, k] int64 / vals [G, k] f32 (k = ids.shape[1] <= ops.TOPK_MAX) on
         the device: the scores metric_step ranks (logits; log_softmax for toyotagraph) in ops.topk_rows' order, so equal scores
         list the lower POI first and `y in ids[:, :k]` is exactly the hit ACC@k counts.  ids are in batched_data.y's label space:
@@ -661,32 +674,45 @@ class Graphormer(nn.Module):
 
         exclude_visited: leave out the POIs of each trajectory (batched_data.x, the same label space as y) -- next *new* POI
         lists.  allow: ops.pack_allow(candidate ids, V, offset) words (offset 0 for toyotagraph, else 1): only those POIs are
-        listed.  A row with fewer than k candidates ends in ids -1 / vals -inf."""
+        listed.  A row with fewer than k candidates ends in ids -1 / vals -inf.
+
+        near = (pos, chord2_max, mode, words): only POIs within a radius of the row's anchor are listed.  pos =
+        ops.pack_positions(coords, V, offset), chord2_max = ops.chord2_of_km(r), mode "last" / "any", words an int32
+        [>= G, >= ceil(V / 32)] device buffer: the step launches ops.near_words on batched_data.x into it (inside a captured
+        graph when the step is captured; a shared `allow` is ANDed in) and ranks with the rows' own words.  A trajectory graph
+        stores distinct POIs, not the visit order: "last" is the trajectory's last node (node_name[-1]), not the last check-in
+        when the walk ended on a revisit; "any" -- within r of anywhere the user has been -- does not depend on order."""
         if self.training:
             raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
         with torch.no_grad():
-            self._recommend_in_head = (ids, vals, work, bool(exclude_visited), allow)
+            self._recommend_in_head = (ids, vals, work, bool(exclude_visited), allow, near)
             try:
                 self(batched_data)
             finally:
                 self._recommend_in_head = None
         return ids, vals
 
-    def recommend(self, dataset, collator, k=20, exclude_visited=False, candidates=None, **kw):
-        """train.PredictLoop(self, collator, dataset, k=k, exclude_visited=..., candidates=..., **kw).run(): (sample_index [n],
-        ids [n, k], vals [n, k]) on the device."""
+    def recommend(self, dataset, collator, k=20, exclude_visited=False, candidates=None, within_km=None, coords=None, near="last",
+                  **kw):
+        """train.PredictLoop(self, collator, dataset, k=k, exclude_visited=..., candidates=..., within_km=..., coords=...,
+        near=..., **kw).run(): (sample_index [n], ids [n, k], vals [n, k]) on the device.  within_km: only POIs within that many
+        km of the trajectory's last node (near="last"; not the last check-in when the walk ended on a revisit) or of any of its
+        POIs (near="any"); coords [P + 1, 2] lat / lon in degrees, default the collator's."""
         from .train import PredictLoop
         max_batches = kw.pop("max_batches", None)
         return PredictLoop(self, collator, dataset, k=k, exclude_visited=exclude_visited, candidates=candidates,
-                           **kw).run(max_batches=max_batches)
+                           within_km=within_km, coords=coords, near=near, **kw).run(max_batches=max_batches)
 
-    def evaluate(self, dataset, collator, exclude_visited=False, candidates=None, split_revisits=False, **kw):
-        """train.EvalLoop(self, collator, dataset, exclude_visited=..., candidates=..., split_revisits=..., **kw).run(): the
-        reference's validation / test protocol over a whole split, optionally over restricted lists and split by revisits."""
+    def evaluate(self, dataset, collator, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
+                 near="last", **kw):
+        """train.EvalLoop(self, collator, dataset, exclude_visited=..., candidates=..., split_revisits=..., within_km=...,
+        coords=..., near=..., **kw).run(): the reference's validation / test protocol over a whole split, optionally over
+        restricted lists (within_km / coords / near as in recommend) and split by revisits."""
         from .train import EvalLoop
         max_batches = kw.pop("max_batches", None)
         return EvalLoop(self, collator, dataset, exclude_visited=exclude_visited, candidates=candidates,
-                        split_revisits=split_revisits, **kw).run(max_batches=max_batches)
+                        split_revisits=split_revisits, within_km=within_km, coords=coords, near=near,
+                        **kw).run(max_batches=max_batches)
 
     def test_epoch_end(self, outputs):
         """model_fqandtoyo.py:1546-1597: ACC / NDCG @1/5/10/20 and MRR over all test samples."""

@@ -3,6 +3,7 @@ HIP stream go in, autograd comes out.  PyTorch is plumbing here (memory, streams
 all arithmetic of the hot path happens in libmobgt_hip.so.  No CPU fallback exists.
 """
 import ctypes
+import math
 
 import torch
 
@@ -982,6 +983,7 @@ def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=N
     p - hist_offset; hist_offset defaults to -target_offset, the target's label space); a row whose target is not a candidate
     counts in n only.  The ranking is that of topk_rows(scores, allow=, exclude=hist): a hit at k <=> y is in its first k.
     CUDA f32 scores: mobgt_rank_metrics_masked, two launches, no host read.  Other inputs: restricted_sums itself.
+    A 2-D `allow` [G, W >= ceil(V / 32)] int32 (near_words) gives every row its own words: mobgt_rank_metrics_masked_rows.
     `work`: a device buffer of rank_metrics_masked_work_bytes(G, V) bytes (default: one per stream)."""
     G, V = scores.shape
     hist_offset = -int(target_offset) if hist_offset is None else int(hist_offset)
@@ -991,8 +993,7 @@ def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=N
     assert acc.dtype == torch.float64 and acc.shape == (S, 11) and acc.is_contiguous(), \
         f"rank_metrics_masked: acc = metrics.new_restricted_accumulator(device, split={bool(split)}), f64 [{S}, 11]"
     if allow is not None:
-        assert allow.dtype == torch.int32 and allow.dim() == 1 and allow.numel() >= (V + 31) // 32, \
-            f"rank_metrics_masked: allow = pack_allow(..., {V}) words, int32 [{(V + 31) // 32}]"
+        _check_allow(allow, G, V, "rank_metrics_masked")
     if hist is not None:
         assert hist.dim() == 2 and hist.shape[0] == G and hist.dtype in (torch.int32, torch.int64), \
             f"rank_metrics_masked: hist = [{G}, n] int32 / int64 ids"
@@ -1005,8 +1006,9 @@ def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=N
     _require_cuda(scores, target, acc)
     scores = scores.contiguous()
     target = target.long().contiguous()
+    ld_allow = 0
     if allow is not None:
-        assert allow.is_cuda and allow.is_contiguous(), "rank_metrics_masked: allow words on the device, contiguous"
+        allow, ld_allow = _allow_on_device(allow, V, "rank_metrics_masked")
     n_h, ld_h = 0, 0
     if hist is not None:
         assert hist.is_cuda, "rank_metrics_masked: hist on the device"
@@ -1015,6 +1017,12 @@ def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=N
         n_h, ld_h = hist.shape[1], max(hist.stride(0), hist.shape[1])
     work = _rank_work(scores.device, G, V, work, rank_metrics_masked_work_bytes(G, V))
     flags = (RM_EXCLUDE_HIST if exclude_hist else 0) | (RM_SPLIT if split else 0)
+    if ld_allow:
+        check(_lib.lib().mobgt_rank_metrics_masked_rows(_p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), ld_allow,
+                                                        _p(hist), _IT[hist.dtype] if hist is not None else I64, ld_h, n_h,
+                                                        hist_offset, flags, _p(acc), _p(work), _stream()),
+              "mobgt_rank_metrics_masked_rows")
+        return acc
     check(_lib.lib().mobgt_rank_metrics_masked(_p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), _p(hist),
                                                _IT[hist.dtype] if hist is not None else I64, ld_h, n_h, hist_offset, flags,
                                                _p(acc), _p(work), _stream()), "mobgt_rank_metrics_masked")
@@ -1078,12 +1086,151 @@ def pack_allow(mask_or_ids, V, offset=0):
     return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
 
 
+EARTH_RADIUS_KM = 6371.0     # synth.haversine_km's constant
+NEAR_LAST, NEAR_ANY = 0, 1   # include/mobgt_hip.h: MOBGT_NEAR_*
+_NEAR_MODES = {"last": NEAR_LAST, "any": NEAR_ANY}
+
+
+def near_mode(mode):
+    if mode not in _NEAR_MODES:
+        raise ValueError(f"near: mode must be 'last' or 'any', got {mode!r}")
+    return _NEAR_MODES[mode]
+
+
+def pack_positions(coords_deg, V, offset, radians=False):
+    """The `pos` of near_words / mobgt_near_words: [V, 4] f32 on the input's device, column c = POI id c + offset.  coords_deg is
+    [P + 1, 2] latitude / longitude in degrees, row 0 the pad POI (synth's and DeviceCollator(coords=)'s layout; radians=True:
+    the table is in radians already, as DeviceCollator.coords keeps it).  x, y, z are the POI's unit vector, computed in
+    float64 and rounded once to f32, w is 0; a column whose id is 0 or beyond the table holds x = y = z = +inf, which the
+    predicate never finds near."""
+    V, offset = int(V), int(offset)
+    if coords_deg.dim() != 2 or coords_deg.shape[1] != 2:
+        raise ValueError(f"pack_positions: coords_deg must be [P + 1, 2] degrees, got {tuple(coords_deg.shape)}")
+    dev = coords_deg.device
+    ids = torch.arange(V, device=dev) + offset
+    has = (ids >= 1) & (ids < coords_deg.shape[0])
+    ll = coords_deg.to(torch.float64)
+    ll = (ll if radians else torch.deg2rad(ll))[ids.clamp(0, coords_deg.shape[0] - 1)]
+    lat, lon = ll[:, 0], ll[:, 1]
+    xyz = torch.stack([torch.cos(lat) * torch.cos(lon), torch.cos(lat) * torch.sin(lon), torch.sin(lat)], 1)
+    pos = torch.zeros(V, 4, dtype=torch.float32, device=dev)
+    pos[:, :3] = torch.where(has[:, None], xyz, torch.full_like(xyz, float("inf"))).to(torch.float32)
+    return pos
+
+
+def chord2_of_km(r):
+    """chord2_max of near_words for a radius of r km: float32((2 sin(min(r, pi R) / (2 R)))^2) computed in float64, the squared
+    chord between unit vectors a great-circle distance r apart (R = 6371.0, synth.haversine_km's constant).  0 at r = 0 (the
+    anchor and POIs on the same spot), 4 from half the circumference on (every POI)."""
+    r = float(r)
+    if not r >= 0.0:
+        raise ValueError(f"chord2_of_km: radius must be >= 0 km, got {r}")
+    c = 2.0 * math.sin(min(r, math.pi * EARTH_RADIUS_KM) / (2.0 * EARTH_RADIUS_KM))
+    return float(torch.tensor(c * c, dtype=torch.float64).to(torch.float32))
+
+
+def _near_words_torch(pos, hist, hist_offset, chord2_max, mode, allow):
+    """mobgt_near_words' contract in torch: the specification of the kernel (same f32 operations in the same order)"""
+    V, (G, n) = pos.shape[0], hist.shape
+    dev = pos.device
+    W = (V + 31) // 32
+    near = torch.zeros(G, W * 32, dtype=torch.bool, device=dev)
+    h = hist.to(device=dev, dtype=torch.int64)
+    col = h - int(hist_offset)
+    valid = (h != 0) & (col >= 0) & (col < V)
+    if mode == NEAR_LAST and n:
+        j = torch.arange(1, n + 1, device=dev)[None, :]
+        last = (valid * j).max(1).values - 1                   # -1: the row has no anchor
+        valid = valid & (j - 1 == last[:, None])
+    c2 = torch.tensor(chord2_max, dtype=torch.float32, device=dev)
+    p = pos[:, :3].to(torch.float32)
+    for g in range(G):
+        a = p[col[g][valid[g]]]                                # [A, 3]
+        for a0 in range(0, a.shape[0], 64):
+            d = p[None, :, :] - a[a0:a0 + 64, None, :]         # [A, V, 3], each operation rounded to f32 on its own
+            d = d * d
+            near[g, :V] |= (((d[..., 0] + d[..., 1]) + d[..., 2]) <= c2).any(0)
+    bits = near.view(G, W, 32).long() << torch.arange(32, dtype=torch.int64, device=dev)
+    words = bits.sum(2)
+    words = torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+    if allow is not None:
+        words &= allow.to(dev)[:W]
+    return words
+
+
+def near_words(pos, hist, hist_offset, chord2_max, mode="last", allow=None, out=None):
+    """Per-row allow words from coordinates: int32 [G, ceil(V / 32)], bit c & 31 of word c >> 5 of row g set when column c is
+    within the radius of one of the row's anchors -- the 2-D `allow` of topk_rows / rank_metrics_masked.
+
+    pos = pack_positions(...) [V, 4] f32; hist [G, n] int32 / int64 ids with the masked kernels' meaning (0 is padding,
+    id - hist_offset is a column, ids mapping outside [0, V) are skipped).  mode "last": the anchor is the row's last such id;
+    "any": every one of them.  Column c is near when an anchor a has, in f32 with every operation rounded on its own,
+        ((dx*dx) + (dy*dy)) + (dz*dz) <= chord2_max,   dx = pos[c, 0] - pos[a, 0], ...       (chord2_max = chord2_of_km(r))
+    inf and NaN compare false: a column without a POI is never near, a row without an anchor has no candidates.  `allow`
+    (pack_allow words) is ANDed in.  CUDA inputs: mobgt_near_words, one graph-capturable launch that writes every word of
+    out[:, :ceil(V / 32)] (`out`: int32 [G, >= ceil(V / 32)], unit column stride; words beyond are left alone).  Other inputs:
+    the torch statement of this contract, which is the kernel's specification."""
+    m = near_mode(mode)
+    assert pos.dim() == 2 and pos.shape[1] == 4 and pos.dtype == torch.float32, "near_words: pos = pack_positions(...), f32 [V, 4]"
+    assert hist.dim() == 2 and hist.dtype in (torch.int32, torch.int64), "near_words: hist = [G, n] int32 / int64 ids"
+    V, (G, n) = pos.shape[0], hist.shape
+    W = (V + 31) // 32
+    if allow is not None:
+        assert allow.dtype == torch.int32 and allow.dim() == 1 and allow.numel() >= W, \
+            f"near_words: allow = pack_allow(..., {V}) words, int32 [{W}]"
+    if out is not None:
+        assert out.dtype == torch.int32 and out.dim() == 2 and out.shape[0] == G and out.shape[1] >= W and out.stride(1) == 1 \
+            and out.stride(0) >= W and out.device == pos.device, f"near_words: out = int32 [{G}, >= {W}] on pos' device"
+    chord2_max = float(chord2_max)
+    if not pos.is_cuda:
+        words = _near_words_torch(pos, hist, hist_offset, chord2_max, m, allow)
+        if out is None:
+            return words
+        out[:, :W].copy_(words)
+        return out
+    _require_cuda(pos, hist)
+    pos = pos.contiguous()
+    if n and (hist.stride(1) != 1 or hist.stride(0) < n):
+        hist = hist.contiguous()
+    if allow is not None:
+        assert allow.is_cuda and allow.is_contiguous(), "near_words: allow words on the device, contiguous"
+    if out is None:
+        out = torch.empty(G, W, dtype=torch.int32, device=pos.device)
+    if G == 0:
+        return out
+    check(_lib.lib().mobgt_near_words(_p(pos), V, _p(hist), _IT[hist.dtype], max(hist.stride(0), n), n, int(hist_offset), m,
+                                      chord2_max, _p(allow), _p(out), out.stride(0), G, _stream()), "mobgt_near_words")
+    return out
+
+
+def _check_allow(allow, G, V, who):
+    """1-D words shared by the rows, or 2-D words per row (near_words)"""
+    W = (V + 31) // 32
+    if allow.dim() == 2:
+        assert allow.dtype == torch.int32 and allow.shape[0] == G and allow.shape[1] >= W, \
+            f"{who}: per-row allow = near_words(...) words, int32 [{G}, {W}]"
+        return
+    assert allow.dtype == torch.int32 and allow.dim() == 1 and allow.numel() >= W, \
+        f"{who}: allow = pack_allow(..., {V}) words, int32 [{W}]"
+
+
+def _allow_on_device(allow, V, who):
+    if allow.dim() == 2:
+        assert allow.is_cuda, f"{who}: allow words on the device"
+        if allow.stride(1) != 1 or allow.stride(0) < (V + 31) // 32:
+            allow = allow.contiguous()
+        return allow, allow.stride(0)
+    assert allow.is_cuda and allow.is_contiguous(), f"{who}: allow words on the device, contiguous"
+    return allow, 0
+
+
 def _candidates(G, V, allow, exclude, exclude_offset, device):
     """[G, V] bool: the candidate columns of topk_rows' restricted form (see there)"""
     ok = torch.ones(G, V, dtype=torch.bool, device=device)
     if allow is not None:
-        w = allow.to(device=device, dtype=torch.int64)[torch.arange(V, device=device) >> 5]
-        ok &= ((w >> (torch.arange(V, device=device) & 31)) & 1).bool()[None, :]
+        cols = torch.arange(V, device=device)
+        w = allow.to(device=device, dtype=torch.int64)[..., cols >> 5]         # ([V], or [G, V] from per-row words)
+        ok &= ((w >> (cols & 31)) & 1).bool()
     if exclude is not None and exclude.numel():
         e = exclude.to(device=device, dtype=torch.int64)
         c = e - int(exclude_offset)
@@ -1105,7 +1252,8 @@ def topk_rows(scores, k, col_offset=0, work=None, out=None, allow=None, exclude=
     are never listed) and / or `exclude` [G, n] int32 / int64 ids per row (entry p != 0 removes column p - exclude_offset from its
     row; 0 is padding; ids outside [0, V) after the shift are ignored; exclude_offset defaults to col_offset).  The result is the
     same order over the candidates only; a row with m < k candidates reads ids -1, vals -inf from position m on.  CUDA f32
-    scores: mobgt_topk_rows_masked (same two launches); other inputs: the torch statement of that contract."""
+    scores: mobgt_topk_rows_masked (same two launches); other inputs: the torch statement of that contract.  A 2-D `allow`
+    [G, W >= ceil(V / 32)] int32 (near_words; row stride free) gives every row its own words: mobgt_topk_rows_masked_rows."""
     G, V = scores.shape
     k = int(k)
     if not 1 <= k <= V:
@@ -1135,8 +1283,7 @@ def topk_rows(scores, k, col_offset=0, work=None, out=None, allow=None, exclude=
 def _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude, exclude_offset):
     G, V = scores.shape
     if allow is not None:
-        assert allow.dtype == torch.int32 and allow.dim() == 1 and allow.numel() >= (V + 31) // 32, \
-            f"topk_rows: allow = pack_allow(..., {V}) words, int32 [{(V + 31) // 32}]"
+        _check_allow(allow, G, V, "topk_rows")
     if exclude is not None:
         assert exclude.dim() == 2 and exclude.shape[0] == G and exclude.dtype in (torch.int32, torch.int64), \
             f"topk_rows: exclude = [{G}, n] int32 / int64 ids"
@@ -1155,8 +1302,9 @@ def _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude, exclude_
         return out
     if scores.stride(1) != 1 or scores.stride(0) < V:
         scores = scores.contiguous()
+    ld_allow = 0
     if allow is not None:
-        assert allow.is_cuda and allow.is_contiguous(), "topk_rows: allow words on the device, contiguous"
+        allow, ld_allow = _allow_on_device(allow, V, "topk_rows")
     n_ex, ld_ex = 0, 0
     if exclude is not None:
         assert exclude.is_cuda, "topk_rows: exclude on the device"
@@ -1167,6 +1315,12 @@ def _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude, exclude_
     if G == 0:
         return out
     work = _topk_work(scores, G, V, k, work)
+    if ld_allow:
+        check(_lib.lib().mobgt_topk_rows_masked_rows(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
+                                                     ld_allow, _p(exclude), _IT[exclude.dtype] if exclude is not None else I64,
+                                                     ld_ex, n_ex, int(exclude_offset), _p(ids), _p(vals), _p(work), _stream()),
+              "mobgt_topk_rows_masked_rows")
+        return out
     check(_lib.lib().mobgt_topk_rows_masked(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
                                             _p(exclude), _IT[exclude.dtype] if exclude is not None else I64, ld_ex, n_ex,
                                             int(exclude_offset), _p(ids), _p(vals), _p(work), _stream()), "mobgt_topk_rows_masked")

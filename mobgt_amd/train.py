@@ -1393,6 +1393,34 @@ def _pack_candidates(model, candidates, V, device):
     return ops.pack_allow(torch.as_tensor(candidates).to(device), V, offset)
 
 
+def _near_args(collator, within_km, coords, near):
+    """The radius restriction of EvalLoop / PredictLoop, checked on the host before anything is allocated:
+    None, or (coordinate table, whether it is in radians, chord2_max, mode)."""
+    ops.near_mode(near)                                               # (a bad mode string is refused here, on the host)
+    mode = near
+    if within_km is None:
+        return None
+    chord2_max = ops.chord2_of_km(within_km)
+    if coords is not None:
+        return torch.as_tensor(coords), False, chord2_max, mode
+    if getattr(collator, "coords", None) is None:
+        raise ValueError("within_km: no POI coordinates -- pass coords=[P + 1, 2] lat / lon in degrees (row 0 the pad POI), or "
+                         "use a collator built with coords=")
+    return collator.coords, True, chord2_max, mode                    # (DeviceCollator keeps radians)
+
+
+def _near_state(model, args, V, batch_size, device):
+    """-> Graphormer.metric_step's / recommend_step's near=(pos, chord2_max, mode, words): the positions packed once and one
+    [batch_size, W] words buffer, so that a loop's graphs build and read the rows' candidate words at fixed addresses."""
+    if args is None:
+        return None
+    table, radians, chord2_max, mode = args
+    offset = 0 if getattr(model, "dataset_name", None) == "toyotagraph" else 1          # (recommend_step's label space)
+    pos = ops.pack_positions(table.to(device), V, offset, radians=radians)
+    words = torch.zeros(batch_size, (V + 31) // 32, dtype=torch.int32, device=device)
+    return pos, chord2_max, mode, words
+
+
 class EvalLoop(_StagedBatches):
     """The validation / test loop (Lightning's `trainer.validate` / `trainer.test` over the reference's eval DataLoader,
     entry.py:120-161, with test_epoch_end's bookkeeping, model_fqandtoyo.py:1484-1597) on the device data path of EpochLoop.
@@ -1414,19 +1442,29 @@ class EvalLoop(_StagedBatches):
     POIs its trajectory has not visited, candidates (POI ids in y's label space, packed once here) among those only.
     split_revisits also reports the rows whose target is a new POI and those whose target is a revisit.  run() then returns
     metrics.finalize_restricted's dict: today's keys, "n", "reachable" (targets that can be listed at all) and, with the split,
-    "new" / "revisit" dicts of the same keys.  The defaults run today's launches and return today's dict."""
+    "new" / "revisit" dicts of the same keys.  The defaults run today's launches and return today's dict.
+
+    within_km=r ranks each target among the POIs within r km of the row's anchor (ops.near_words inside the captured graph, then
+    the per-row form of ops.rank_metrics_masked); it combines with the other restrictions.  coords: [P + 1, 2] lat / lon in
+    degrees, row 0 the pad POI (default: the collator's coords; neither: ValueError).  near="last": the anchor is the
+    trajectory's last node -- a trajectory graph stores distinct POIs, not the visit order, so this is node_name[-1], not the
+    last check-in when the walk ended on a revisit; near="any": within r of any POI of the trajectory, which does not depend on
+    order.  A target outside its row's radius is unreachable and counts in n only."""
 
     def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
-                 side_collate=True, exclude_visited=False, candidates=None, split_revisits=False):
+                 side_collate=True, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
+                 near="last"):
         from . import metrics
         if not hasattr(model, "metric_step"):
             raise TypeError("EvalLoop: the model has no metric_step (the fq model, model_fqandtoyo.Graphormer)")
+        near_args = _near_args(collator, within_km, coords, near)
         self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
         self.captures = 0                                   # graphs captured so far (a replayed run captures none)
         V = model.out_proj.out_features
         self.exclude_visited, self.split_revisits = bool(exclude_visited), bool(split_revisits)
         self.allow = _pack_candidates(model, candidates, V, self.device)
-        self.restricted = self.exclude_visited or self.allow is not None or self.split_revisits
+        self.near = _near_state(model, near_args, V, self.batch_size, self.device)
+        self.restricted = self.exclude_visited or self.allow is not None or self.split_revisits or self.near is not None
         if self.restricted:
             self.acc = metrics.new_restricted_accumulator(self.device, self.split_revisits)
             self._scratch = metrics.new_restricted_accumulator(self.device, self.split_revisits)     # warm-ups count nowhere
@@ -1462,7 +1500,7 @@ class EvalLoop(_StagedBatches):
         b = self.collator.finish(batch) if isinstance(batch, dict) else batch      # (raw views: the in-graph collate)
         if self.restricted:
             self.model.metric_step(b, acc, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow,
-                                   split_revisits=self.split_revisits)
+                                   split_revisits=self.split_revisits, near=self.near)
             return
         self.model.metric_step(b, acc, work=self.work)
 
@@ -1591,12 +1629,18 @@ class PredictLoop(EvalLoop):
 
     A loop keeps one restriction for its lifetime: exclude_visited leaves out each trajectory's own POIs (next *new* POI lists);
     candidates, a 1-D tensor of POI ids in y's label space, limits every list to them (packed once, here, into words the graphs
-    read at a fixed address).  Rows with fewer than k candidates end in ids -1 / vals -inf, as dropped trajectories do."""
+    read at a fixed address).  Rows with fewer than k candidates end in ids -1 / vals -inf, as dropped trajectories do.
+
+    within_km=r limits each list to the POIs within r km of the row's anchor, with coords and near as in EvalLoop (near="last":
+    the trajectory's last node, node_name[-1], which is not the last check-in when the walk ended on a revisit; near="any":
+    within r of any POI of the trajectory).  The rows' candidate words are built inside the captured graph (ops.near_words) from
+    positions packed once here, and combine with exclude_visited and candidates."""
 
     def __init__(self, model, collator, dataset, k=20, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
-                 side_collate=True, exclude_visited=False, candidates=None):
+                 side_collate=True, exclude_visited=False, candidates=None, within_km=None, coords=None, near="last"):
         if not hasattr(model, "recommend_step"):
             raise TypeError("PredictLoop: the model has no recommend_step (the fq model, model_fqandtoyo.Graphormer)")
+        near_args = _near_args(collator, within_km, coords, near)
         V = model.out_proj.out_features
         self.k = int(k)
         if not 1 <= self.k <= min(ops.TOPK_MAX, V):
@@ -1604,6 +1648,7 @@ class PredictLoop(EvalLoop):
         self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
         self.exclude_visited = bool(exclude_visited)
         self.allow = _pack_candidates(model, candidates, V, self.device)
+        self.near = _near_state(model, near_args, V, self.batch_size, self.device)
         self.captures = 0
         self.acc = self._scratch = None                     # (EvalLoop._launch passes them to _forward, which ignores them)
         self.outs = {}                                      # (G, N) -> the [G, k] buffers its graphs write
@@ -1612,7 +1657,8 @@ class PredictLoop(EvalLoop):
 
     def _forward(self, batch, _acc):
         b = self.collator.finish(batch) if isinstance(batch, dict) else batch
-        self.model.recommend_step(b, *self._out, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow)
+        self.model.recommend_step(b, *self._out, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow,
+                                  near=self.near)
 
     def _launch(self, slot, st):
         key = (slot["layout"].G, slot["layout"].N)

@@ -9,8 +9,11 @@
           (256) and S-BIG's (784) trajectories, `allow` at 10 / 50 / 99 % density; next to mobgt_topk_rows and the torch route
           (masked_fill(-inf) of a precomputed mask + the stable sort), timed as the kernel leg; then PredictLoop(k = 20) check-ins
           / s with exclude_visited next to the plain loop at S-FSQ (both captured first, then the best of 5 alternated runs).
+  near    the radius restriction at G = 16, V = 7 857 / 100 001, 64 ids per row, a 2 km radius in a synthetic city: ops.near_words
+          alone ("last" and "any"), near_words + the per-row top-k (mobgt_topk_rows_masked_rows, k = 20), and the shared-allow
+          top-k of the same build, timed as the kernel leg.
 
-  python tools/topk_bench.py [--part kernel|loop|masked|all] [--batches N] [--reps N]
+  python tools/topk_bench.py [--part kernel|loop|masked|near|all] [--batches N] [--reps N]
 """
 import argparse
 import json
@@ -134,9 +137,41 @@ def bench_masked_loop(n_batches):
     return res
 
 
+def bench_near(G, V, k, reps, n_ids=64, r_km=2.0):
+    import numpy as np
+    from mobgt_amd import synth
+    uni = synth.make_sparse_universe(P=V, n_cat=8, n_user=8, seed=3)          # ~32 POIs within 3 km of a POI, whatever V is
+    pos = ops.pack_positions(torch.from_numpy(uni.coords), V, 1).to(DEV)
+    gen = torch.Generator(device=DEV).manual_seed(V + k)
+    x = torch.randn(G, V, device=DEV, generator=gen)
+    ids = torch.randint(1, V + 1, (G, n_ids), device=DEV, generator=gen, dtype=torch.int32)
+    c2 = ops.chord2_of_km(r_km)
+    W = (V + 31) // 32
+    words = torch.zeros(G, W, dtype=torch.int32, device=DEV)
+    out = (torch.empty(G, k, dtype=torch.int64, device=DEV), torch.empty(G, k, device=DEV))
+    work = torch.empty(ops.topk_work_bytes(G, V, k), dtype=torch.uint8, device=DEV)
+    res = dict(part="near", G=G, V=V, k=k, ids_per_row=n_ids, r_km=r_km)
+    same = True
+    for mode in ("last", "any"):
+        res[f"near_words_{mode}_us"] = _per_call_us(lambda: ops.near_words(pos, ids, 1, c2, mode, out=words), reps)
+        same &= bool(torch.equal(words.cpu(), ops.near_words(pos.cpu(), ids.cpu(), 1, c2, mode)))
+        res[f"candidates_per_row_{mode}"] = int(np.unpackbits(words.cpu().numpy().view(np.uint8)).sum()) / G
+
+        def both():
+            ops.near_words(pos, ids, 1, c2, mode, out=words)
+            ops.topk_rows(x, k, col_offset=1, work=work, out=out, allow=words)
+        res[f"near_{mode}_plus_topk_rows_us"] = _per_call_us(both, reps)
+    res["topk_per_row_allow_us"] = _per_call_us(lambda: ops.topk_rows(x, k, col_offset=1, work=work, out=out, allow=words), reps)
+    shared = words[0].clone()
+    res["topk_shared_allow_us"] = _per_call_us(lambda: ops.topk_rows(x, k, col_offset=1, work=work, out=out, allow=shared), reps)
+    res["topk_rows_us"] = _per_call_us(lambda: ops.topk_rows(x, k, col_offset=1, work=work, out=out), reps)
+    res["near_words_same_as_torch_form"] = same
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=("kernel", "loop", "masked", "all"))
+    ap.add_argument("--part", default="all", choices=("kernel", "loop", "masked", "near", "all"))
     ap.add_argument("--batches", type=int, default=32)
     ap.add_argument("--reps", type=int, default=50)
     a = ap.parse_args()
@@ -153,6 +188,9 @@ def main():
         for G in (1, 16):
             for V in (3680, 7857, 20000, 100001):
                 print(json.dumps(bench_masked(G, V, 20, a.reps)), flush=True)
+    if a.part in ("near", "all"):
+        for V in (7857, 100001):
+            print(json.dumps(bench_near(16, V, 20, a.reps)), flush=True)
 
 
 if __name__ == "__main__":
