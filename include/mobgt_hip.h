@@ -39,8 +39,10 @@ extern "C" {
 
 /* Library / device identification (no GPU work). */
 /* Bumped on every incompatible change of a signature below (round 5 inserted `out_lo` into the attention entry points under
- * version 1 -- ADVICE r5; version 2 = that ABI; version 3 = round 6).  mobgt_amd/_lib.py refuses a library whose
- * version differs from the one its SIGNATURES table was written for. */
+ * version 1 -- ADVICE r5; version 2 = that ABI; version 3 = round 6).  mobgt_amd/_lib.py derives its SIGNATURES table and its
+ * constants from this file (mobgt_amd/_cabi.py: one-statement prototypes over int / int64_t / float / double /
+ * uint64_t / uint32_t and pointers, integer #defines named MOBGT_*) and refuses a library whose version differs from the number
+ * below: a new entry point is its prototype here, its definition in csrc/ and its caller. */
 #define MOBGT_ABI_VERSION 3
 int mobgt_abi_version(void);
 const char* mobgt_build_info(void);

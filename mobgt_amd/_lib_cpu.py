@@ -4,26 +4,21 @@ import ctypes
 import os
 import subprocess
 
+from . import _cabi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmobgt_cpu.so")
 CSRC = os.path.join(_HERE, "csrc_cpu")
+_HEADER = os.path.join(os.path.dirname(_HERE), "include", "mobgt_cpu.h")
 
-_c = ctypes
-_vp, _i = _c.c_void_p, _c.c_int
-
-SIGNATURES = {
-    "mobgt_cpu_abi_version": (_i, []),
-    "mobgt_floyd_warshall_cpu": (_i, [_vp, _i, _vp, _vp]),
-    "mobgt_gen_edge_input_cpu": (_i, [_i, _vp, _vp, _i, _i, _vp]),
-    "mobgt_get_all_edges_cpu": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
-}
-EINDEX, ERECURSION, ENOMEM = 1, 3, 4
+SIGNATURES, CONSTANTS = _cabi.load(_HEADER)          # (derived from the header, like _lib's)
+EINDEX, ERECURSION, ENOMEM = (CONSTANTS["MOBGT_CPU_" + n] for n in ("EINDEX", "ERECURSION", "ENOMEM"))
 
 _lib = None
 
 
 def build(force=False):
-    srcs = [os.path.join(CSRC, "algos_cpu.cpp"), os.path.join(os.path.dirname(_HERE), "include", "mobgt_cpu.h")]
+    srcs = [os.path.join(CSRC, "algos_cpu.cpp"), _HEADER]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-C", CSRC])
@@ -35,10 +30,5 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing; build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = handle
+        _lib = _cabi.bind(ctypes.CDLL(LIB_PATH), SIGNATURES)
     return _lib

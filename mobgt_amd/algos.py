@@ -96,7 +96,7 @@ def _fw_device(adj):
     M = torch.empty(n, n, dtype=torch.int64, device=dev)
     path = torch.empty(n, n, dtype=torch.int64, device=dev)
     work = torch.empty(int(_lib.lib().mobgt_floyd_warshall_workspace_bytes(n)), dtype=torch.uint8, device=dev)
-    _lib.check(_lib.lib().mobgt_floyd_warshall(_p(a), n, _p(M), _p(path), _p(work), _stream()), "mobgt_floyd_warshall")
+    _lib.call("mobgt_floyd_warshall", _p(a), n, _p(M), _p(path), _p(work), _stream())
     return M.cpu().numpy(), path.cpu().numpy()
 
 
@@ -109,8 +109,7 @@ def _edge_input_device(max_dist, p, f):
     pd, fd = torch.from_numpy(p).to(dev), torch.from_numpy(f).to(dev)
     out = torch.empty(n, n, max_dist, F, dtype=torch.float32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().mobgt_gen_edge_input(max_dist, _p(pd), _p(fd), n, F, _p(out), _p(err), _stream()),
-               "mobgt_gen_edge_input")
+    _lib.call("mobgt_gen_edge_input", max_dist, _p(pd), _p(fd), n, F, _p(out), _p(err), _stream())
     code = int(err.item())
     if code in (1, 2):
         raise IndexError("gen_edge_input: a shortest path has more hops than max_dist")
@@ -129,8 +128,7 @@ def _all_edges_device(p, i, j):
     out = torch.empty(n + 2, dtype=torch.int32, device=dev)
     ln = torch.zeros(1, dtype=torch.int32, device=dev)
     work = torch.empty(2 * n + 4, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().mobgt_get_all_edges(_p(pd), n, int(i), int(j), _p(out), _p(ln), _p(work), _stream()),
-               "mobgt_get_all_edges")
+    _lib.call("mobgt_get_all_edges", _p(pd), n, int(i), int(j), _p(out), _p(ln), _p(work), _stream())
     k = int(ln.item())
     if k < 0:
         raise RecursionError("get_all_edges: path matrix does not terminate")

@@ -144,13 +144,12 @@ class DeviceCollator:
         lib = _lib.lib()
         if work is None:
             work = torch.empty(int(lib.mobgt_spd_workspace_bytes(G, N)), dtype=torch.uint8, device=self.device)
-        _lib.check(lib.mobgt_spd_batched(_p(v["counts"]), _p(v["n_nodes"]), _p(v["spd"]), _p(v["path"]), _p(v["rel_pos"]),
-                                         _p(v["edge_input"]), _p(v["in_degree"]), _p(v["out_degree"]), _p(work), G, N, self.D,
-                                         _stream()), "mobgt_spd_batched")
+        _lib.call("mobgt_spd_batched", _p(v["counts"]), _p(v["n_nodes"]), _p(v["spd"]), _p(v["path"]), _p(v["rel_pos"]),
+                  _p(v["edge_input"]), _p(v["in_degree"]), _p(v["out_degree"]), _p(work), G, N, self.D,
+                  _stream())
         bt = self.bin_table
-        _lib.check(lib.mobgt_collate_finish(_p(v["x"]), _p(v["n_nodes"]), _p(v["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
-                                            self.rel_pos_max, _p(v["attn_bias"]), _p(v["poi_pos"]), G, N, _stream()),
-                   "mobgt_collate_finish")
+        _lib.call("mobgt_collate_finish", _p(v["x"]), _p(v["n_nodes"]), _p(v["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
+                  self.rel_pos_max, _p(v["attn_bias"]), _p(v["poi_pos"]), G, N, _stream())
         return work
 
     @staticmethod
@@ -174,9 +173,8 @@ class DeviceCollator:
             attn_bias = torch.empty(G, T, T, device=self.device)
             poi_pos = torch.empty(G, N, N, dtype=torch.int16, device=self.device)
             bt = self.bin_table
-            _lib.check(_lib.lib().mobgt_collate_finish(_p(x), _p(n_nodes), _p(sp["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
-                                                       self.rel_pos_max, _p(attn_bias), _p(poi_pos), G, N, _stream()),
-                       "mobgt_collate_finish")
+            _lib.call("mobgt_collate_finish", _p(x), _p(n_nodes), _p(sp["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
+                      self.rel_pos_max, _p(attn_bias), _p(poi_pos), G, N, _stream())
             return DeviceBatch1(counts, n_nodes, idx=d["idx"], attn_bias=attn_bias, rel_pos=sp["rel_pos"],
                                 in_degree=sp["in_degree"], out_degree=sp["out_degree"], x=x, edge_input=sp["edge_input"],
                                 y=d["y"], time=d["time"], time_normal=d["time_normal"], user=d["user"], cat=d["cat"],

@@ -15,7 +15,6 @@ import ctypes
 import torch
 
 from . import _lib, forms, ops
-from ._lib import check
 from .ops import _p, _stream, _DT
 
 
@@ -88,13 +87,12 @@ class _WgradBatch:
             a, w, c = tail
             if (a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and c.dtype == torch.float32 and a.shape[1] % 32 == 0
                     and w.shape[1] % 8 == 0 and a.is_contiguous() and w.is_contiguous() and c.is_contiguous()):
-                check(_lib.lib().mobgt_layer_backward_tail(n, garr, ldg, xarr, ldx, warr, ldw, barr, R, M, N, _DT[it[0][0].dtype],
-                                                           _p(a), a.stride(0), _p(w), w.stride(0), _p(c), c.stride(0),
-                                                           a.shape[0], w.shape[1], a.shape[1], _stream()),
-                      "mobgt_layer_backward_tail")
+                _lib.call("mobgt_layer_backward_tail", n, garr, ldg, xarr, ldx, warr, ldw, barr, R, M, N, _DT[it[0][0].dtype],
+                          _p(a), a.stride(0), _p(w), w.stride(0), _p(c), c.stride(0),
+                          a.shape[0], w.shape[1], a.shape[1], _stream())
                 return True
-        check(_lib.lib().mobgt_linear_wgrad_group(n, garr, ldg, xarr, ldx, warr, ldw, barr, R, M, N, _DT[it[0][0].dtype],
-                                                  _stream()), "mobgt_linear_wgrad_group")
+        _lib.call("mobgt_linear_wgrad_group", n, garr, ldg, xarr, ldx, warr, ldw, barr, R, M, N, _DT[it[0][0].dtype],
+                  _stream())
         return False
 
 
@@ -105,7 +103,7 @@ def _wgrad(g, x, db=None, sink=None):
     if _wgrad_hip(g.dtype, g.shape[1], x.shape[1], g.shape[0]):
         return ops.linear_wgrad(g, x, db=db)[0]
     if db is not None:
-        check(_lib.lib().mobgt_colsum(_p(g), _p(db), g.shape[0], g.shape[1], _DT[g.dtype], _stream()), "mobgt_colsum")
+        _lib.call("mobgt_colsum", _p(g), _p(db), g.shape[0], g.shape[1], _DT[g.dtype], _stream())
     return _mm_tn_f32(g, x, sink=sink)
 
 
@@ -172,8 +170,8 @@ def _addmm_f32(c, a, b, inplace=False):
 
 
 def _k1_fwd(x, y, x1, w, b, z, z32, mean, rstd, R, C, p, seed, seed_dev, salt, act):
-    check(_lib.lib().mobgt_dropout_add_ln_fwd(_p(x), _p(y), _p(x1), _p(w), _p(b), _p(z), _p(z32), _p(mean), _p(rstd), R, C,
-                                              p, seed, _p(seed_dev), salt, act, _stream()), "mobgt_dropout_add_ln_fwd")
+    _lib.call("mobgt_dropout_add_ln_fwd", _p(x), _p(y), _p(x1), _p(w), _p(b), _p(z), _p(z32), _p(mean), _p(rstd), R, C,
+              p, seed, _p(seed_dev), salt, act, _stream())
 
 
 # forms "ln_gemm" / "ln_gemm_bwd" (csrc/lngemm.hip).  Measured on the S-FSQ step (608 rows, C = 192), kernel durations inside the replayed graph:
@@ -296,9 +294,9 @@ def _ln_gemm_fwd(x, y, x1, w, b, z, mean, rstd, R, C, p, seed, seed_dev, salt, w
     N = weight.shape[0]
     out = torch.empty(R, N, dtype=torch.bfloat16, device=x.device)
     aux = torch.empty(R, N, dtype=torch.bfloat16, device=x.device) if epilogue == ops.GEMM_GELU else None
-    check(_lib.lib().mobgt_ln_gemm_fwd(_p(x), _p(y), _p(x1), _p(w), _p(b), _p(z), _p(mean), _p(rstd), R, C, p, seed,
-                                       _p(seed_dev), salt, _p(weight), weight.stride(0), _p(bias), _p(out), N, epilogue,
-                                       _p(aux), N, _stream()), "mobgt_ln_gemm_fwd")
+    _lib.call("mobgt_ln_gemm_fwd", _p(x), _p(y), _p(x1), _p(w), _p(b), _p(z), _p(mean), _p(rstd), R, C, p, seed,
+              _p(seed_dev), salt, _p(weight), weight.stride(0), _p(bias), _p(out), N, epilogue,
+              _p(aux), N, _stream())
     return (out, aux) if aux is not None else out
 
 
@@ -307,17 +305,16 @@ def _ln_gemm_bwd(dz, dz32, dres, x1, mean, rstd, w, dx1, dy, dgamma, dbeta, dbia
     """dx1 = dres + LayerNorm'(dz + dz32); dy = dropout'(dx1); out = dy @ weight_kn [* gelu'(aux_in)] in ONE launch."""
     N = weight_kn.shape[1]
     out = torch.empty(R, N, dtype=torch.bfloat16, device=x1.device)
-    check(_lib.lib().mobgt_ln_gemm_bwd(_p(dz), _p(dz32), _p(dres), _p(x1), _p(mean), _p(rstd), _p(w), _p(dx1), _p(dy),
-                                       _p(dgamma), _p(dbeta), _p(dbias), R, C, p, seed, _p(seed_dev), salt, _p(weight_kn),
-                                       weight_kn.stride(0), _p(out), N, epilogue, _p(aux_in), N, _stream()),
-          "mobgt_ln_gemm_bwd")
+    _lib.call("mobgt_ln_gemm_bwd", _p(dz), _p(dz32), _p(dres), _p(x1), _p(mean), _p(rstd), _p(w), _p(dx1), _p(dy),
+              _p(dgamma), _p(dbeta), _p(dbias), R, C, p, seed, _p(seed_dev), salt, _p(weight_kn),
+              weight_kn.stride(0), _p(out), N, epilogue, _p(aux_in), N, _stream())
     return out
 
 
 def _k1_bwd(dz, dz32, dres, x1, mean, rstd, w, dx1, dy, dgamma, dbeta, dbias, R, C, p, seed, seed_dev, salt, act):
-    check(_lib.lib().mobgt_dropout_add_ln_bwd(_p(dz), _p(dz32), _p(dres), _p(x1), _p(mean), _p(rstd), _p(w), _p(dx1), _p(dy),
-                                              _p(dgamma), _p(dbeta), _p(dbias), R, C, p, seed, _p(seed_dev), salt, act,
-                                              _stream()), "mobgt_dropout_add_ln_bwd")
+    _lib.call("mobgt_dropout_add_ln_bwd", _p(dz), _p(dz32), _p(dres), _p(x1), _p(mean), _p(rstd), _p(w), _p(dx1), _p(dy),
+              _p(dgamma), _p(dbeta), _p(dbias), R, C, p, seed, _p(seed_dev), salt, act,
+              _stream())
 
 
 class LayerConfig:
@@ -433,12 +430,12 @@ class _FusedLayerFn(torch.autograd.Function):
                 nq = None
             qkv_next = torch.empty(R, 3 * C, **bf) if nq is not None else None
             p_wo, p_w1, p_w2 = cfg.packed
-            check(_lib.lib().mobgt_layer_chain_fwd(_p(a), _p(x), _p(p_wo), _p(s_bo), _p(n1w), _p(n1b), _p(p_w1), _p(s_b1), _p(p_w2),
-                                                   _p(s_b2), _p(nxw), _p(nxb), _p(nq[0] if nq else None),
-                                                   _p(nq[1] if nq else None), _p(x1), _p(z), _p(u), _p(h), _p(x2), _p(out),
-                                                   _p(out_a), _p(qkv_next), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                                                   _p(stats[5]), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                                                   (salt + 2) & 0xFFFFFFFF, _p(chain_workspace(dev, C, R)), _stream()), "mobgt_layer_chain_fwd")
+            _lib.call("mobgt_layer_chain_fwd", _p(a), _p(x), _p(p_wo), _p(s_bo), _p(n1w), _p(n1b), _p(p_w1), _p(s_b1), _p(p_w2),
+                      _p(s_b2), _p(nxw), _p(nxb), _p(nq[0] if nq else None),
+                      _p(nq[1] if nq else None), _p(x1), _p(z), _p(u), _p(h), _p(x2), _p(out),
+                      _p(out_a), _p(qkv_next), _p(stats[2]), _p(stats[3]), _p(stats[4]),
+                      _p(stats[5]), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
+                      (salt + 2) & 0xFFFFFFFF, _p(chain_workspace(dev, C, R)), _stream())
             cfg.out_act, cfg.out_qkv = out_a, qkv_next
         elif stock_chain:
             bf = dict(dtype=A, device=dev)
@@ -453,12 +450,12 @@ class _FusedLayerFn(torch.autograd.Function):
             out_a = torch.empty(R, C, **bf) if nq is not None else None
             qkv_next = torch.empty(R, 3 * C, **bf) if nq is not None else None
             p_wo, p_w1, p_w2 = cfg.packed
-            check(_lib.lib().mobgt_layer_chain_fwd(_p(a), _p(x), _p(p_wo), _p(s_bo), _p(n1w), _p(n1b), _p(p_w1), _p(s_b1), _p(p_w2),
-                                                   _p(s_b2), _p(nnw if nq is not None else None), _p(nnb if nq is not None else None),
-                                                   _p(nq[0] if nq else None), _p(nq[1] if nq else None), _p(x1), _p(z), _p(u), _p(h),
-                                                   _p(x2), _p(None), _p(out_a), _p(qkv_next), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                                                   _p(stats[5]), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                                                   (salt + 2) & 0xFFFFFFFF, _p(chain_workspace(dev, C, R)), _stream()), "mobgt_layer_chain_fwd")
+            _lib.call("mobgt_layer_chain_fwd", _p(a), _p(x), _p(p_wo), _p(s_bo), _p(n1w), _p(n1b), _p(p_w1), _p(s_b1), _p(p_w2),
+                      _p(s_b2), _p(nnw if nq is not None else None), _p(nnb if nq is not None else None),
+                      _p(nq[0] if nq else None), _p(nq[1] if nq else None), _p(x1), _p(z), _p(u), _p(h),
+                      _p(x2), _p(None), _p(out_a), _p(qkv_next), _p(stats[2]), _p(stats[3]), _p(stats[4]),
+                      _p(stats[5]), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
+                      (salt + 2) & 0xFFFFFFFF, _p(chain_workspace(dev, C, R)), _stream())
             out = x2                                                  # the residual stream passes the next layer's norm by
             if nq is not None:
                 cfg.out_act, cfg.out_qkv, cfg.out_preln = out_a, qkv_next, True
@@ -515,7 +512,7 @@ class _FusedLayerFn(torch.autograd.Function):
             _k1_fwd(x, y, x1, n1w, n1b, z, None, stats[2], stats[3], R, C, cfg.p, seed, sd, salt + 1, act)
             u = torch.addmm(s_b1, z, s_w1.t())
             h = torch.empty_like(u)
-            check(_lib.lib().mobgt_gelu_fwd(_p(u), _p(h), u.numel(), act, _stream()), "mobgt_gelu_fwd")
+            _lib.call("mobgt_gelu_fwd", _p(u), _p(h), u.numel(), act, _stream())
             f = torch.addmm(s_b2, h, s_w2.t())
         x2 = torch.empty(R, C, **f32)
         if stock:                                                     # x = x + dropout(ffn(...))  (model.py:485-488)
@@ -557,8 +554,8 @@ class _FusedLayerFn(torch.autograd.Function):
         else:
             dh = df @ s_w2
             du = torch.empty_like(u)
-            check(_lib.lib().mobgt_gelu_bwd_colsum(_p(dh), _p(u), _p(du), _p(None if db1_in_wgrad else db1), R, F, act,
-                                                   _stream()), "mobgt_gelu_bwd_colsum")
+            _lib.call("mobgt_gelu_bwd_colsum", _p(dh), _p(u), _p(du), _p(None if db1_in_wgrad else db1), R, F, act,
+                      _stream())
         dz = ops.layer_gemm(du, s_w1, None, True) if own else du @ s_w1
         dw1 = wb.add(du, z, db=db1 if db1_in_wgrad else None, sink=k_w1)
         dx1 = torch.empty(R, C, dtype=torch.float32, device=dev)
@@ -638,22 +635,21 @@ class _FusedLayerFn(torch.autograd.Function):
             if R > 4096 and (pend is None or not pend["items"]):
                 # the 64-row form: b1's gradient is summed inside (db1 is zero-filled: `small`); it hosts the upper layer's tail
                 # (dout = that layer's dx1; dout + dqkv Wqkv is finished in front of the first norm), not its weight gradients
-                check(_lib.lib().mobgt_layer_chain_bwd_big(_p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                                                           _p(stats[5]), _p(n1w), _p(nxw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
-                                                           _p(dy), _p(da), _p(dx1), _p(dnxw), _p(dnxb), _p(db2), _p(dn1w), _p(dn1b),
-                                                           _p(dbo), _p(None if db1_in_wgrad else db1), R, C, F, cfg.p, seed, _p(sd),
-                                                           (salt + 1) & 0xFFFFFFFF, (salt + 2) & 0xFFFFFFFF,
-                                                           _p(pend["dqkv"]) if pend is not None else None,
-                                                           _p(pend["wqt"]) if pend is not None else None, _stream()),
-                      "mobgt_layer_chain_bwd_big")
+                _lib.call("mobgt_layer_chain_bwd_big", _p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
+                          _p(stats[5]), _p(n1w), _p(nxw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
+                          _p(dy), _p(da), _p(dx1), _p(dnxw), _p(dnxb), _p(db2), _p(dn1w), _p(dn1b),
+                          _p(dbo), _p(None if db1_in_wgrad else db1), R, C, F, cfg.p, seed, _p(sd),
+                          (salt + 1) & 0xFFFFFFFF, (salt + 2) & 0xFFFFFFFF,
+                          _p(pend["dqkv"]) if pend is not None else None,
+                          _p(pend["wqt"]) if pend is not None else None, _stream())
             else:
-                check(_lib.lib().mobgt_layer_chain_bwd(_p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                                                       _p(stats[5]), _p(n1w), _p(nxw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
-                                                       _p(dy), _p(da), _p(dx1), _p(dnxw), _p(dnxb), _p(db2), _p(dn1w), _p(dn1b),
-                                                       _p(dbo), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                                                       (salt + 2) & 0xFFFFFFFF, *extra, _p(chain_workspace(dev, C, R)), _stream()), "mobgt_layer_chain_bwd")
+                _lib.call("mobgt_layer_chain_bwd", _p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
+                          _p(stats[5]), _p(n1w), _p(nxw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
+                          _p(dy), _p(da), _p(dx1), _p(dnxw), _p(dnxb), _p(db2), _p(dn1w), _p(dn1b),
+                          _p(dbo), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
+                          (salt + 2) & 0xFFFFFFFF, *extra, _p(chain_workspace(dev, C, R)), _stream())
                 if not db1_in_wgrad:
-                    check(_lib.lib().mobgt_colsum(_p(du), _p(db1), R, F, act, _stream()), "mobgt_colsum")
+                    _lib.call("mobgt_colsum", _p(du), _p(db1), R, F, act, _stream())
             da = da.view(G, T, C)
             big_items = None
             if R > 4096 and forms.on("wgrad_big") and A == torch.bfloat16 and not db1_in_wgrad:
@@ -781,12 +777,12 @@ class _FusedLayerFn(torch.autograd.Function):
         dx1 = torch.empty(R, C, dtype=torch.float32, device=dev)
         w2t, w1t, wot = cfg.packed_t[:3]
         tail = (_p(pend["dqkv"]), _p(pend["wqt"])) if pend is not None else (None, None)
-        check(_lib.lib().mobgt_layer_chain_bwd_preln(_p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                                                     _p(stats[5]), _p(n1w), _p(nnw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
-                                                     _p(dy), _p(da), _p(dx1), _p(dnnw), _p(dnnb), _p(db2), _p(dn1w), _p(dn1b),
-                                                     _p(dbo), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                                                     (salt + 2) & 0xFFFFFFFF, *tail, 0, None, None, None, None, None, None, None,
-                                                     None, None, _p(chain_workspace(dev, C, R)), _stream()), "mobgt_layer_chain_bwd_preln")
+        _lib.call("mobgt_layer_chain_bwd_preln", _p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
+                  _p(stats[5]), _p(n1w), _p(nnw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
+                  _p(dy), _p(da), _p(dx1), _p(dnnw), _p(dnnb), _p(db2), _p(dn1w), _p(dn1b),
+                  _p(dbo), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
+                  (salt + 2) & 0xFFFFFFFF, *tail, 0, None, None, None, None, None, None, None,
+                  None, None, _p(chain_workspace(dev, C, R)), _stream())
         dw2 = wb.add(df, h, sink=k_w2)
         dw1 = wb.add(du, z, db=db1, sink=k_w1)
         dwo = wb.add(dy, a.view(R, C), sink=k_wo)

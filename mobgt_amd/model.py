@@ -303,9 +303,9 @@ def _launch_pack(jobs):
         part = jobs[o:o + 96]
         n = len(part)
         vp, ci = ctypes.c_void_p, ctypes.c_int
-        _lib.check(_lib.lib().mobgt_pack_mfma_b(n, (vp * n)(*[j[0].data_ptr() for j in part]), (vp * n)(*[j[1].data_ptr() for j in part]),
-                                                (ci * n)(*[j[2] for j in part]), (ci * n)(*[j[3] for j in part]),
-                                                (ci * n)(*[j[4] for j in part]), _stream()), "mobgt_pack_mfma_b")
+        _lib.call("mobgt_pack_mfma_b", n, (vp * n)(*[j[0].data_ptr() for j in part]), (vp * n)(*[j[1].data_ptr() for j in part]),
+                  (ci * n)(*[j[2] for j in part]), (ci * n)(*[j[3] for j in part]),
+                  (ci * n)(*[j[4] for j in part]), _stream())
 
 
 class _PendingBackward:

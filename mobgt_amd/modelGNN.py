@@ -130,8 +130,8 @@ class _RowsConvFn(torch.autograd.Function):
             # the f32 gradient as it arrives: rounded to bf16 while loading, bias gradient = its column sums, one launch
             d_support = ops.zeros_f32((P, C), g.device)
             db = (ctx.sinks[1][:] if ctx.sinks[1] is not None else ops.zeros_f32((C,), g.device)) if ctx.has_bias else None
-            _lib.check(_lib.lib().mobgt_linear_wgrad_mixed(_p(a_rows), a_rows.stride(0), _p(g), g.stride(0), _p(d_support), C,
-                                                           _p(db), R, P, C, _stream()), "mobgt_linear_wgrad_mixed")
+            _lib.call("mobgt_linear_wgrad_mixed", _p(a_rows), a_rows.stride(0), _p(g), g.stride(0), _p(d_support), C,
+                      _p(db), R, P, C, _stream())
         else:
             d_support = ops.linear_wgrad(a_rows, g.to(torch.bfloat16).contiguous())[0]      # [P,C] f32
             db = _colsum(g) if ctx.has_bias else None
@@ -199,16 +199,16 @@ def mask_gemm(adj, x, transposed=False, bias=None, xt=None):
     if xt is not None:
         N, P = xt.shape[0], adj.scale.numel()
         out = torch.empty(P, N, dtype=torch.float32, device=xt.device)
-        _lib.check(_lib.lib().mobgt_mask_gemm(_p(mask), mask.shape[1], None, 0, None, _p(None if transposed else adj.scale),
-                                              _p(bias), _p(out), N, _p(xt), P, P, N, _stream()), "mobgt_mask_gemm")
+        _lib.call("mobgt_mask_gemm", _p(mask), mask.shape[1], None, 0, None, _p(None if transposed else adj.scale),
+                  _p(bias), _p(out), N, _p(xt), P, P, N, _stream())
         return out
     x = x.contiguous()
     P, N = x.shape
     out = torch.empty(P, N, dtype=torch.float32, device=x.device)
     work = torch.empty(int(_lib.lib().mobgt_mask_gemm_workspace_bytes(P, N)), dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.lib().mobgt_mask_gemm(_p(mask), mask.shape[1], _p(x), x.stride(0), _p(adj.scale if transposed else None),
-                                          _p(None if transposed else adj.scale), _p(bias), _p(out), N, _p(work), P, P, N,
-                                          _stream()), "mobgt_mask_gemm")
+    _lib.call("mobgt_mask_gemm", _p(mask), mask.shape[1], _p(x), x.stride(0), _p(adj.scale if transposed else None),
+              _p(None if transposed else adj.scale), _p(bias), _p(out), N, _p(work), P, P, N,
+              _stream())
     return out
 
 
@@ -333,8 +333,8 @@ def spmm(adj, b, bias=None, rows=None, transposed=False):
     R = rows.numel() if rows is not None else rp.numel() - 1
     C = b.shape[1]
     out = torch.empty(R, C, dtype=torch.float32, device=b.device)
-    _lib.check(_lib.lib().mobgt_spmm_csr(_p(rp), _p(col), _p(val), _p(rows), _p(b), b.stride(0), _p(bias), _p(out), C, R, C,
-                                         _stream()), "mobgt_spmm_csr")
+    _lib.call("mobgt_spmm_csr", _p(rp), _p(col), _p(val), _p(rows), _p(b), b.stride(0), _p(bias), _p(out), C, R, C,
+              _stream())
     return out
 
 
@@ -370,15 +370,14 @@ class _SpConvFn(torch.autograd.Function):
                 head = adj._rows_head = torch.full((adj.shape[0],), -1, dtype=torch.int32, device=g.device)
             nxt = torch.empty(rows.numel(), dtype=torch.int32, device=g.device)
             d_support = torch.empty(P, g.shape[1], dtype=torch.float32, device=g.device)
-            _lib.check(_lib.lib().mobgt_spmm_csr_t_rows_gather(_p(adj.t_rowptr), _p(adj.t_col), _p(adj.t_val), _p(rows), _p(head),
-                                                               _p(nxt), _p(g), g.stride(0), _p(d_support), d_support.stride(0),
-                                                               P, rows.numel(), g.shape[1], _stream()),
-                       "mobgt_spmm_csr_t_rows_gather")
+            _lib.call("mobgt_spmm_csr_t_rows_gather", _p(adj.t_rowptr), _p(adj.t_col), _p(adj.t_val), _p(rows), _p(head),
+                      _p(nxt), _p(g), g.stride(0), _p(d_support), d_support.stride(0),
+                      P, rows.numel(), g.shape[1], _stream())
         else:                                                           # adj[rows]^T @ g: scatter of R rows
             d_support = torch.zeros(adj.shape[1], g.shape[1], dtype=torch.float32, device=g.device)
-            _lib.check(_lib.lib().mobgt_spmm_csr_t_rows(_p(adj.rowptr), _p(adj.col), _p(adj.val), _p(rows), _p(g), g.stride(0),
-                                                        _p(d_support), d_support.stride(0), rows.numel(), g.shape[1],
-                                                        _stream()), "mobgt_spmm_csr_t_rows")
+            _lib.call("mobgt_spmm_csr_t_rows", _p(adj.rowptr), _p(adj.col), _p(adj.val), _p(rows), _p(g), g.stride(0),
+                      _p(d_support), d_support.stride(0), rows.numel(), g.shape[1],
+                      _stream())
         dW = mm_tn_splitk(x, d_support, bf16_operands=True, dw=ctx.sinks[0][:] if ctx.sinks[0] is not None else None)
         dx = _mm_small(d_support, weight, True) if ctx.needs_input_grad[0] else None
         db = _colsum(g) if ctx.has_bias else None
@@ -475,9 +474,9 @@ def _small_gcn_launch(ax, a, ws, slope, p_drop, seed, seed_dev, salt):
     hop, ni = ops.take_front_jobs()
     front = ([1] + ni[0] if ni is not None else [0, None, 0, 0, 0, None, 0, 0, None, None, None, 0, None, None, 0, 0, 0]) + \
             ([1] + hop[0] if hop is not None else [0, None, None, None, 0, 0, 0, 0])
-    _lib.check(_lib.lib().mobgt_small_gcn_fwd_pack(_p(ax), _p(a), *[_p(w) for w in ws], _p(h1), _p(t), _p(h2), _p(t2), _p(out),
-                                                   _p(counter), n, K0, H1, H2, H3, slope, p_drop, seed, _p(seed_dev), salt,
-                                                   nj, *pack, *front, _stream()), "mobgt_small_gcn_fwd_pack")
+    _lib.call("mobgt_small_gcn_fwd_pack", _p(ax), _p(a), *[_p(w) for w in ws], _p(h1), _p(t), _p(h2), _p(t2), _p(out),
+              _p(counter), n, K0, H1, H2, H3, slope, p_drop, seed, _p(seed_dev), salt,
+              nj, *pack, *front, _stream())
     return keep, out
 
 
@@ -544,10 +543,10 @@ class _SmallGcnFn(torch.autograd.Function):
             extra = [1] + bias_args
         else:
             extra = [0, None, 0, 1, 0] + [None] * 8 + [0] * 9 + [0, 0, 0]
-        _lib.check(_lib.lib().mobgt_small_gcn_bwd_bias(_p(g.contiguous()), _p(ax), _p(a_t), _p(w1), _p(w2), _p(h1), _p(t), _p(h2),
-                                                       _p(t2), *[_p(x) for x in grads], _p(scratch[n * H1:]), _p(scratch[:n * H1]),
-                                                       _p(counter), n, K0, H1, H2, H3, slope, p_drop, seed, _p(seed_dev), salt,
-                                                       *extra, _stream()), "mobgt_small_gcn_bwd_bias")
+        _lib.call("mobgt_small_gcn_bwd_bias", _p(g.contiguous()), _p(ax), _p(a_t), _p(w1), _p(w2), _p(h1), _p(t), _p(h2),
+                  _p(t2), *[_p(x) for x in grads], _p(scratch[n * H1:]), _p(scratch[:n * H1]),
+                  _p(counter), n, K0, H1, H2, H3, slope, p_drop, seed, _p(seed_dev), salt,
+                  *extra, _stream())
         if job is not None:
             job["done"] = outs
         return (None, None, None, *grads, None, None, None, None, None, None)
@@ -581,12 +580,11 @@ class _DistGcnFn(torch.autograd.Function):
         u = torch.empty(R, 64, dtype=torch.float32, device=dev)
         parts = torch.empty(4, R, NO, dtype=torch.float32, device=dev)                # out = parts[0] + parts[1] + parts[2] + parts[3]
         rs_rows = torch.empty(R, dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        _lib.check(L.mobgt_mask_gemm_l1_fwd(_p(mask), mask.shape[1], _p(scale), _p(y0t), y0t.stride(0), _p(t1), _p(w1), _p(b1),
-                                            float(slope), float(p_drop), int(seed), _p(seed_dev), int(salt) & 0xFFFFFFFF, _p(y1),
-                                            _p(y1t), y1t.stride(0), None, 0, P, P, _stream()), "mobgt_mask_gemm_l1_fwd")
-        _lib.check(L.mobgt_mask_rows_fwd(_p(mask), mask.shape[1], _p(rows), _p(scale), _p(y1t), y1t.stride(0), _p(w2), _p(b2),
-                                         _p(u), _p(parts), _p(rs_rows), R, P, NO, _stream()), "mobgt_mask_rows_fwd")
+        _lib.call("mobgt_mask_gemm_l1_fwd", _p(mask), mask.shape[1], _p(scale), _p(y0t), y0t.stride(0), _p(t1), _p(w1), _p(b1),
+                  float(slope), float(p_drop), int(seed), _p(seed_dev), int(salt) & 0xFFFFFFFF, _p(y1),
+                  _p(y1t), y1t.stride(0), None, 0, P, P, _stream())
+        _lib.call("mobgt_mask_rows_fwd", _p(mask), mask.shape[1], _p(rows), _p(scale), _p(y1t), y1t.stride(0), _p(w2), _p(b2),
+                  _p(u), _p(parts), _p(rs_rows), R, P, NO, _stream())
         ctx.save_for_backward(ax_pad, y0, t1, y1, u, rs_rows, rows, w0, w1, w2, mask_t, scale)
         ctx.mv0, ctx.mv1 = ops.act_mask_values(slope, 0.0), ops.act_mask_values(slope, p_drop)
         ctx.sinks = tuple(ops.grad_sink(t) for t in (w0, b0, w1, b1, w2, b2))
@@ -617,9 +615,9 @@ class _DistGcnFn(torch.autograd.Function):
         ops.small_gemm(g, w2, b_is_nk=True, ct=(gut, rs_rows, True))                 # (rs[rows] * (g W2^T))^T, bf16
         dy1 = torch.empty(P, 64, dtype=torch.float32, device=dev)
         dtt = xt_workspace(dev, P, 16, slot=1)
-        _lib.check(_lib.lib().mobgt_mask_rows_bwd(_p(mask_t), mask_t.shape[1], _p(rows), _p(gut), gut.stride(0), _p(y1),
-                                                  float(ctx.mv1[0]), float(ctx.mv1[1]), float(ctx.mv1[2]), _p(w1), _p(scale), _p(dy1),
-                                                  _p(dtt), dtt.stride(0), R, P, _stream()), "mobgt_mask_rows_bwd")
+        _lib.call("mobgt_mask_rows_bwd", _p(mask_t), mask_t.shape[1], _p(rows), _p(gut), gut.stride(0), _p(y1),
+                  float(ctx.mv1[0]), float(ctx.mv1[1]), float(ctx.mv1[2]), _p(w1), _p(scale), _p(dy1),
+                  _p(dtt), dtt.stride(0), R, P, _stream())
         db1 = dst(k_b1, 64)
         dW1 = ops.linear_wgrad_masked(t1, dy1, x_mask=y1, mask_vals=ctx.mv1, db=db1, db_of_x=True, leaf=True,
                                       dw=k_w1[:] if k_w1 is not None else None)

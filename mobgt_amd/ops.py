@@ -77,7 +77,7 @@ def peer_wait_faults(reset=True):
                 w.zero_()
                 _scrub_exchange_area(ws, off)
     c = ctypes.c_uint32(0)
-    check(lib.mobgt_small_gcn_faults(1 if reset else 0, ctypes.byref(c)), "mobgt_small_gcn_faults")
+    _lib.call("mobgt_small_gcn_faults", 1 if reset else 0, ctypes.byref(c))
     if c.value:
         out["small_gcn"] = int(c.value)
     return out
@@ -97,7 +97,7 @@ def set_peer_wait_limit(rounds=0, gcn_ticks=0):
     ws = _HEAD_WS.get(dev)
     if ws is not None:
         _ws_word(ws, int(lib.mobgt_head_chain_ws_limit_offset())).fill_(int(rounds))
-    check(lib.mobgt_small_gcn_set_wait_limit(int(gcn_ticks)), "mobgt_small_gcn_set_wait_limit")
+    _lib.call("mobgt_small_gcn_set_wait_limit", int(gcn_ticks))
     torch.cuda.synchronize()
 
 
@@ -270,8 +270,8 @@ class _PackFn(torch.autograd.Function):
         G, H, T = pack.G, pack.H, pack.T
         s = src.expand(G, H, T, T)
         st = s.stride()
-        check(_lib.lib().mobgt_bias_pack(_p(s), _DT[s.dtype], st[0], st[1], st[2], st[3], _p(pack.bias), _p(pack.bias_t),
-                                         _DT[pack.dtype], G, H, T, pack.ld, _stream()), "mobgt_bias_pack")
+        _lib.call("mobgt_bias_pack", _p(s), _DT[s.dtype], st[0], st[1], st[2], st[3], _p(pack.bias), _p(pack.bias_t),
+                  _DT[pack.dtype], G, H, T, pack.ld, _stream())
         ctx.pack = pack
         ctx.src_shape = src.shape
         ctx.src_dtype = src.dtype
@@ -332,9 +332,9 @@ def take_front_jobs():
 def flush_front():
     hop, ni = take_front_jobs()
     if hop is not None:
-        check(_lib.lib().mobgt_hop_table_fwd(*hop[0], _stream()), "mobgt_hop_table_fwd")
+        _lib.call("mobgt_hop_table_fwd", *hop[0], _stream())
     if ni is not None:
-        check(_lib.lib().mobgt_node_index(*ni[0], _stream()), "mobgt_node_index")
+        _lib.call("mobgt_node_index", *ni[0], _stream())
 
 
 def _bias_bwd_alloc(shapes, dev, sinks=(None, None, None, None)):
@@ -385,9 +385,9 @@ class _BuildBiasFn(torch.autograd.Function):
         n_poi = poi_table.shape[0] if poi_table is not None else 0
         n_edge = hop_table.shape[1] if has_edge else 0
         args = (G, N, H, D_in, D if has_edge else 0, F, rel_table.shape[0], n_poi, n_edge, pack.ld, idx_dt, edge_dt)
-        check(_lib.lib().mobgt_build_bias(_p(attn_bias), _p(rel_pos), _p(poi_pos), _p(edge_input if has_edge else None), _p(rel_table),
-                                          _p(poi_table), _p(hop_table if has_edge else None), _p(vdist), _p(pack.bias), _p(pack.bias_t),
-                                          *args, _DT[pack.dtype], _stream()), "mobgt_build_bias")
+        _lib.call("mobgt_build_bias", _p(attn_bias), _p(rel_pos), _p(poi_pos), _p(edge_input if has_edge else None), _p(rel_table),
+                  _p(poi_table), _p(hop_table if has_edge else None), _p(vdist), _p(pack.bias), _p(pack.bias_t),
+                  *args, _DT[pack.dtype], _stream())
         ctx.pack, ctx.args = pack, args
         ctx.set_materialize_grads(False)          # the token carries no gradient: no zero-fill launch to materialise one
         ctx.idx = (attn_bias, rel_pos, poi_pos, edge_input if has_edge else None)
@@ -420,10 +420,9 @@ class _BuildBiasFn(torch.autograd.Function):
             a = ctx.args
             n_sl = max(pack.n_bwd, 1) if pack.sliced else 1
             stride = pack.dbias.stride(0) if pack.sliced else 0
-            check(_lib.lib().mobgt_build_bias_bwd(_p(pack.dbias), _DT[pack.dbias.dtype], n_sl, stride,
-                                                  _p(attn_bias), _p(rel_pos), _p(poi_pos), _p(edge_input),
-                                                  _p(d_rel), _p(d_poi), _p(d_hop), _p(d_vd), *a, _stream()),
-                  "mobgt_build_bias_bwd")
+            _lib.call("mobgt_build_bias_bwd", _p(pack.dbias), _DT[pack.dbias.dtype], n_sl, stride,
+                      _p(attn_bias), _p(rel_pos), _p(poi_pos), _p(edge_input),
+                      _p(d_rel), _p(d_poi), _p(d_hop), _p(d_vd), *a, _stream())
         return d_rel, d_poi, d_hop, d_vd, None, None, None, None, None, None, None
 
 
@@ -492,9 +491,9 @@ def _attn_fwd(q, k, v, pack, scale, p_drop, seed, seed_dev):
     _check_rows(q, k, v)
     if pack.needs_grad:
         pack.n_use += 1
-    check(_lib.lib().mobgt_attn_bias_fwd(_p(q), _p(k), _p(v), _p(pack.bias), _p(out), _out_lo_ptr(lse, G, H, T, q.dtype), _p(lse), G, H, T, C // H,
-                                         q.stride(1), k.stride(1), v.stride(1), C, pack.ld, scale, p_drop, seed,
-                                         _p(seed_dev), _DT[q.dtype], _DT[pack.dtype], _stream()), "mobgt_attn_bias_fwd")
+    _lib.call("mobgt_attn_bias_fwd", _p(q), _p(k), _p(v), _p(pack.bias), _p(out), _out_lo_ptr(lse, G, H, T, q.dtype), _p(lse), G, H, T, C // H,
+              q.stride(1), k.stride(1), v.stride(1), C, pack.ld, scale, p_drop, seed,
+              _p(seed_dev), _DT[q.dtype], _DT[pack.dtype], _stream())
     return out, lse
 
 
@@ -538,11 +537,11 @@ def _attn_bwd(q, k, v, out, lse, dout, dq, dk, dv, pack, scale, p_drop, seed, se
                 _DQ_ACC_RETIRED.append(ent["buf"])
             ent = _DQ_ACC[key] = dict(buf=torch.zeros(G * T * C, dtype=torch.float32, device=q.device), busy=False)
         ent["busy"] = True
-        check(_lib.lib().mobgt_attn_bias_bwd_fused_z(*args, _p(ent["buf"]), _stream()), "mobgt_attn_bias_bwd_fused_z")
+        _lib.call("mobgt_attn_bias_bwd_fused_z", *args, _p(ent["buf"]), _stream())
         ent["busy"] = False
         _bias_bwd_beside(pack)
         return
-    check(_lib.lib().mobgt_attn_bias_bwd(*args, _stream()), "mobgt_attn_bias_bwd")
+    _lib.call("mobgt_attn_bias_bwd", *args, _stream())
     _bias_bwd_beside(pack)
 
 
@@ -581,7 +580,7 @@ def _bias_bwd_beside(pack):
     lib = _lib.lib()
     lib.mobgt_build_bias_bwd_set_workgroups(max(1, cus * 3 // 4))
     try:
-        check(lib.mobgt_build_bias_bwd(*args, ctypes.c_void_p(side.cuda_stream)), "mobgt_build_bias_bwd")
+        _lib.call("mobgt_build_bias_bwd", *args, ctypes.c_void_p(side.cuda_stream))
     finally:
         lib.mobgt_build_bias_bwd_set_workgroups(0)
     done = torch.cuda.Event()
@@ -649,8 +648,7 @@ def dropout_keep_mask(seed, G, H, T, p_drop):
     """Host replay of the attention kernels' keep rule (tests): bool [G,H,T,T] (mobgt_attn_dropout_mask_host)."""
     import numpy as np
     m = np.empty((G, H, T, T), dtype=np.uint8)
-    check(_lib.lib().mobgt_attn_dropout_mask_host(int(seed) & 0xFFFFFFFFFFFFFFFF, G, H, T, float(p_drop), m.ctypes.data),
-          "mobgt_attn_dropout_mask_host")
+    _lib.call("mobgt_attn_dropout_mask_host", int(seed) & 0xFFFFFFFFFFFFFFFF, G, H, T, float(p_drop), m.ctypes.data)
     return m.astype(bool)
 
 
@@ -659,8 +657,8 @@ def dropout_site_mask(seed, salt, R, C, p_drop, row0=0):
     step counter, `salt` = the site's constant, rows numbered from `row0` (mobgt_dropout_mask_host)."""
     import numpy as np
     m = np.empty((R, C), dtype=np.uint8)
-    check(_lib.lib().mobgt_dropout_mask_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(salt) & 0xFFFFFFFF, int(row0), R, C, float(p_drop),
-                                             m.ctypes.data), "mobgt_dropout_mask_host")
+    _lib.call("mobgt_dropout_mask_host", int(seed) & 0xFFFFFFFFFFFFFFFF, int(salt) & 0xFFFFFFFF, int(row0), R, C, float(p_drop),
+              m.ctypes.data)
     return m.astype(bool)
 
 
@@ -676,9 +674,9 @@ def spd_batched(counts, n_nodes, D):
         edge_input=torch.empty(G, N, N, D, 1, dtype=torch.uint8, device=dev),
         in_degree=torch.empty(G, N, dtype=torch.int16, device=dev), out_degree=torch.empty(G, N, dtype=torch.int16, device=dev))
     work = torch.empty(int(_lib.lib().mobgt_spd_workspace_bytes(G, N)), dtype=torch.uint8, device=dev)
-    check(_lib.lib().mobgt_spd_batched(_p(counts.contiguous()), _p(n_nodes.contiguous()), _p(out["spd"]), _p(out["path"]),
-                                       _p(out["rel_pos"]), _p(out["edge_input"]), _p(out["in_degree"]),
-                                       _p(out["out_degree"]), _p(work), G, N, D, _stream()), "mobgt_spd_batched")
+    _lib.call("mobgt_spd_batched", _p(counts.contiguous()), _p(n_nodes.contiguous()), _p(out["spd"]), _p(out["path"]),
+              _p(out["rel_pos"]), _p(out["edge_input"]), _p(out["in_degree"]),
+              _p(out["out_degree"]), _p(work), G, N, D, _stream())
     return out
 
 
@@ -695,8 +693,8 @@ class _GatherSumFn(torch.autograd.Function):
         R = idx[0].numel()
         C = tables[0].shape[1]
         out = torch.empty(R, C, dtype=torch.float32, device=tables[0].device)
-        check(_lib.lib().mobgt_embed_gather_sum(_ptr_array(tables), _ptr_array(idx), n_tables, _p(out), R, C, C,
-                                                _IT[idx[0].dtype], _stream()), "mobgt_embed_gather_sum")
+        _lib.call("mobgt_embed_gather_sum", _ptr_array(tables), _ptr_array(idx), n_tables, _p(out), R, C, C,
+                  _IT[idx[0].dtype], _stream())
         ctx.idx, ctx.skip = idx, skip
         ctx.shapes = [t.shape for t in tables]
         # gradient sinks of the tables that are trained parameters (a table listed twice keeps separate buffers: autograd adds
@@ -715,8 +713,8 @@ class _GatherSumFn(torch.autograd.Function):
                  for s, k in zip(ctx.shapes, ctx.sinks)]
         skip = (ctypes.c_int64 * n)(*ctx.skip)
         R, C = dout.shape
-        check(_lib.lib().mobgt_embed_scatter_add(_ptr_array(grads), _ptr_array(ctx.idx), skip, n, _p(dout), R, C,
-                                                 dout.stride(0), _IT[ctx.idx[0].dtype], _stream()), "mobgt_embed_scatter_add")
+        _lib.call("mobgt_embed_scatter_add", _ptr_array(grads), _ptr_array(ctx.idx), skip, n, _p(dout), R, C,
+                  dout.stride(0), _IT[ctx.idx[0].dtype], _stream())
         return (None, None, *grads, *([None] * n))
 
 
@@ -732,7 +730,7 @@ class _HopTableFn(torch.autograd.Function):
                 flush_front()
             _FRONT_DEFER["hop"] = (args, (ew, dw, tab))          # (rides in the category GCN's forward launch)
         else:
-            check(_lib.lib().mobgt_hop_table_fwd(*args, _stream()), "mobgt_hop_table_fwd")
+            _lib.call("mobgt_hop_table_fwd", *args, _stream())
         ctx.save_for_backward(ew, dw)
         ctx.misc = (H, D, int(fp16_roundtrip), edge_dis_weight.shape)
         ctx.sinks = (grad_sink(edge_weight), grad_sink(edge_dis_weight))
@@ -761,8 +759,8 @@ class _HopTableFn(torch.autograd.Function):
             # shares ONE grid with the backward of the stock encoder input when that is parked too (csrc/layer.hip stock_tail_kernel)
             _WGRAD_DEFER["hop_wide"] = (dtab, ew, dw, d_ew, d_dw, D, E, rt)
             return d_ew[:], d_dw[:], None, None, None
-        check(_lib.lib().mobgt_hop_table_bwd(_p(dtab), _p(ew), _p(dw), _p(d_ew), _p(d_dw), D, E, H, rt,
-                                             _stream()), "mobgt_hop_table_bwd")
+        _lib.call("mobgt_hop_table_bwd", _p(dtab), _p(ew), _p(dw), _p(d_ew), _p(d_dw), D, E, H, rt,
+                  _stream())
         return d_ew, d_dw, None, None, None
 
 
@@ -789,13 +787,11 @@ class _SkinnyLinearFn(torch.autograd.Function):
         ctx.all_hip = forms.on("skinny_all")
         if ctx.all_hip:
             y = torch.empty(G, V, dtype=torch.float32, device=x.device)
-            check(_lib.lib().mobgt_skinny_linear_fwd(_p(x), _p(w), _p(bias), _p(y), G, K, V, _stream()),
-                  "mobgt_skinny_linear_fwd")
+            _lib.call("mobgt_skinny_linear_fwd", _p(x), _p(w), _p(bias), _p(y), G, K, V, _stream())
         elif K % 64 == 0 and K <= 448:
             # one pass over W on the matrix cores (csrc/skinny.hip; the library's M = 16 GEMM: 9.2 us at K = 320, 29 us at K = 128)
             y = torch.empty(G, V, dtype=torch.float32, device=x.device)
-            check(_lib.lib().mobgt_skinny_linear_fwd_mfma(_p(x), _p(w), _p(bias), _p(y), G, K, V, _stream()),
-                  "mobgt_skinny_linear_fwd_mfma")
+            _lib.call("mobgt_skinny_linear_fwd_mfma", _p(x), _p(w), _p(bias), _p(y), G, K, V, _stream())
         else:
             y = torch.addmm(bias, x, w.t()) if bias is not None else x @ w.t()
         ctx.save_for_backward(x, w)
@@ -822,7 +818,7 @@ def _skinny_backward(ctx, dy):
     if dx_mfma:     # one pass over W at the full L1 rate (the library's 16x16 tiles: 26 us at V = 7857, K = 448)
         dx = zeros_f32((G, K), x.device)
         if not both:
-            check(_lib.lib().mobgt_skinny_linear_dx(_p(dy), _p(w), _p(dx), G, K, V, _stream()), "mobgt_skinny_linear_dx")
+            _lib.call("mobgt_skinny_linear_dx", _p(dy), _p(w), _p(dx), G, K, V, _stream())
     elif ctx.needs_input_grad[0]:
         dx = torch.empty_like(x) if ctx.all_hip else dy @ w
     dw = None
@@ -832,11 +828,10 @@ def _skinny_backward(ctx, dy):
     if ctx.has_bias and ctx.needs_input_grad[2]:      # (written in full by the kernel: the sink needs no zeroing for it)
         db = ctx.sink_b[:] if ctx.sink_b is not None else torch.empty(V, dtype=torch.float32, device=x.device)
     if both:        # dx and dW (+ db) share nothing but dy: one launch, the first workgroups run the dx body
-        check(_lib.lib().mobgt_skinny_linear_bwd_both(_p(dy), _p(x), _p(w), _p(dx), _p(dw), _p(db), G, K, V, _stream()),
-              "mobgt_skinny_linear_bwd_both")
+        _lib.call("mobgt_skinny_linear_bwd_both", _p(dy), _p(x), _p(w), _p(dx), _p(dw), _p(db), G, K, V, _stream())
         return dx, dw, db
-    check(_lib.lib().mobgt_skinny_linear_bwd(_p(dy), _p(x), _p(w), _p(dx if ctx.all_hip else None), _p(dw), _p(db),
-                                             G, K, V, _stream()), "mobgt_skinny_linear_bwd")
+    _lib.call("mobgt_skinny_linear_bwd", _p(dy), _p(x), _p(w), _p(dx if ctx.all_hip else None), _p(dw), _p(db),
+              G, K, V, _stream())
     return dx, dw, db
 
 
@@ -856,8 +851,8 @@ class _SkinnyLinearGtlFn(torch.autograd.Function):
         y = None
         if logits_out is not None:
             y = logits_out.t = torch.empty(G, V, dtype=torch.float32, device=x.device)
-        check(_lib.lib().mobgt_skinny_linear_gtl(_p(x), _p(w), _p(bias), _p(targets.long().contiguous()), int(target_offset), _p(y), _p(dz),
-                                                 _p(loss), G, K, V, float(alpha), _stream()), "mobgt_skinny_linear_gtl")
+        _lib.call("mobgt_skinny_linear_gtl", _p(x), _p(w), _p(bias), _p(targets.long().contiguous()), int(target_offset), _p(y), _p(dz),
+                  _p(loss), G, K, V, float(alpha), _stream())
         ctx.save_for_backward(x, w, dz)
         ctx.all_hip = False
         ctx.has_bias = bias is not None
@@ -904,8 +899,7 @@ def gather_rows_t(a, rows):
     R, C = rows.numel(), a.shape[1]
     out = torch.empty(R, C, dtype=a.dtype, device=a.device)
     out_t = torch.empty(C, R, dtype=a.dtype, device=a.device)
-    check(_lib.lib().mobgt_gather_rows_t(_p(a), a.stride(0), _p(rows.contiguous()), _p(out), _p(out_t), R, C, _stream()),
-          "mobgt_gather_rows_t")
+    _lib.call("mobgt_gather_rows_t", _p(a), a.stride(0), _p(rows.contiguous()), _p(out), _p(out_t), R, C, _stream())
     return out, out_t
 
 
@@ -917,7 +911,7 @@ def target_rank(scores, target):
     target = target.reshape(-1).long().contiguous()
     G, V = scores.shape
     rank = torch.empty(G, 2, dtype=torch.int32, device=scores.device)
-    check(_lib.lib().mobgt_target_rank(_p(scores), _p(target), _p(rank), G, V, _stream()), "mobgt_target_rank")
+    _lib.call("mobgt_target_rank", _p(scores), _p(target), _p(rank), G, V, _stream())
     return rank
 
 
@@ -966,12 +960,11 @@ def rank_metrics(scores, target, acc, target_offset=0, work=None):
     G, V = scores.shape
     assert target.numel() >= G
     work = _rank_work(scores.device, G, V, work)
-    check(_lib.lib().mobgt_rank_metrics(_p(scores), _p(target), int(target_offset), G, V, _p(acc), _p(work), _stream()),
-          "mobgt_rank_metrics")
+    _lib.call("mobgt_rank_metrics", _p(scores), _p(target), int(target_offset), G, V, _p(acc), _p(work), _stream())
     return acc
 
 
-RM_EXCLUDE_HIST, RM_SPLIT = 1, 2          # include/mobgt_hip.h: MOBGT_RM_*
+RM_EXCLUDE_HIST, RM_SPLIT = _lib.CONSTANTS["MOBGT_RM_EXCLUDE_HIST"], _lib.CONSTANTS["MOBGT_RM_SPLIT"]
 
 
 def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=None, hist_offset=None, exclude_hist=False,
@@ -1018,14 +1011,13 @@ def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=N
     work = _rank_work(scores.device, G, V, work, rank_metrics_masked_work_bytes(G, V))
     flags = (RM_EXCLUDE_HIST if exclude_hist else 0) | (RM_SPLIT if split else 0)
     if ld_allow:
-        check(_lib.lib().mobgt_rank_metrics_masked_rows(_p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), ld_allow,
-                                                        _p(hist), _IT[hist.dtype] if hist is not None else I64, ld_h, n_h,
-                                                        hist_offset, flags, _p(acc), _p(work), _stream()),
-              "mobgt_rank_metrics_masked_rows")
+        _lib.call("mobgt_rank_metrics_masked_rows", _p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), ld_allow,
+                  _p(hist), _IT[hist.dtype] if hist is not None else I64, ld_h, n_h,
+                  hist_offset, flags, _p(acc), _p(work), _stream())
         return acc
-    check(_lib.lib().mobgt_rank_metrics_masked(_p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), _p(hist),
-                                               _IT[hist.dtype] if hist is not None else I64, ld_h, n_h, hist_offset, flags,
-                                               _p(acc), _p(work), _stream()), "mobgt_rank_metrics_masked")
+    _lib.call("mobgt_rank_metrics_masked", _p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), _p(hist),
+              _IT[hist.dtype] if hist is not None else I64, ld_h, n_h, hist_offset, flags,
+              _p(acc), _p(work), _stream())
     return acc
 
 
@@ -1049,8 +1041,8 @@ def skinny_linear_rank_metrics(x, weight, bias, target, acc, target_offset=0, wo
     assert target.numel() == G
     b = bias.detach().contiguous() if bias is not None else None
     work = _rank_work(x.device, G, V, work)
-    check(_lib.lib().mobgt_skinny_linear_rank_metrics(_p(x.detach()), _p(weight.detach()), _p(b), _p(target), int(target_offset),
-                                                      G, K, V, _p(acc), _p(work), _stream()), "mobgt_skinny_linear_rank_metrics")
+    _lib.call("mobgt_skinny_linear_rank_metrics", _p(x.detach()), _p(weight.detach()), _p(b), _p(target), int(target_offset),
+              G, K, V, _p(acc), _p(work), _stream())
     return acc
 
 
@@ -1087,7 +1079,7 @@ def pack_allow(mask_or_ids, V, offset=0):
 
 
 EARTH_RADIUS_KM = 6371.0     # synth.haversine_km's constant
-NEAR_LAST, NEAR_ANY = 0, 1   # include/mobgt_hip.h: MOBGT_NEAR_*
+NEAR_LAST, NEAR_ANY = _lib.CONSTANTS["MOBGT_NEAR_LAST"], _lib.CONSTANTS["MOBGT_NEAR_ANY"]
 _NEAR_MODES = {"last": NEAR_LAST, "any": NEAR_ANY}
 
 
@@ -1198,8 +1190,8 @@ def near_words(pos, hist, hist_offset, chord2_max, mode="last", allow=None, out=
         out = torch.empty(G, W, dtype=torch.int32, device=pos.device)
     if G == 0:
         return out
-    check(_lib.lib().mobgt_near_words(_p(pos), V, _p(hist), _IT[hist.dtype], max(hist.stride(0), n), n, int(hist_offset), m,
-                                      chord2_max, _p(allow), _p(out), out.stride(0), G, _stream()), "mobgt_near_words")
+    _lib.call("mobgt_near_words", _p(pos), V, _p(hist), _IT[hist.dtype], max(hist.stride(0), n), n, int(hist_offset), m,
+              chord2_max, _p(allow), _p(out), out.stride(0), G, _stream())
     return out
 
 
@@ -1275,8 +1267,8 @@ def topk_rows(scores, k, col_offset=0, work=None, out=None, allow=None, exclude=
     if G == 0:
         return out
     work = _topk_work(scores, G, V, k, work)
-    check(_lib.lib().mobgt_topk_rows(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(ids), _p(vals), _p(work),
-                                     _stream()), "mobgt_topk_rows")
+    _lib.call("mobgt_topk_rows", _p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(ids), _p(vals), _p(work),
+              _stream())
     return out
 
 
@@ -1316,14 +1308,13 @@ def _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude, exclude_
         return out
     work = _topk_work(scores, G, V, k, work)
     if ld_allow:
-        check(_lib.lib().mobgt_topk_rows_masked_rows(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
-                                                     ld_allow, _p(exclude), _IT[exclude.dtype] if exclude is not None else I64,
-                                                     ld_ex, n_ex, int(exclude_offset), _p(ids), _p(vals), _p(work), _stream()),
-              "mobgt_topk_rows_masked_rows")
+        _lib.call("mobgt_topk_rows_masked_rows", _p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
+                  ld_allow, _p(exclude), _IT[exclude.dtype] if exclude is not None else I64,
+                  ld_ex, n_ex, int(exclude_offset), _p(ids), _p(vals), _p(work), _stream())
         return out
-    check(_lib.lib().mobgt_topk_rows_masked(_p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
-                                            _p(exclude), _IT[exclude.dtype] if exclude is not None else I64, ld_ex, n_ex,
-                                            int(exclude_offset), _p(ids), _p(vals), _p(work), _stream()), "mobgt_topk_rows_masked")
+    _lib.call("mobgt_topk_rows_masked", _p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
+              _p(exclude), _IT[exclude.dtype] if exclude is not None else I64, ld_ex, n_ex,
+              int(exclude_offset), _p(ids), _p(vals), _p(work), _stream())
     return out
 
 
@@ -1375,7 +1366,7 @@ def node_index(x, time_normal, poi2cat, rows_only, in_degree=None, out_degree=No
             flush_front()
         _FRONT_DEFER["ni"] = (args, (x, time_normal, poi2cat, in_degree, out_degree, idx, real))     # (see front_deferral)
     else:
-        check(_lib.lib().mobgt_node_index(*args, _stream()), "mobgt_node_index")
+        _lib.call("mobgt_node_index", *args, _stream())
     return idx, real
 
 
@@ -1401,8 +1392,8 @@ class _GatherConcatFn(torch.autograd.Function):
         ctot = sum(widths)
         out = torch.empty(R, ctot, dtype=torch.float32, device=tables[0].device)
         warr = (ctypes.c_int * n_tables)(*widths)
-        check(_lib.lib().mobgt_embed_gather_concat(_ptr_array(tables), _ptr_array(idx), warr, n_tables, _p(out), R, ctot,
-                                                   _IT[idx[0].dtype], _stream()), "mobgt_embed_gather_concat")
+        _lib.call("mobgt_embed_gather_concat", _ptr_array(tables), _ptr_array(idx), warr, n_tables, _p(out), R, ctot,
+                  _IT[idx[0].dtype], _stream())
         ctx.idx, ctx.skip, ctx.widths = idx, skip, widths
         ctx.shapes = [t.shape for t in tables]
         return out
@@ -1415,8 +1406,8 @@ class _GatherConcatFn(torch.autograd.Function):
         grads = [zeros_f32(tuple(s), dout.device) for s in ctx.shapes]
         skip = (ctypes.c_int64 * n)(*ctx.skip)
         warr = (ctypes.c_int * n)(*ctx.widths)
-        check(_lib.lib().mobgt_embed_scatter_concat(_ptr_array(grads), _ptr_array(ctx.idx), skip, warr, n, _p(dout), R, ctot,
-                                                    _IT[ctx.idx[0].dtype], _stream()), "mobgt_embed_scatter_concat")
+        _lib.call("mobgt_embed_scatter_concat", _ptr_array(grads), _ptr_array(ctx.idx), skip, warr, n, _p(dout), R, ctot,
+                  _IT[ctx.idx[0].dtype], _stream())
         return (None, None, *grads, *([None] * n))
 
 
@@ -1474,11 +1465,11 @@ class _GatherMultiFn(torch.autograd.Function):
         ci, i64, vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
 
         def launch():
-            check(_lib.lib().mobgt_embed_gather_multi(
+            _lib.call("mobgt_embed_gather_multi",
                 n, _ptr_array(tables), None, _ptr_array(idx), (i64 * n)(*[sp[3] for sp in spec]),
                 (ci * n)(*[t.shape[1] for t in tables]), (ci * n)(*[sp[1] for sp in spec]), (ci * n)(*[int(sp[2]) for sp in spec]),
                 (vp * n)(*[outs[sp[0]].data_ptr() for sp in spec]), (i64 * n)(*[outs[sp[0]].stride(0) for sp in spec]), R,
-                _IT[idx[0].dtype], 0, None, 0, _stream()), "mobgt_embed_gather_multi")
+                _IT[idx[0].dtype], 0, None, 0, _stream())
         if _TOKEN_FWD["on"] and _TOKEN_FWD["gather"] is None and len(outs) == 3 and all(i_.dtype == idx[0].dtype for i_ in idx):
             _TOKEN_FWD["gather"] = dict(launch=launch, tables=tables, idx=idx, spec=spec, outs=outs, R=R)     # (see token_fwd_deferral)
         else:
@@ -1511,12 +1502,12 @@ class _GatherMultiFn(torch.autograd.Function):
                 pend = _ROW0_PENDING.pop(ctx.ptrs[t], None)
                 if pend is not None:
                     extra, extra_job = pend, k
-            check(_lib.lib().mobgt_embed_gather_multi(
+            _lib.call("mobgt_embed_gather_multi",
                 m, None, (vp * m)(*[grads[t].data_ptr() for t in jobs]), (vp * m)(*[ctx.idx[t].data_ptr() for t in jobs]),
                 (i64 * m)(*[spec[t][3] for t in jobs]), (ci * m)(*[ctx.shapes[t][1] for t in jobs]),
                 (ci * m)(*[spec[t][1] for t in jobs]), None, (vp * m)(*[gbuf[spec[t][0]].data_ptr() for t in jobs]),
                 (i64 * m)(*[gbuf[spec[t][0]].stride(0) for t in jobs]), R, _IT[ctx.idx[0].dtype], 1, _p(extra), extra_job,
-                _stream()), "mobgt_embed_gather_multi")
+                _stream())
         return (None, None, None, *grads, *([None] * n))
 
 
@@ -1563,8 +1554,8 @@ class _GradientTailLossFn(torch.autograd.Function):
         G, V = logits.shape
         dlogits = torch.empty_like(logits)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        check(_lib.lib().mobgt_gradient_tail_loss(_p(logits), _p(targets.long().contiguous()), int(target_offset), _p(dlogits),
-                                                  _p(loss), G, V, float(alpha), _stream()), "mobgt_gradient_tail_loss")
+        _lib.call("mobgt_gradient_tail_loss", _p(logits), _p(targets.long().contiguous()), int(target_offset), _p(dlogits),
+                  _p(loss), G, V, float(alpha), _stream())
         ctx.save_for_backward(dlogits)
         return loss
 
@@ -1586,7 +1577,7 @@ class _StockTokensFn(torch.autograd.Function):
                G, N, C, atom.shape[0], indeg.shape[0], outdeg.shape[0], p, seed, _p(seed_dev), salt)
         hop, ni = take_front_jobs() if _FRONT_DEFER["on"] else (None, None)
         if ni is not None:                                       # (not a job of the stock model: launched alone)
-            check(_lib.lib().mobgt_node_index(*ni[0], _stream()), "mobgt_node_index")
+            _lib.call("mobgt_node_index", *ni[0], _stream())
         jobs = []
         if _FRONT_DEFER["on"]:
             from .model import take_pending_pack
@@ -1604,9 +1595,9 @@ class _StockTokensFn(torch.autograd.Function):
             pack = ((vp * nj)(*[j[0].data_ptr() for j in part]), (vp * nj)(*[j[1].data_ptr() for j in part]), (ci * nj)(*[j[2] for j in part]),
                     (ci * nj)(*[j[3] for j in part]), (ci * nj)(*[j[4] for j in part])) if nj else (None, None, None, None, None)
             hargs = [1] + hop[0] if hop is not None else [0, None, None, None, 0, 0, 0, 0]
-            check(_lib.lib().mobgt_stock_front_fwd(*tok, nj, *pack, *hargs, _stream()), "mobgt_stock_front_fwd")
+            _lib.call("mobgt_stock_front_fwd", *tok, nj, *pack, *hargs, _stream())
         else:
-            check(_lib.lib().mobgt_stock_tokens_fwd(*tok, _stream()), "mobgt_stock_tokens_fwd")
+            _lib.call("mobgt_stock_tokens_fwd", *tok, _stream())
         ctx.idx = (x, din, dout)
         ctx.misc = (p, seed, seed_dev, salt, padding_idx, [t.shape for t in (atom, indeg, outdeg, gtok)])
         # (a table listed twice keeps separate buffers: autograd adds the results, which must not be one memory)
@@ -1633,7 +1624,7 @@ class _StockTokensFn(torch.autograd.Function):
             # autograd gets back are fresh views (AccumulateGrad clones a returned gradient something else still references)
             _WGRAD_DEFER["stock_tok"] = (args, (dy, x, din, dout, seed_dev, grads))
             return (None, None, None, *[g_[:] if g_ is not None else None for g_ in grads], None, None, None, None, None)
-        check(_lib.lib().mobgt_stock_tokens_bwd(*args, _stream()), "mobgt_stock_tokens_bwd")
+        _lib.call("mobgt_stock_tokens_bwd", *args, _stream())
         return (None, None, None, *grads, None, None, None, None, None)
 
 
@@ -1664,8 +1655,8 @@ class _TokenLayerNormFn(torch.autograd.Function):
         G, T, C = enc.shape
         y = torch.empty(G, C, dtype=torch.float32, device=enc.device)
         stat = torch.empty(2, G, dtype=torch.float32, device=enc.device)
-        check(_lib.lib().mobgt_token_ln_fwd(_p(enc), _p(weight), _p(bias), _p(y), _p(stat[0]), _p(stat[1]), G, T, C, float(eps),
-                                            _stream()), "mobgt_token_ln_fwd")
+        _lib.call("mobgt_token_ln_fwd", _p(enc), _p(weight), _p(bias), _p(y), _p(stat[0]), _p(stat[1]), G, T, C, float(eps),
+                  _stream())
         ctx.save_for_backward(enc, weight, stat)
         ctx.sinks = (grad_sink(weight), grad_sink(bias))
         return y
@@ -1677,8 +1668,8 @@ class _TokenLayerNormFn(torch.autograd.Function):
         denc = torch.empty_like(enc)
         # (the affine gradients ACCUMULATE: into the parameters' sinks -- zeroed by the trainer's prologue -- or into zeros)
         dg, db = (k[:] if k is not None else zeros_f32((C,), enc.device) for k in ctx.sinks)
-        check(_lib.lib().mobgt_token_ln_bwd(_p(dy.contiguous()), _p(enc), _p(stat[0]), _p(stat[1]), _p(weight), _p(denc), _p(dg), _p(db),
-                                            G, T, C, _stream()), "mobgt_token_ln_bwd")
+        _lib.call("mobgt_token_ln_bwd", _p(dy.contiguous()), _p(enc), _p(stat[0]), _p(stat[1]), _p(weight), _p(denc), _p(dg), _p(db),
+                  G, T, C, _stream())
         return denc, dg, db, None
 
 
@@ -1701,8 +1692,8 @@ class _CrossEntropyFn(torch.autograd.Function):
         G, V = logits.shape
         dlogits = torch.empty_like(logits)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        check(_lib.lib().mobgt_cross_entropy(_p(logits), _p(targets.long().contiguous()), int(ignore_index), _p(dlogits), _p(loss), G, V,
-                                             _stream()), "mobgt_cross_entropy")
+        _lib.call("mobgt_cross_entropy", _p(logits), _p(targets.long().contiguous()), int(ignore_index), _p(dlogits), _p(loss), G, V,
+                  _stream())
         ctx.save_for_backward(dlogits)
         return loss
 
@@ -1801,10 +1792,10 @@ def _token_park_linear(g, w, y):
         W2 = ent["w2"].shape[0]
         d_pt = torch.empty(G * N, W2, dtype=torch.float32, device=g.device)
         dx4 = pend["dx4"]
-        check(_lib.lib().mobgt_token_bwd_chain(_p(pend["dout"]), _p(pend["real"]), _p(ent["nf"]), _p(ent["x4"]), ent["x4"].stride(0),
-                                               _p(ent["w4"]), _p(ent["w2"]), _p(pend["d_nf"]), _p(pend["d_add"]), _p(dx4), dx4.stride(0),
-                                               _p(d_pt), _p(pend["d_tok"]), G, N, C, W2, ent["slope4"], ent["slope2"], p_pos, p_in, seed,
-                                               _p(seed_dev), salts[0], salts[1], salts[2], _stream()), "mobgt_token_bwd_chain")
+        _lib.call("mobgt_token_bwd_chain", _p(pend["dout"]), _p(pend["real"]), _p(ent["nf"]), _p(ent["x4"]), ent["x4"].stride(0),
+                  _p(ent["w4"]), _p(ent["w2"]), _p(pend["d_nf"]), _p(pend["d_add"]), _p(dx4), dx4.stride(0),
+                  _p(d_pt), _p(pend["d_tok"]), G, N, C, W2, ent["slope4"], ent["slope2"], p_pos, p_in, seed,
+                  _p(seed_dev), salts[0], salts[1], salts[2], _stream())
         return d_pt
     return None
 
@@ -1941,7 +1932,7 @@ class _DropoutFn(torch.autograd.Function):
         x = x.contiguous()
         y = torch.empty_like(x)
         row = x.shape[-1] if x.dim() > 1 else x.numel()
-        check(_lib.lib().mobgt_dropout(_p(x), _p(y), x.numel(), row, p, seed, _p(seed_dev), salt, _stream()), "mobgt_dropout")
+        _lib.call("mobgt_dropout", _p(x), _p(y), x.numel(), row, p, seed, _p(seed_dev), salt, _stream())
         ctx.misc = (p, seed, seed_dev, salt, row)
         return y
 
@@ -1950,7 +1941,7 @@ class _DropoutFn(torch.autograd.Function):
         p, seed, seed_dev, salt, row = ctx.misc
         g = g.contiguous()
         dx = torch.empty_like(g)
-        check(_lib.lib().mobgt_dropout(_p(g), _p(dx), g.numel(), row, p, seed, _p(seed_dev), salt, _stream()), "mobgt_dropout")
+        _lib.call("mobgt_dropout", _p(g), _p(dx), g.numel(), row, p, seed, _p(seed_dev), salt, _stream())
         return dx, None, None, None, None
 
 
@@ -1971,9 +1962,9 @@ class _BiasActFn(torch.autograd.Function):
         x = x.contiguous()
         R, C = x.shape
         y = torch.empty_like(x)
-        check(_lib.lib().mobgt_bias_act_fwd_t(_p(x), _p(bias), _p(y), _p(yt.t if yt is not None else None),
-                                              yt.t.stride(0) if yt is not None else 0, R, C, slope, p_drop, seed, _p(seed_dev), salt,
-                                              _stream()), "mobgt_bias_act_fwd_t")
+        _lib.call("mobgt_bias_act_fwd_t", _p(x), _p(bias), _p(y), _p(yt.t if yt is not None else None),
+                  yt.t.stride(0) if yt is not None else 0, R, C, slope, p_drop, seed, _p(seed_dev), salt,
+                  _stream())
         ctx.save_for_backward(y)
         ctx.misc = (slope, p_drop, seed, seed_dev, salt, bias is not None)
         return y
@@ -1985,8 +1976,8 @@ class _BiasActFn(torch.autograd.Function):
         R, C = y.shape
         dx = torch.empty_like(y)
         db = zeros_f32((C,), y.device) if has_bias else None
-        check(_lib.lib().mobgt_bias_act_bwd(_p(dy.contiguous()), _p(y), _p(dx), _p(db), R, C, slope, p_drop, seed, _p(seed_dev),
-                                            salt, _stream()), "mobgt_bias_act_bwd")
+        _lib.call("mobgt_bias_act_bwd", _p(dy.contiguous()), _p(y), _p(dx), _p(db), R, C, slope, p_drop, seed, _p(seed_dev),
+                  salt, _stream())
         return dx, db, None, None, None, None, None, None
 
 
@@ -2019,8 +2010,8 @@ class _HeadActFn(torch.autograd.Function):
         R, C = u.shape
         out = torch.empty_like(u)
         stats = torch.empty(2, R, dtype=torch.float32, device=u.device)
-        check(_lib.lib().mobgt_head_act_fwd(_p(u), _p(w), _p(b), _p(out), _p(stats[0]), _p(stats[1]), R, C, eps, slope, p_drop,
-                                            seed, _p(seed_dev), salt, _stream()), "mobgt_head_act_fwd")
+        _lib.call("mobgt_head_act_fwd", _p(u), _p(w), _p(b), _p(out), _p(stats[0]), _p(stats[1]), R, C, eps, slope, p_drop,
+                  seed, _p(seed_dev), salt, _stream())
         ctx.save_for_backward(u, w, b, stats)
         ctx.misc = (eps, slope, p_drop, seed, seed_dev, salt)
         return out
@@ -2032,9 +2023,8 @@ class _HeadActFn(torch.autograd.Function):
         R, C = u.shape
         du = torch.empty_like(u)
         dg, db = zeros_f32((C,), u.device), zeros_f32((C,), u.device)
-        check(_lib.lib().mobgt_head_act_bwd(_p(dout.contiguous()), _p(u), _p(w), _p(b), _p(stats[0]), _p(stats[1]), _p(du),
-                                            _p(dg), _p(db), R, C, eps, slope, p_drop, seed, _p(seed_dev), salt, _stream()),
-              "mobgt_head_act_bwd")
+        _lib.call("mobgt_head_act_bwd", _p(dout.contiguous()), _p(u), _p(w), _p(b), _p(stats[0]), _p(stats[1]), _p(du),
+                  _p(dg), _p(db), R, C, eps, slope, p_drop, seed, _p(seed_dev), salt, _stream())
         return du, dg, db, None, None, None, None, None, None
 
 
@@ -2062,10 +2052,9 @@ class _HeadChainFn(torch.autograd.Function):
         dev = enc.device
         x3, u3, out = (torch.empty(G, W, dtype=torch.float32, device=dev) for _ in range(3))
         stats = torch.empty(2, G, dtype=torch.float32, device=dev)
-        check(_lib.lib().mobgt_head_chain_fwd(_p(enc), _p(user), _IT[user.dtype], offset, _p(table), table.shape[0], _p(w3), _p(b3),
-                                              _p(ln_w), _p(ln_b), _p(x3), _p(u3), _p(out), _p(stats[0]), _p(stats[1]), G, T, C, U,
-                                              eps, slope, p_drop, seed, _p(seed_dev), salt, _p(_head_chain_ws(dev)), _stream()),
-              "mobgt_head_chain_fwd")
+        _lib.call("mobgt_head_chain_fwd", _p(enc), _p(user), _IT[user.dtype], offset, _p(table), table.shape[0], _p(w3), _p(b3),
+                  _p(ln_w), _p(ln_b), _p(x3), _p(u3), _p(out), _p(stats[0]), _p(stats[1]), G, T, C, U,
+                  eps, slope, p_drop, seed, _p(seed_dev), salt, _p(_head_chain_ws(dev)), _stream())
         ctx.save_for_backward(x3, u3, stats, w3, ln_w, ln_b)
         ctx.user = user
         ctx.misc = (G, T, C, U, offset, tuple(table.shape), eps, slope, p_drop, seed, seed_dev, salt, bf16_wgrad)
@@ -2085,10 +2074,9 @@ class _HeadChainFn(torch.autograd.Function):
         k_w3, k_b3, k_g, k_beta = ctx.psinks
         dg = k_g[:] if k_g is not None else zeros_f32((C + U,), dev)
         dbeta = k_beta[:] if k_beta is not None else zeros_f32((C + U,), dev)
-        check(_lib.lib().mobgt_head_chain_bwd(_p(dout), _p(u3), _p(stats[0]), _p(stats[1]), _p(ctx.user), _IT[ctx.user.dtype], offset,
-                                              tshape[0], _p(w3), _p(ln_w), _p(ln_b), _p(du3), _p(denc), _p(dtable), _p(dg), _p(dbeta),
-                                              G, T, C, U, eps, slope, p_drop, seed, _p(seed_dev), salt, _stream()),
-              "mobgt_head_chain_bwd")
+        _lib.call("mobgt_head_chain_bwd", _p(dout), _p(u3), _p(stats[0]), _p(stats[1]), _p(ctx.user), _IT[ctx.user.dtype], offset,
+                  tshape[0], _p(w3), _p(ln_w), _p(ln_b), _p(du3), _p(denc), _p(dtable), _p(dg), _p(dbeta),
+                  G, T, C, U, eps, slope, p_drop, seed, _p(seed_dev), salt, _stream())
         if bf16_wgrad:                                                     # (operands rounded to bf16 while loading)
             dw, db = linear_wgrad(du3, x3, with_bias=True, leaf=True, dw=k_w3[:] if k_w3 is not None else None,
                                   db=k_b3[:] if k_b3 is not None else None)
@@ -2141,8 +2129,8 @@ class _HeadInputFn(torch.autograd.Function):
         G, T, C = enc.shape
         U = table.shape[1]
         x3 = torch.empty(G, C + U, dtype=torch.float32, device=enc.device)
-        check(_lib.lib().mobgt_head_input_fwd(_p(enc), _p(user), _IT[user.dtype], offset, _p(table), table.shape[0], _p(x3),
-                                              G, T, C, U, _stream()), "mobgt_head_input_fwd")
+        _lib.call("mobgt_head_input_fwd", _p(enc), _p(user), _IT[user.dtype], offset, _p(table), table.shape[0], _p(x3),
+                  G, T, C, U, _stream())
         ctx.user, ctx.misc = user, (G, T, C, U, offset, table.shape)
         ctx.sink = grad_sink(table)
         return x3
@@ -2153,8 +2141,8 @@ class _HeadInputFn(torch.autograd.Function):
         dx3 = dx3.contiguous()
         denc = torch.empty(G, T, C, dtype=torch.float32, device=dx3.device)
         dtable = ctx.sink[:] if ctx.sink is not None else zeros_f32(tuple(tshape), dx3.device)
-        check(_lib.lib().mobgt_head_input_bwd(_p(dx3), _p(ctx.user), _IT[ctx.user.dtype], offset, _p(denc), _p(dtable),
-                                              tshape[0], G, T, C, U, _stream()), "mobgt_head_input_bwd")
+        _lib.call("mobgt_head_input_bwd", _p(dx3), _p(ctx.user), _IT[ctx.user.dtype], offset, _p(denc), _p(dtable),
+                  tshape[0], G, T, C, U, _stream())
         return denc, dtable, None, None
 
 
@@ -2190,7 +2178,7 @@ def _token_fwd_fused(nf, real, add, token, pe0, out, out16, qkv_w, qkv, G, N, C,
         _p(f2["w"]), _p(f2["b"]), float(f2["slope"]), _p(f4["w"]), _p(f4["b"]), float(f4["slope"]),
         _p(real), _p(token), _p(pe0), _p(out), _p(out16), _p(qkv_w[0].t), _p(qkv_w[1].t), _p(qkv), G, N, C, p_pos, p_in, seed,
         _p(seed_dev), salts[0], salts[1], salts[2], _stream()))
-    if rc == -1:                          # MOBGT_EBADDIM: a job list the kernel's gather stage is not laid out for (nothing was launched)
+    if rc == _lib.CONSTANTS["MOBGT_EBADDIM"]:     # a job list the kernel's gather stage is not laid out for (nothing was launched)
         flush_token_fwd()
         return False
     check(rc, "mobgt_token_fwd_chain")
@@ -2220,17 +2208,15 @@ class _AssembleTokensFn(torch.autograd.Function):
             # packed [3C, C] weight and the bf16 bias
             qkv = torch.empty(G * (N + 1), 3 * C, dtype=torch.bfloat16, device=nf.device)
             if not _token_fwd_fused(nf, real, add, token, pe0, out, out16, qkv_w, qkv, G, N, C, p_pos, p_in, seed, seed_dev, salts):
-                check(_lib.lib().mobgt_assemble_tokens_qkv(_p(nf), _p(real), _p(add), _p(token), _p(pe0), _p(out), _p(out16),
-                                                           _p(qkv_w[0].t), _p(qkv_w[1].t), _p(qkv), G, N, C, p_pos, p_in, seed,
-                                                           _p(seed_dev), salts[0], salts[1], salts[2], _stream()),
-                      "mobgt_assemble_tokens_qkv")
+                _lib.call("mobgt_assemble_tokens_qkv", _p(nf), _p(real), _p(add), _p(token), _p(pe0), _p(out), _p(out16),
+                          _p(qkv_w[0].t), _p(qkv_w[1].t), _p(qkv), G, N, C, p_pos, p_in, seed,
+                          _p(seed_dev), salts[0], salts[1], salts[2], _stream())
             side.append(out16)
             side.append(qkv)
         else:
             flush_token_fwd()
-            check(_lib.lib().mobgt_assemble_tokens_fwd(_p(nf), _p(real), _p(add), _p(token), _p(pe0), _p(out), _p(out16), G, N, C,
-                                                       p_pos, p_in, seed, _p(seed_dev), salts[0], salts[1], salts[2], _stream()),
-                  "mobgt_assemble_tokens_fwd")
+            _lib.call("mobgt_assemble_tokens_fwd", _p(nf), _p(real), _p(add), _p(token), _p(pe0), _p(out), _p(out16), G, N, C,
+                      p_pos, p_in, seed, _p(seed_dev), salts[0], salts[1], salts[2], _stream())
             if side is not None:
                 side.append(out16)
         ctx.save_for_backward(real)
@@ -2261,9 +2247,8 @@ class _AssembleTokensFn(torch.autograd.Function):
             _TOKEN_PENDING[d_nf.data_ptr()] = dict(stage=1, ent=ent, dout=dout, real=real, d_nf=d_nf, d_add=d_add, d_tok=d_tok,
                                                    misc=(G, N, C, p_pos, p_in, seed, seed_dev, salts))
         else:
-            check(_lib.lib().mobgt_assemble_tokens_bwd(_p(dout), _p(real), _p(d_nf), _p(d_add), _p(d_tok), G, N, C, p_pos, p_in, seed,
-                                                       _p(seed_dev), salts[0], salts[1], salts[2], _stream()),
-                  "mobgt_assemble_tokens_bwd")
+            _lib.call("mobgt_assemble_tokens_bwd", _p(dout), _p(real), _p(d_nf), _p(d_add), _p(d_tok), G, N, C, p_pos, p_in, seed,
+                      _p(seed_dev), salts[0], salts[1], salts[2], _stream())
         if ctx.pe_ptr is not None:
             # the positional table's other consumer (the gather of pe[1..n]) adds this row-0 share inside ITS scatter launch:
             # one gradient producer for the table, no [L, C] zero table here and no table-sized add after
@@ -2328,20 +2313,19 @@ def small_gemm(a, b, bias=None, b_is_nk=False, out=None, out_dtype=torch.float32
     only_t = ct is not None and ct[2]
     c = None if only_t else (out if out is not None else torch.empty(M, N, dtype=out_dtype, device=a.device))
     if leaky is None and a_mask is None and ct is None and k_b is None:
-        check(_lib.lib().mobgt_small_gemm_f32(_p(a), a.stride(0), _p(b), b.stride(0), int(b_is_nk), _p(bias), _p(c), c.stride(0),
-                                              _DT[c.dtype], M, N, K, _stream()), "mobgt_small_gemm_f32")
+        _lib.call("mobgt_small_gemm_f32", _p(a), a.stride(0), _p(b), b.stride(0), int(b_is_nk), _p(bias), _p(c), c.stride(0),
+                  _DT[c.dtype], M, N, K, _stream())
         return c
     y, pos, neg, zer = a_mask if a_mask is not None else (None, 1.0, 1.0, 1.0)
     if y is not None:
         assert y.dtype == torch.float32 and y.shape == a.shape and y.stride(1) == 1 and y.stride(0) == a.stride(0)
     p_drop, seed, seed_dev, salt = drop if drop is not None else (0.0, 0, None, 0)
-    check(_lib.lib().mobgt_small_gemm_f32_act(_p(a), a.stride(0), _p(y), float(pos), float(neg), float(zer), _p(b), b.stride(0),
-                                              int(b_is_nk), _p(bias), int(leaky is not None), float(leaky or 0.0), float(p_drop),
-                                              int(seed), _p(seed_dev), int(salt) & 0xFFFFFFFF, _p(c), c.stride(0) if c is not None else N,
-                                              _DT[c.dtype] if c is not None else F32, _p(ct[0] if ct else None),
-                                              ct[0].stride(0) if ct else 0, _p(ct[1] if ct else None), M, N, K, int(k_b or 0),
-                                              _stream()),
-          "mobgt_small_gemm_f32_act")
+    _lib.call("mobgt_small_gemm_f32_act", _p(a), a.stride(0), _p(y), float(pos), float(neg), float(zer), _p(b), b.stride(0),
+              int(b_is_nk), _p(bias), int(leaky is not None), float(leaky or 0.0), float(p_drop),
+              int(seed), _p(seed_dev), int(salt) & 0xFFFFFFFF, _p(c), c.stride(0) if c is not None else N,
+              _DT[c.dtype] if c is not None else F32, _p(ct[0] if ct else None),
+              ct[0].stride(0) if ct else 0, _p(ct[1] if ct else None), M, N, K, int(k_b or 0),
+              _stream())
     return c
 
 
@@ -2374,7 +2358,7 @@ def front_small_gemm_flush():
     if job is None:
         return
     if _lib.lib().mobgt_front_sgemm_pending():             # no launch took it along: drop the job, launch the product alone
-        check(_lib.lib().mobgt_front_sgemm_job(None, 0, None, 0, None, 0, 0.0, None, 0, None, 0, 0, 0, 0, 0), "mobgt_front_sgemm_job")
+        _lib.call("mobgt_front_sgemm_job", None, 0, None, 0, None, 0, 0.0, None, 0, None, 0, 0, 0, 0, 0)
         a, b, bias, leaky, k_b, ct = job["args"]
         job["c"] = small_gemm(a, b, bias, leaky=leaky, k_b=k_b, ct=(ct, None, False) if ct is not None else None)
     _FRONT_SGEMM["done"] = job
@@ -2383,7 +2367,7 @@ def front_small_gemm_flush():
 def front_small_gemm_drop():
     """Forget a job that is still waiting for a launch (an exception between front_small_gemm and its flush) and an unclaimed result."""
     if _FRONT_SGEMM.pop("job", None) is not None:
-        check(_lib.lib().mobgt_front_sgemm_job(None, 0, None, 0, None, 0, 0.0, None, 0, None, 0, 0, 0, 0, 0), "mobgt_front_sgemm_job")
+        _lib.call("mobgt_front_sgemm_job", None, 0, None, 0, None, 0, 0.0, None, 0, None, 0, 0, 0, 0, 0)
     _FRONT_SGEMM.pop("done", None)
 
 
@@ -2442,12 +2426,12 @@ def layer_wgrad_big(items, R):
     S = lib.mobgt_layer_wgrad_big_splits(R, tiles)
     dev = items[0][0].device
     parts = [torch.empty(S, g.shape[1], x.shape[1], dtype=torch.float32, device=dev) for g, x, _, _ in items]
-    check(lib.mobgt_layer_wgrad_big(n, (vp * n)(*[t[0].data_ptr() for t in items]), (i64 * n)(*[t[0].stride(0) for t in items]),
-                                    (vp * n)(*[t[1].data_ptr() for t in items]), (i64 * n)(*[t[1].stride(0) for t in items]),
-                                    (vp * n)(*[q.data_ptr() for q in parts]),
-                                    (vp * n)(*[(t[2].data_ptr() if t[2] is not None else None) for t in items]),
-                                    (ci * n)(*[t[0].shape[1] for t in items]), (ci * n)(*[t[1].shape[1] for t in items]), R, S,
-                                    _stream()), "mobgt_layer_wgrad_big")
+    _lib.call("mobgt_layer_wgrad_big", n, (vp * n)(*[t[0].data_ptr() for t in items]), (i64 * n)(*[t[0].stride(0) for t in items]),
+              (vp * n)(*[t[1].data_ptr() for t in items]), (i64 * n)(*[t[1].stride(0) for t in items]),
+              (vp * n)(*[q.data_ptr() for q in parts]),
+              (vp * n)(*[(t[2].data_ptr() if t[2] is not None else None) for t in items]),
+              (ci * n)(*[t[0].shape[1] for t in items]), (ci * n)(*[t[1].shape[1] for t in items]), R, S,
+              _stream())
     outs = []
     for part, (_, _, _, sink) in zip(parts, items):
         parked = defer_partial_sum(part, sink) if sink is not None else None
@@ -2509,25 +2493,23 @@ def flush_deferred_wgrads():
     for o in range(0, len(psum), 48):            # the sums over the library's split-K partial weight gradients: one launch
         part = psum[o:o + 48]
         n = len(part)
-        check(_lib.lib().mobgt_partial_sum_multi(n, (ctypes.c_void_p * n)(*[p_[0].data_ptr() for p_ in part]),
-                                                 (ctypes.c_void_p * n)(*[p_[1].data_ptr() for p_ in part]),
-                                                 (ctypes.c_int * n)(*[p_[0].shape[0] for p_ in part]),
-                                                 (ctypes.c_int64 * n)(*[p_[1].numel() for p_ in part]), _stream()),
-              "mobgt_partial_sum_multi")
+        _lib.call("mobgt_partial_sum_multi", n, (ctypes.c_void_p * n)(*[p_[0].data_ptr() for p_ in part]),
+                  (ctypes.c_void_p * n)(*[p_[1].data_ptr() for p_ in part]),
+                  (ctypes.c_int * n)(*[p_[0].shape[0] for p_ in part]),
+                  (ctypes.c_int64 * n)(*[p_[1].numel() for p_ in part]), _stream())
     tok, wide = _WGRAD_DEFER.pop("stock_tok", None), _WGRAD_DEFER.pop("hop_wide", None)
     if tok is not None and wide is not None:     # the stock step's tail: both in one grid
         dtab, ew, dw_, d_ew, d_dw, D, E, rt = wide
-        check(_lib.lib().mobgt_stock_tail_bwd(*tok[0], _p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream()),
-              "mobgt_stock_tail_bwd")
+        _lib.call("mobgt_stock_tail_bwd", *tok[0], _p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream())
     elif tok is not None:
-        check(_lib.lib().mobgt_stock_tokens_bwd(*tok[0], _stream()), "mobgt_stock_tokens_bwd")
+        _lib.call("mobgt_stock_tokens_bwd", *tok[0], _stream())
     elif wide is not None:
         dtab, ew, dw_, d_ew, d_dw, D, E, rt = wide
-        check(_lib.lib().mobgt_hop_table_bwd(_p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream()), "mobgt_hop_table_bwd")
+        _lib.call("mobgt_hop_table_bwd", _p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream())
     vp, i64, ci, cf = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
     if hop is not None and not items:            # nobody to ride with
         dtab, ew, dw_, d_ew, d_dw, D, E, rt = hop
-        check(_lib.lib().mobgt_hop_table_bwd(_p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream()), "mobgt_hop_table_bwd")
+        _lib.call("mobgt_hop_table_bwd", _p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream())
         hop = None
     for o in range(0, len(items), 32):
         part = items[o:o + 32]
@@ -2542,7 +2524,7 @@ def flush_deferred_wgrads():
         mv = []
         for it in part:
             mv += list(it[4])
-        check(_lib.lib().mobgt_linear_wgrad_multi_hop(
+        _lib.call("mobgt_linear_wgrad_multi_hop",
             n, (vp * n)(*[ptr(it[0]) for it in part]), (i64 * n)(*[it[0].stride(0) for it in part]),
             (vp * n)(*[ptr(it[1]) for it in part]), (i64 * n)(*[it[1].stride(0) for it in part]),
             (vp * n)(*[ptr(it[2]) for it in part]), (vp * n)(*[ptr(it[3]) for it in part]), (cf * (3 * n))(*mv),
@@ -2550,7 +2532,7 @@ def flush_deferred_wgrads():
             (vp * n)(*[ptr(it[6]) for it in part]), (ci * n)(*[int(it[7]) for it in part]),
             (i64 * n)(*[it[0].shape[0] for it in part]), (ci * n)(*[it[0].shape[1] for it in part]),
             (ci * n)(*[it[1].shape[1] for it in part]), (ci * n)(*[1 if it[0].dtype == torch.float32 else 0 for it in part]),
-            *hop_args, _stream()), "mobgt_linear_wgrad_multi_hop")
+            *hop_args, _stream())
 
 
 def linear_wgrad_masked(g, x, g_mask=None, x_mask=None, mask_vals=(1.0, 1.0, 1.0), db=None, db_of_x=False, dw=None, g_out=None,
@@ -2569,9 +2551,9 @@ def linear_wgrad_masked(g, x, g_mask=None, x_mask=None, mask_vals=(1.0, 1.0, 1.0
     assert g_out is None or (g_mask is not None and g_out.shape == g.shape and g_out.stride() == g.stride())
     if leaf and _WGRAD_DEFER["on"] and g_out is None and M % 2 == 0 and N % 2 == 0:
         return _wgrad_defer(g, x, g_mask, x_mask, mask_vals, dw, db, db_of_x)
-    check(_lib.lib().mobgt_linear_wgrad_masked(_p(g), g.stride(0), _p(x), x.stride(0), _p(g_mask), _p(x_mask), float(mask_vals[0]),
-                                               float(mask_vals[1]), float(mask_vals[2]), _p(g_out), _p(dw), N, _p(db), int(db_of_x),
-                                               R, M, N, _stream()), "mobgt_linear_wgrad_masked")
+    _lib.call("mobgt_linear_wgrad_masked", _p(g), g.stride(0), _p(x), x.stride(0), _p(g_mask), _p(x_mask), float(mask_vals[0]),
+              float(mask_vals[1]), float(mask_vals[2]), _p(g_out), _p(dw), N, _p(db), int(db_of_x),
+              R, M, N, _stream())
     return dw
 
 
@@ -2581,7 +2563,7 @@ def small_gemm_ok(a, b):
 
 
 # ------------------------------------------------------------------- the encoder layer's small GEMMs
-GEMM_BIAS, GEMM_GELU, GEMM_GELU_BWD, GEMM_ADD = 0, 1, 2, 3
+GEMM_BIAS, GEMM_GELU, GEMM_GELU_BWD, GEMM_ADD = (_lib.CONSTANTS["MOBGT_GEMM_" + n] for n in ("BIAS", "GELU", "GELU_BWD", "ADD"))
 
 
 def layer_gemm_ok(a, b, b_is_kn=False):
@@ -2618,8 +2600,8 @@ def layer_gemm(a, b, bias=None, b_is_kn=False, epilogue=GEMM_BIAS, aux_in=None):
             assert aux_in.dtype == torch.bfloat16 and aux_in.shape == (M, N) and aux_in.is_contiguous()
     if bias is not None:
         assert bias.dtype == torch.bfloat16 and bias.numel() == N and bias.is_contiguous()
-    check(_lib.lib().mobgt_layer_gemm(_p(a), a.stride(0), _p(b), b.stride(0), int(b_is_kn), _p(bias), _p(c), N, epilogue,
-                                      _p(aux_in), _p(aux_out), M, N, K, _stream()), "mobgt_layer_gemm")
+    _lib.call("mobgt_layer_gemm", _p(a), a.stride(0), _p(b), b.stride(0), int(b_is_kn), _p(bias), _p(c), N, epilogue,
+              _p(aux_in), _p(aux_out), M, N, K, _stream())
     return (c, aux_out) if epilogue == GEMM_GELU else c
 
 
@@ -2670,15 +2652,15 @@ def linear_wgrad(g, x, with_bias=False, db=None, out_bias=None, leaf=False, dw=N
         dw = zeros_f32((M, N), g.device)
     if out_bias is not None:
         assert db is None and not with_bias and out_bias.dtype == torch.float32 and out_bias.numel() == N
-        check(_lib.lib().mobgt_linear_wgrad_bias(_p(g), g.stride(0), _p(x), x.stride(0), _p(out_bias.contiguous()), _p(dw), N, R, M, N,
-                                                 _DT[g.dtype], _stream()), "mobgt_linear_wgrad_bias")
+        _lib.call("mobgt_linear_wgrad_bias", _p(g), g.stride(0), _p(x), x.stride(0), _p(out_bias.contiguous()), _p(dw), N, R, M, N,
+                  _DT[g.dtype], _stream())
         return dw, None
     if db is None and with_bias:
         db = zeros_f32((M,), g.device)
     if leaf and _WGRAD_DEFER["on"] and M % 2 == 0 and N % 2 == 0:
         return _wgrad_defer(g, x, None, None, (1.0, 1.0, 1.0), dw, db, False), (db[:] if db is not None else None)
-    check(_lib.lib().mobgt_linear_wgrad(_p(g), g.stride(0), _p(x), x.stride(0), _p(dw), N, _p(db), R, M, N, _DT[g.dtype],
-                                        _stream()), "mobgt_linear_wgrad")
+    _lib.call("mobgt_linear_wgrad", _p(g), g.stride(0), _p(x), x.stride(0), _p(dw), N, _p(db), R, M, N, _DT[g.dtype],
+              _stream())
     return dw, db
 
 
@@ -2688,5 +2670,5 @@ def colsum(g):
     g = g.contiguous()
     R, C = g.shape
     out = zeros_f32((C,), g.device)
-    check(_lib.lib().mobgt_colsum(_p(g), _p(out), R, C, _DT[g.dtype], _stream()), "mobgt_colsum")
+    _lib.call("mobgt_colsum", _p(g), _p(out), R, C, _DT[g.dtype], _stream())
     return out

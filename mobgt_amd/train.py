@@ -553,11 +553,11 @@ class TrainStep:
         if self._step_base is None:                  # t = 1 on this very call; the counter advances once per step
             self._step_base = int(self.seed_dev.item()) - 1
         n = self.flat.flat.numel()
-        _lib.check(_lib.lib().mobgt_adamw_flat(_p(self.flat_params.tensor), _p(self.flat.flat), _p(self.exp_avg),
-                                               _p(self.exp_avg_sq), _p(self.shadow_flat), n, _p(self.lr_dev),
-                                               _p(self.sched_dev), _p(self.seed_dev), self._step_base, self.betas[0],
-                                               self.betas[1], self.eps,
-                                               float(self.model.weight_decay), _stream()), "mobgt_adamw_flat")
+        _lib.call("mobgt_adamw_flat", _p(self.flat_params.tensor), _p(self.flat.flat), _p(self.exp_avg),
+                  _p(self.exp_avg_sq), _p(self.shadow_flat), n, _p(self.lr_dev),
+                  _p(self.sched_dev), _p(self.seed_dev), self._step_base, self.betas[0],
+                  self.betas[1], self.eps,
+                  float(self.model.weight_decay), _stream())
 
     def _capturing(self, graph):
         """torch.cuda.graph on the trainer's stream.  With a process group, captures use the THREAD-LOCAL error mode: c10d's
@@ -622,9 +622,8 @@ class TrainStep:
         self.arena.off = 0
         ops.set_zero_arena(self.arena)             # valid from here to the end of this backward pass only
         lo, hi = (self._skip[1], self._skip[2]) if self._skip is not None else (0, 0)
-        _lib.check(_lib.lib().mobgt_step_prologue_skip(_p(self.flat.flat), self.flat.flat.numel(), lo, hi, _p(self.arena.buf),
-                                                       self.arena.buf.numel(), _p(self.seed_dev), _stream()),
-                   "mobgt_step_prologue_skip")
+        _lib.call("mobgt_step_prologue_skip", _p(self.flat.flat), self.flat.flat.numel(), lo, hi, _p(self.arena.buf),
+                  self.arena.buf.numel(), _p(self.seed_dev), _stream())
 
     def _fwd_bwd(self, batch, slot=None):
         self._prologue()
@@ -883,26 +882,25 @@ class TrainStep:
         part = self.partials if not self.ddp else None
         n = self.flat.flat.numel()
         if self.acc is not None:
-            _lib.check(_lib.lib().mobgt_grad_accumulate(_p(self.acc), _p(self.flat.flat), n, _p(part), _stream()),
-                       "mobgt_grad_accumulate")
+            _lib.call("mobgt_grad_accumulate", _p(self.acc), _p(self.flat.flat), n, _p(part), _stream())
         elif part is not None:                       # (k = 1: nothing to add, the norm of the flat gradient buffer itself)
-            _lib.check(_lib.lib().mobgt_grad_accumulate(_p(self.flat.flat), None, n, _p(part), _stream()), "mobgt_grad_accumulate")
+            _lib.call("mobgt_grad_accumulate", _p(self.flat.flat), None, n, _p(part), _stream())
 
     def _update_kernels(self):
         """[norm of the exchanged gradient,] finish (grad_norm, scale = coef / k, update counter + 1), AdamW on scale * acc (which
         leaves the accumulator zero)."""
         from . import _lib
         from .ops import _p, _stream
-        lib, n, g = _lib.lib(), self.flat.flat.numel(), self._gsrc
+        n, g = self.flat.flat.numel(), self._gsrc
         if self.partials is not None and self.ddp:
-            _lib.check(lib.mobgt_grad_accumulate(_p(g), None, n, _p(self.partials), _stream()), "mobgt_grad_accumulate")
-        _lib.check(lib.mobgt_grad_norm_finish(_p(self.partials), 0 if self.partials is None else self.partials.numel(),
-                                              1.0 / self.accumulate, self.clip_norm or 0.0, _p(self.grad_norm), _p(self.scale_dev),
-                                              _p(self.upd_dev), _stream()), "mobgt_grad_norm_finish")
-        _lib.check(lib.mobgt_adamw_flat_scaled(_p(self.flat_params.tensor), _p(g), _p(self.exp_avg), _p(self.exp_avg_sq),
-                                               _p(self.shadow_flat), n, _p(self.lr_dev), _p(self.sched_dev), _p(self.upd_dev), 0,
-                                               _p(self.scale_dev), 1 if self.acc is not None else 0, self.betas[0], self.betas[1],
-                                               self.eps, float(self.model.weight_decay), _stream()), "mobgt_adamw_flat_scaled")
+            _lib.call("mobgt_grad_accumulate", _p(g), None, n, _p(self.partials), _stream())
+        _lib.call("mobgt_grad_norm_finish", _p(self.partials), 0 if self.partials is None else self.partials.numel(),
+                  1.0 / self.accumulate, self.clip_norm or 0.0, _p(self.grad_norm), _p(self.scale_dev),
+                  _p(self.upd_dev), _stream())
+        _lib.call("mobgt_adamw_flat_scaled", _p(self.flat_params.tensor), _p(g), _p(self.exp_avg), _p(self.exp_avg_sq),
+                  _p(self.shadow_flat), n, _p(self.lr_dev), _p(self.sched_dev), _p(self.upd_dev), 0,
+                  _p(self.scale_dev), 1 if self.acc is not None else 0, self.betas[0], self.betas[1],
+                  self.eps, float(self.model.weight_decay), _stream())
 
     def _capture_micro(self, i, warm=True):
         if warm:

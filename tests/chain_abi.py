@@ -8,7 +8,7 @@ import torch
 from mobgt_amd import _lib
 from mobgt_amd.ops import _p, _stream
 
-EBADDIM, EALIGN = -1, -2              # MOBGT_EBADDIM, MOBGT_EALIGN
+EBADDIM, EALIGN = _lib.CONSTANTS["MOBGT_EBADDIM"], _lib.CONSTANTS["MOBGT_EALIGN"]
 SUM_NAMES = ("dnxw", "dnxb", "db2", "dn1w", "dn1b", "dbo")
 
 

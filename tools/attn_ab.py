@@ -11,11 +11,7 @@ names = ["ship"] + sys.argv[1:]
 handles = {}
 for n in names:
     path = _lib.LIB_PATH if n == "ship" else os.path.join(ROOT, "mobgt_amd", f"libmobgt_hip_ab_{n}.so")
-    h = ctypes.CDLL(path)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(h, name)
-        fn.restype, fn.argtypes = res, args
-    handles[n] = h
+    handles[n] = _lib.bind(ctypes.CDLL(path))
 _lib.lib()
 P = float(os.environ.get("P", 0.1))
 res = {n: [] for n in names}
