@@ -16,6 +16,7 @@ import torch
 
 from . import _lib, forms, ops
 from .ops import _p, _stream, _DT
+from .step_state import STEP
 
 
 _MM_OUT_DTYPE = [None]
@@ -192,31 +193,18 @@ def _k1_fwd(x, y, x1, w, b, z, z32, mean, rstd, R, C, p, seed, seed_dev, salt, a
 # first norm and runs the weight gradients as extra workgroups (csrc/chain.hip).  A parked entry that no layer picks up is
 # an error, raised when the backward pass ends -- never a silently incomplete gradient.  (forms "defer_tail")
 _DEFER_MAX_R = [4096]      # S-GOW: 1024 / 2048 / 4096 / 16384 -> 18.96 / 19.33 / 19.65 / 19.5 k check-ins/s
-_PENDING_TAIL = {}          # (graph task id, device index, address of dx1) -> parked work; see _pending_key
-_PENDING_CB = [None]        # graph task id for which the end-of-backward check is queued
-
-
-def _task_id():
-    """Id of the autograd graph task (one per top-level backward / autograd.grad call) this code runs under, -1 outside."""
-    fn = getattr(torch._C, "_current_graph_task_id", None)
-    return int(fn()) if fn is not None else -1
+# (STEP.layer_tails, keyed by _pending_key; STEP.tail_check_task; tails of a backward pass that died: STEP.drop_stale_tails)
 
 
 def _pending_key(t):
-    return (_task_id(), t.device.index, t.data_ptr())
+    return (ops.graph_task_id(), t.device.index, t.data_ptr())
 
 
-def _drop_stale_pending():
-    """Entries parked by a backward pass that is not the running one: that pass died before its end-of-backward callback
-    ran (an exception in some backward function -- the engine then skips the callbacks).  Their buffers belong to a graph
-    that no longer exists: drop them, never feed them to a kernel.  (An entry holds views of its buffers, so while it is
-    parked no other tensor can be allocated at its address: a key of the RUNNING task always names the tensor it was
-    parked under.)"""
-    tid = _task_id()
-    if _PENDING_CB[0] is not None and _PENDING_CB[0] != tid:
-        _PENDING_CB[0] = None
-    for k in [k for k in _PENDING_TAIL if k[0] != tid]:
-        del _PENDING_TAIL[k]
+def _park_tail(dx1, **work):
+    STEP.layer_tails[_pending_key(dx1)] = dict(dx1=dx1[:], **work)
+    if STEP.tail_check_task != ops.graph_task_id():
+        STEP.tail_check_task = ops.graph_task_id()
+        torch.autograd.Variable._execution_engine.queue_callback(_pending_check)
 
 
 def _complete_pending(pend):
@@ -240,16 +228,16 @@ def _pending_check():
     recognises it and the entry is still here: the weight gradients are completed, the input gradient cannot be repaired
     (the sum was taken without dqkv Wqkv) -- hence the error, never a silent result.  (Had dx1 arrived first, the engine
     accumulates in place into it and the hosted product lands on top: correct.)"""
-    tid = _task_id()
-    _PENDING_CB[0] = None
-    mine = [k for k in _PENDING_TAIL if k[0] == tid or tid == -1]
+    tid = ops.graph_task_id()
+    STEP.tail_check_task = None
+    mine = [k for k in STEP.layer_tails if k[0] == tid or tid == -1]
     if mine:
-        left = [_PENDING_TAIL.pop(k) for k in mine]
+        left = [STEP.layer_tails.pop(k) for k in mine]
         try:
             for pend in left:                    # finish the arithmetic, then say that the protocol was broken
                 _complete_pending(pend)
         finally:
-            _PENDING_TAIL.clear()
+            STEP.layer_tails.clear()
         raise RuntimeError("mobgt fused layer: a deferred input gradient was not consumed by the layer below "
                            "(was the layer's input used by something else as well?); set MOBGT_NO_DEFER_TAIL=1")
 
@@ -417,7 +405,7 @@ class _FusedLayerFn(torch.autograd.Function):
         ctx.chain_bwd = bool(use_chain and forms.on("chain_bwd") and cfg.packed_t is not None and (R <= 4096 or forms.on("chain_big"))
                              and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in cfg.packed_t))
         # the layer below produced this layer's qkv in ITS chain launch and will run chain_bwd: it can host what this layer's
-        # backward leaves undone (see _PENDING_TAIL)
+        # backward leaves undone (see STEP.layer_tails)
         ctx.below_hosts = bool(cfg.from_layer and qkv_pre is not None and ctx.chain_bwd and len(cfg.packed_t) > 3)
         if use_chain:               # everything row-local of the layer (+ the next layer's QKV projection) in one launch
             bf = dict(dtype=A, device=dev)
@@ -601,9 +589,9 @@ class _FusedLayerFn(torch.autograd.Function):
         wb = _WgradBatch()
         k_qkv, k_wo, k_w1, k_w2 = ctx.sinks                          # gradient sinks (or None)
         db1_in_wgrad = _wgrad_hip(A, F, C, R)                         # then b1's gradient rides on the dW1 kernel
-        if _PENDING_TAIL or _PENDING_CB[0] is not None:
-            _drop_stale_pending()
-        pend = _PENDING_TAIL.pop(_pending_key(dout), None) if _PENDING_TAIL else None
+        if STEP.layer_tails or STEP.tail_check_task is not None:
+            STEP.drop_stale_tails(ops.graph_task_id())
+        pend = STEP.layer_tails.pop(_pending_key(dout), None) if STEP.layer_tails else None
         # (the 64-row backward chain, R > 4096: b1's gradient is a column sum of du behind it -- the weight gradients are the
         #  library's there)
         chain_b = getattr(ctx, "chain_bwd", False) and (db1_in_wgrad or R > 4096) and not stock
@@ -687,10 +675,7 @@ class _FusedLayerFn(torch.autograd.Function):
             # past 4 096 rows: the 64-row chain of the layer below finishes dx = dx1 + dqkv Wqkv in front of its first norm (a
             # 20 us library GEMM otherwise); the weight gradients are the library's and are issued here
             wb.flush(tail=None)
-            _PENDING_TAIL[_pending_key(dx1)] = dict(dx1=dx1[:], dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=[], R=R, big=True)
-            if _PENDING_CB[0] != _task_id():
-                _PENDING_CB[0] = _task_id()
-                torch.autograd.Variable._execution_engine.queue_callback(_pending_check)
+            _park_tail(dx1, dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=[], R=R, big=True)
             rode = True
             dx = dx1
         elif defer:
@@ -698,20 +683,17 @@ class _FusedLayerFn(torch.autograd.Function):
             # (parked as FRESH views of the gradient buffers: autograd's AccumulateGrad clones a returned gradient that anything
             # else still references, and the clone -- taken before the buffers are filled -- would later be copied over them)
             items = [(g_, x_, dw_[:], db_[:] if db_ is not None else None) for g_, x_, dw_, db_ in wb.items]
-            _PENDING_TAIL[_pending_key(dx1)] = dict(dx1=dx1[:], dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=items, R=R)
+            _park_tail(dx1, dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=items, R=R)
             wb.items = []
-            if _PENDING_CB[0] != _task_id():
-                _PENDING_CB[0] = _task_id()
-                torch.autograd.Variable._execution_engine.queue_callback(_pending_check)
             rode = True
             dx = dx1
-        elif (stock and ops._WGRAD_DEFER["on"] and wb.items and R <= _DEFER_MAX_R[0] and all(k is not None for k in ctx.sinks)
+        elif (stock and STEP.wgrad_on and wb.items and R <= _DEFER_MAX_R[0] and all(k is not None for k in ctx.sinks)
               and all(g_.dtype == torch.bfloat16 and x_.dtype == torch.bfloat16 for g_, x_, _, _ in wb.items)):
             # stock variant inside a train step: nothing downstream reads a weight gradient and all four land in their sinks, so
             # they join the step's ONE grouped launch (ops.flush_deferred_wgrads) instead of one 7 us launch per layer -- parked
             # as FRESH views (see above: AccumulateGrad clones a returned gradient that anything else still references)
             for g_, x_, dw_, db_ in wb.items:
-                ops._WGRAD_DEFER["items"].append((g_, x_, None, None, (1.0, 1.0, 1.0), dw_[:], db_[:] if db_ is not None else None, False))
+                STEP.wgrad_items.append((g_, x_, None, None, (1.0, 1.0, 1.0), dw_[:], db_[:] if db_ is not None else None, False))
             wb.items = []
             rode = False
         else:
@@ -765,9 +747,9 @@ class _FusedLayerFn(torch.autograd.Function):
         dnnw, dnnb = (dst(ctx.nn_sinks[0]), dst(ctx.nn_sinks[1])) if nnw is not None else (None, None)
         wb = _WgradBatch()
         k_qkv, k_wo, k_w1, k_w2 = ctx.sinks
-        if _PENDING_TAIL or _PENDING_CB[0] is not None:
-            _drop_stale_pending()
-        pend = _PENDING_TAIL.pop(_pending_key(dout), None) if _PENDING_TAIL else None
+        if STEP.layer_tails or STEP.tail_check_task is not None:
+            STEP.drop_stale_tails(ops.graph_task_id())
+        pend = STEP.layer_tails.pop(_pending_key(dout), None) if STEP.layer_tails else None
         if pend is not None and not (pend.get("preln") and nnw is not None and pend["R"] == R):
             _complete_pending(pend)                    # (not this layer's kind of guest: finish it as its own launches)
             pend = None
@@ -794,19 +776,16 @@ class _FusedLayerFn(torch.autograd.Function):
         dwqkv = wb.add(dqkv2, xa, db=dbqkv, sink=k_qkv)
         # the four weight gradients: inside a train step they join the step's ONE grouped launch (as the separate-launch stock
         # layer's do), else their own grouped launch now
-        if (ops._WGRAD_DEFER["on"] and wb.items and R <= _DEFER_MAX_R[0] and all(k_ is not None for k_ in ctx.sinks)
+        if (STEP.wgrad_on and wb.items and R <= _DEFER_MAX_R[0] and all(k_ is not None for k_ in ctx.sinks)
                 and all(g_.dtype == torch.bfloat16 and x_.dtype == torch.bfloat16 for g_, x_, _, _ in wb.items)):
             for g_, x_, dw_, db_ in wb.items:
-                ops._WGRAD_DEFER["items"].append((g_, x_, None, None, (1.0, 1.0, 1.0), dw_[:], db_[:] if db_ is not None else None, False))
+                STEP.wgrad_items.append((g_, x_, None, None, (1.0, 1.0, 1.0), dw_[:], db_[:] if db_ is not None else None, False))
             wb.items = []
         else:
             wb.flush()
         if ctx.chained_in:
             # nothing more for this layer: the layer below opens its chain launch with  dx2 = dx1 + norm'(dqkv Wqkv)
-            _PENDING_TAIL[_pending_key(dx1)] = dict(dx1=dx1[:], dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=[], R=R, preln=True)
-            if _PENDING_CB[0] != _task_id():
-                _PENDING_CB[0] = _task_id()
-                torch.autograd.Variable._execution_engine.queue_callback(_pending_check)
+            _park_tail(dx1, dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=[], R=R, preln=True)
             dx = dx1
         else:                                                           # back through this layer's own self_attention_norm
             dz0 = ops.layer_gemm(dqkv2, s_wqkv, None, True)
@@ -826,5 +805,5 @@ def fused_encoder_layer(x, pack, cfg, shadows, params, xa_pre=None, qkv_pre=None
         out._mobgt_act = cfg.out_act          # picked up by the next fused layer (same Python tensor object)
     if cfg.out_qkv is not None:
         out._mobgt_qkv = cfg.out_qkv          # ... and its QKV projection, already computed by this layer's chain kernel
-        out._mobgt_from_layer = True          # (the consumer's backward may leave its tail to this layer's: _PENDING_TAIL)
+        out._mobgt_from_layer = True          # (the consumer's backward may leave its tail to this layer's: STEP.layer_tails)
     return out

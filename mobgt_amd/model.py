@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import forms, ops
+from .step_state import STEP
 
 
 def init_bert_params(module, n_layers):
@@ -243,7 +244,7 @@ def fused_layer_forward(layer, variant, x, attn_bias, n1, nx, next_layer=None):
         else:
             # pre-LN (model.py:479-489): the next layer's self_attention_norm AND its QKV projection ride in this layer's chain
             # launch; that layer then has no norm / projection of its own and leaves the norm's backward to this layer's chain
-            # (fused_layer._PENDING_TAIL) -- so not across a cut of the trainer's backward pass, and not without deferral
+            # (STEP.layer_tails) -- so not across a cut of the trainer's backward pass, and not without deferral
             bwd_ok = (not torch.is_grad_enabled()) or (getattr(nxt, "_packed_t_fresh", False) and getattr(layer, "_packed_t_fresh", False))
             if forms.on("defer_tail") and not getattr(nxt, "_mobgt_cut", False) and getattr(layer, "_packed_fresh", False) and bwd_ok:
                 cfg.next_qkv = (nxt._packed[0], nxt._shadows[1])
@@ -278,13 +279,9 @@ def fused_layer_forward(layer, variant, x, attn_bias, n1, nx, next_layer=None):
     return out
 
 
-_PENDING_PACK = []          # jobs of a deferred weight pack (see pack_layer_weights(defer=True))
-
-
 def take_pending_pack():
-    """The deferred pack jobs, handed to the launch that will carry them (modelGNN._SmallGcnFn); the list is emptied."""
-    jobs = list(_PENDING_PACK)
-    del _PENDING_PACK[:]
+    """The deferred pack jobs (pack_layer_weights(defer=True)) for the launch that will carry them (modelGNN._SmallGcnFn)."""
+    jobs, STEP.weight_pack = STEP.weight_pack, []
     return jobs
 
 
@@ -456,7 +453,7 @@ def pack_layer_weights(layers, defer=False, rows=None):
     #  S-BIG -- 18.9 M -- the passengers outlasted the network: 102 us for 28 + 37, measured)
     small = sum(j[2] * j[3] for j in jobs) <= (8 << 20)
     if defer and jobs and len(jobs) <= 96 and small and forms.on("pack_passenger"):
-        _PENDING_PACK.extend(jobs)
+        STEP.weight_pack.extend(jobs)
     else:
         _launch_pack(jobs)
 

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from torch.nn import Parameter
 
 from . import forms
+from .step_state import STEP
 
 
 def mm_tn_splitk(x, g, max_chunks=32, bf16_operands=False, dw=None):
@@ -280,7 +281,7 @@ class _ConvActFn(torch.autograd.Function):
             dw_dst = torch.as_strided(k_w, (t.shape[1], weight.shape[1]), (weight.shape[1], 1))
         dW = ops.linear_wgrad_masked(t, g, x_mask=y, mask_vals=ctx.mv, db=db, db_of_x=True, leaf=True, dw=dw_dst)   # t^T (g * m(y)), db = colsum
         dW = dW[:weight.shape[0]]                                                                # (rows of the zero padding)
-        db = db[:]                                                                               # (a fresh view: see ops.wgrad_deferral)
+        db = db[:]                                                                               # (a fresh view: see ops.recording_wgrads)
         dx = None
         if ctx.adj is not None and ctx.needs_input_grad[0]:
             # dt = (g * m(y)) W^T [P, in] leaves the GEMM transposed, scaled by 1/(deg+1) and in bf16 -- the operand of
@@ -501,7 +502,7 @@ def prelaunch_small_gcn(gcn, x, adj, adj_x, adj_t, same_stream=False):
     salt = (0x2000 + g2.out_features) & 0xFFFFFFFF
     with torch.autocast(device_type="cuda", enabled=False):
         keep, out = _small_gcn_launch(adj_x, adj, ws, float(gcn.leaky_relu.negative_slope), float(p_drop), seed, seed_dev, salt)
-    gcn._prelaunched = ((float(p_drop), seed, id(seed_dev), salt), (keep, out, None))
+    STEP.gcn_prelaunched[id(gcn)] = ((float(p_drop), seed, id(seed_dev), salt), (keep, out, None))
     return True
 
 
@@ -679,8 +680,8 @@ class GCN(nn.Module):
             p_drop = self.dropout if self.training else 0.0
             g0, g1, g2 = self.gcn
             salt = (0x2000 + g2.out_features) & 0xFFFFFFFF
-            pre = self.__dict__.pop("_prelaunched", None)
-            seed_dev = ops._DROPOUT_STATE["seed_dev"]
+            pre = STEP.gcn_prelaunched.pop(id(self), None)
+            seed_dev = ops.dropout_seed(0.0)[1]                       # (p = 0: the device counter, no host seed drawn)
             if pre is not None and (pre[0][0], pre[0][2], pre[0][3]) == (float(p_drop), id(seed_dev), salt):
                 seed = pre[0][1]                                        # (the masks the prelaunched pass drew)
             else:
@@ -728,7 +729,7 @@ class GCN(nn.Module):
                     yt = xt_workspace(pre_pad.device, pre_pad.shape[0], gc.out_features, slot=0)
                     with torch.autocast(device_type="cuda", enabled=False):
                         x = _ConvActFn.apply(None, pre_pad, gc.weight, gc.bias, None, float(self.leaky_relu.negative_slope),
-                                             float(p_drop), seed, seed_dev, salt, ops._OutRef(yt))
+                                             float(p_drop), seed, seed_dev, salt, ops.OutRef(yt))
                     x._mobgt_xt = yt
                     continue
                 if (pre is None and mask_adj is not None and not isinstance(adj, CsrAdj) and x.dtype == torch.float32
@@ -739,7 +740,7 @@ class GCN(nn.Module):
                     with torch.autocast(device_type="cuda", enabled=False):
                         x = _ConvActFn.apply(None if pre is not None else x, pre, gc.weight, gc.bias, mask_adj,
                                              float(self.leaky_relu.negative_slope), float(p_drop), seed, seed_dev, salt,
-                                             ops._OutRef(xt) if xt is not None else None)
+                                             ops.OutRef(xt) if xt is not None else None)
                     continue
                 h = gc(x, adj, pre, adj_t, bias=False, mask_adj=mask_adj)
                 # when the next layer is a bitmask product, the activation also leaves its result in that product's operand

@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import forms, ops
+from .step_state import STEP
 from .lr import PolynomialDecayLR
 from .model import (FeedForwardNetwork, MultiHeadAttention, hop_table_from, no_grad_row0, fused_layer_forward,
                     refresh_shadows, flush_pending_pack)
@@ -496,11 +497,12 @@ class Graphormer(nn.Module):
             bias = self.assemble_bias(batched_data, hop=hop)
             ops.front_small_gemm_flush()
             output = self.node_features(batched_data, indices=indices)
-        finally:
-            # (a prelaunched result nobody adopted -- an exception on the way -- must not meet a later, direct call of the GCN;
-            #  the same for a small GEMM no bias launch took along)
-            self.poi_cat_model.__dict__.pop("_prelaunched", None)
-            ops.front_small_gemm_drop()
+        except BaseException:
+            ops.drop_parked()
+            raise
+        # (a prelaunched result nobody adopted must not meet a later, direct call of the GCN; the same for a small GEMM's result)
+        STEP.gcn_prelaunched.pop(id(self.poi_cat_model), None)
+        STEP.front_sgemm.pop("done", None)
         ops.trace_nan("x0", output)
         self._bias_pack, self._cuts = bias, {}
         for li, enc_layer in enumerate(self.layers):                                           # :1347-1352

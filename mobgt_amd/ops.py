@@ -2,6 +2,7 @@
 HIP stream go in, autograd comes out.  PyTorch is plumbing here (memory, streams, autograd graph);
 all arithmetic of the hot path happens in libmobgt_hip.so.  No CPU fallback exists.
 """
+import contextlib
 import ctypes
 import math
 
@@ -9,6 +10,7 @@ import torch
 
 from . import _lib, forms
 from ._lib import F32, BF16, I64, I32, I16, U8, check
+from .step_state import STEP
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 _IT = {torch.int64: I64, torch.int32: I32, torch.int16: I16, torch.uint8: U8}
@@ -122,11 +124,8 @@ class ZeroArena:
         return t
 
 
-_ARENA = [None]
-
-
 def set_zero_arena(arena):
-    _ARENA[0] = arena
+    STEP.zero_arena = arena
 
 
 def zeros_f32(shape, device):
@@ -134,7 +133,7 @@ def zeros_f32(shape, device):
     n = 1
     for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)):
         n *= int(d)
-    a = _ARENA[0]
+    a = STEP.zero_arena
     if a is not None and a.buf.device == torch.device(device):
         t = a.take(n)
         if t is not None:
@@ -143,18 +142,12 @@ def zeros_f32(shape, device):
 
 
 # ---- gradient sinks: where a trainer wants a parameter's gradient written (train.FlatGrads) ------------------
-_GRAD_SINKS = {}
-
-
 def set_grad_sinks(params, views):
     """params[i]'s gradient belongs at views[i] (a slice of the trainer's flat gradient buffer, zeroed before every
     backward).  Kernels that produce a large gradient write it THERE and return that view, so the trainer's
     gather has nothing to copy for it.  Keyed by the parameter's storage address; `None` clears."""
     import weakref
-    _GRAD_SINKS.clear()
-    if params is not None:
-        for p, v in zip(params, views):
-            _GRAD_SINKS[p.data_ptr()] = (weakref.ref(p), v)
+    STEP.grad_sinks = {p.data_ptr(): (weakref.ref(p), v) for p, v in zip(params, views)} if params is not None else {}
 
 
 # A sink is handed to the op that asks for it in its forward and written by that op's backward as if it were its own
@@ -164,16 +157,13 @@ def set_grad_sinks(params, views):
 # would add the two views of it.  The trainer's dry run counts the requests per forward pass
 # (`sink_census_*`, train.used_parameters) and leaves such parameters out of `set_grad_sinks`: they get fresh buffers,
 # autograd sums them, the gather copies the sum.
-_SINK_CENSUS = {"on": False, "cur": {}, "max": {}}
-
-
 def sink_census_begin():
-    _SINK_CENSUS.update(on=True, cur={}, max={})
+    STEP.sink_census.update(on=True, cur={}, max={})
 
 
 def sink_census_pass():
     """A forward pass ends / the next one begins: fold this pass's request counts into the per-parameter maximum."""
-    c = _SINK_CENSUS
+    c = STEP.sink_census
     for k, n in c["cur"].items():
         if n > c["max"].get(k, 0):
             c["max"][k] = n
@@ -183,17 +173,18 @@ def sink_census_pass():
 def sink_census_end():
     """-> {id(parameter): most requests seen in one forward pass}"""
     sink_census_pass()
-    _SINK_CENSUS["on"] = False
-    out, _SINK_CENSUS["max"] = _SINK_CENSUS["max"], {}
+    c = STEP.sink_census
+    out, c["on"], c["max"] = c["max"], False, {}
     return out
 
 
 def grad_sink(param):
     """The registered destination of `param`'s gradient, or None.  The entry must belong to this very tensor
     object: addresses get reused, and a stale entry would redirect some other model's gradient."""
-    if _SINK_CENSUS["on"]:
-        _SINK_CENSUS["cur"][id(param)] = _SINK_CENSUS["cur"].get(id(param), 0) + 1
-    e = _GRAD_SINKS.get(param.data_ptr())
+    c = STEP.sink_census
+    if c["on"]:
+        c["cur"][id(param)] = c["cur"].get(id(param), 0) + 1
+    e = STEP.grad_sinks.get(param.data_ptr())
     if e is not None and e[0]() is param and e[1].shape == param.shape:
         return e[1]
     return None
@@ -307,25 +298,21 @@ def pack_bias(attn_bias, G, H, T, dtype=None):
 # The bias tables' backward (mobgt_build_bias_bwd, 21.6 us of the S-FSQ step) depends on nothing but the dBias slices, which
 # are complete once the last attention backward has run -- long before autograd reaches this node (created first, run last).
 # The category GCN's backward launch (19 compute units busy for 25 us, modelGNN._SmallGcnFn) comes in between and carries it
-# as passenger workgroups: _BuildBiasFn.forward leaves a job here, the GCN's backward takes it (take_bias_bwd_job) and stores
-# the four gradients in it, _BuildBiasFn.backward then only hands them out.  MOBGT_NO_BIAS_BWD_PASSENGER=1: own launch.
-_BIAS_BWD_JOB = {}
+# as passenger workgroups: _BuildBiasFn.forward leaves a job (STEP.bias_bwd_job), the GCN's backward takes it (take_bias_bwd_job) and
+# stores the four gradients in it, _BuildBiasFn.backward then only hands them out.  MOBGT_NO_BIAS_BWD_PASSENGER=1: own launch.
 
 
 # Two tiny front-of-step launches -- the hop table's forward and the index derivation of the node features, 4.8 us each, all ramp --
 # ride in the category GCN's forward launch as well: inside front_deferral(True) their ops only allocate their outputs and leave a
 # job (take_front_jobs); the model calls the one-launch GCN next and flush_front() behind it (a job nobody took is launched
-# alone there).  MOBGT_NO_FRONT_PASSENGERS=1: own launches.
-_FRONT_DEFER = {"on": False, "hop": None, "ni": None}
-
-
+# alone there).  MOBGT_NO_FRONT_PASSENGERS=1: own launches.  (STEP.front_on, front_hop, front_ni)
 def front_deferral(on):
-    _FRONT_DEFER["on"] = bool(on) and forms.on("front_passengers")
+    STEP.front_on = bool(on) and forms.on("front_passengers")
 
 
 def take_front_jobs():
-    hop, ni = _FRONT_DEFER["hop"], _FRONT_DEFER["ni"]
-    _FRONT_DEFER["hop"] = _FRONT_DEFER["ni"] = None
+    hop, ni = STEP.front_hop, STEP.front_ni
+    STEP.front_hop = STEP.front_ni = None
     return hop, ni
 
 
@@ -347,7 +334,7 @@ def _bias_bwd_alloc(shapes, dev, sinks=(None, None, None, None)):
 def take_bias_bwd_job():
     """The pending bias-backward job if its inputs are complete and it is the instantiation the passenger form covers
     (int16 indices, uint8 edge ids, 8 heads, one edge feature, <= 20 hops, a short batch); None otherwise."""
-    job = _BIAS_BWD_JOB.pop("cur", None)
+    job, STEP.bias_bwd_job = STEP.bias_bwd_job, None
     if job is None or not forms.on("bias_bwd_passenger"):
         return None
     pack = job["pack"]()
@@ -396,9 +383,8 @@ class _BuildBiasFn(torch.autograd.Function):
         import weakref
         # (weak: the pack's token belongs to this forward pass's autograd graph, which must not outlive its backward)
         ctx.job = dict(pack=weakref.ref(pack), args=args, idx=ctx.idx, shapes=ctx.shapes, done=None, sinks=sinks)
-        _BIAS_BWD_JOB.pop("cur", None)
-        if pack.needs_grad:                        # (build_bias() looked at the grad mode: it is off inside Function.forward)
-            _BIAS_BWD_JOB["cur"] = ctx.job
+        # (build_bias() looked at the grad mode: it is off inside Function.forward)
+        STEP.bias_bwd_job = ctx.job if pack.needs_grad else None
         return zeros_f32((1,), rel_table.device)
 
     @staticmethod
@@ -412,8 +398,8 @@ class _BuildBiasFn(torch.autograd.Function):
                 torch.cuda.current_stream(pack.bias.device).wait_event(ev)
             ctx.job["done"] = None
             return d_rel, d_poi, d_hop, d_vd, None, None, None, None, None, None, None
-        if _BIAS_BWD_JOB.get("cur") is ctx.job:
-            del _BIAS_BWD_JOB["cur"]
+        if STEP.bias_bwd_job is ctx.job:
+            STEP.bias_bwd_job = None
         d_rel, d_poi, d_hop, d_vd = _bias_bwd_alloc(ctx.shapes, dev, ctx.job.get("sinks", (None,) * 4))
         if pack.dbias is not None:
             attn_bias, rel_pos, poi_pos, edge_input = ctx.idx
@@ -447,7 +433,7 @@ def build_bias(attn_bias, rel_pos, poi_pos, edge_input, rel_table, poi_table, ho
 
 
 # -------------------------------------------------------------------------------------- attention
-# T > 64, bf16: one-pass backward (round 4); MOBGT_ATTN_TWO_PASS=1: the two passes.  bench.py reads `ops._ATTN_ONE_PASS[0]` to
+# T > 64, bf16: one-pass backward (round 4); MOBGT_ATTN_TWO_PASS=1: the two passes.  bench.py reads `_ATTN_ONE_PASS[0]` to
 # name the kernel it measured and no pull request edits bench.py: this read-only view onto the registry keeps that spelling (the
 # one alias that stays; _attn_bwd reads it too, so the tests that replace the attribute with a list still steer the dispatch).
 _ATTN_ONE_PASS = type("_AttnOnePassView", (), {"__getitem__": lambda self, i: forms.on("attn_one_pass")})()
@@ -556,7 +542,7 @@ _SIDE_STREAMS = {}
 
 
 def _bias_bwd_beside(pack):
-    job = _BIAS_BWD_JOB.get("cur")
+    job = STEP.bias_bwd_job
     if (job is None or not forms.on("bias_bwd_beside") or job["pack"]() is not pack or not pack.sliced or pack.dbias is None
             or pack.n_use < 1 or pack.n_bwd < pack.n_use or job["done"] is not None):
         return
@@ -568,7 +554,7 @@ def _bias_bwd_beside(pack):
     side = _SIDE_STREAMS.get(dev)
     if side is None:
         side = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev)
-    del _BIAS_BWD_JOB["cur"]
+    STEP.bias_bwd_job = None
     outs, args = bias_bwd_job_args(job)             # (allocated on the main stream: zero-filled sinks / arena views)
     fork = torch.cuda.Event()
     fork.record(main)
@@ -725,10 +711,10 @@ class _HopTableFn(torch.autograd.Function):
         ew, dw = edge_weight.contiguous(), edge_dis_weight.contiguous()
         tab = torch.empty(D, E, H, dtype=torch.float32, device=ew.device)
         args = [_p(ew), _p(dw), _p(tab), D, E, H, int(fp16_roundtrip)]
-        if _FRONT_DEFER["on"]:
-            if _FRONT_DEFER["hop"] is not None:
+        if STEP.front_on:
+            if STEP.front_hop is not None:
                 flush_front()
-            _FRONT_DEFER["hop"] = (args, (ew, dw, tab))          # (rides in the category GCN's forward launch)
+            STEP.front_hop = (args, (ew, dw, tab))          # (rides in the category GCN's forward launch)
         else:
             _lib.call("mobgt_hop_table_fwd", *args, _stream())
         ctx.save_for_backward(ew, dw)
@@ -748,20 +734,24 @@ class _HopTableFn(torch.autograd.Function):
         # (parked only into a FREE slot and only when both gradients land in sinks: a second hop table in the same backward pass --
         #  two models, two tables -- would overwrite the first one's entry, whose gradient would then never be computed, and a
         #  buffer allocated here would reach autograd before the deferred launch has filled it: ADVICE r4)
-        park = _WGRAD_DEFER["on"] and k_e is not None and k_d is not None
-        if (park and "hop" not in _WGRAD_DEFER and H == 8 and E <= 256 and dtab.data_ptr() % 16 == 0 and dw.data_ptr() % 16 == 0):
+        park = STEP.wgrad_on and k_e is not None and k_d is not None
+        if (park and STEP.wgrad_hop is None and H == 8 and E <= 256 and dtab.data_ptr() % 16 == 0 and dw.data_ptr() % 16 == 0):
             # rides in the step's grouped weight-gradient launch (flush_deferred_wgrads): nothing but the optimizer reads these
-            _WGRAD_DEFER["hop"] = (dtab, ew, dw, d_ew, d_dw, D, E, rt)
+            STEP.wgrad_hop = (dtab, ew, dw, d_ew, d_dw, D, E, rt)
             return d_ew[:], d_dw[:], None, None, None
-        if (park and "hop_wide" not in _WGRAD_DEFER and H == 8 and E <= 2048 and dtab.data_ptr() % 16 == 0 and dw.data_ptr() % 16 == 0
+        if (park and STEP.wgrad_hop_wide is None and H == 8 and E <= 2048 and dtab.data_ptr() % 16 == 0 and dw.data_ptr() % 16 == 0
                 and forms.on("stock_tail")):
             # too many edge ids for the grouped launch's hop slot (the stock variant's 1 537): parked until the flush, where it
             # shares ONE grid with the backward of the stock encoder input when that is parked too (csrc/layer.hip stock_tail_kernel)
-            _WGRAD_DEFER["hop_wide"] = (dtab, ew, dw, d_ew, d_dw, D, E, rt)
+            STEP.wgrad_hop_wide = (dtab, ew, dw, d_ew, d_dw, D, E, rt)
             return d_ew[:], d_dw[:], None, None, None
-        _lib.call("mobgt_hop_table_bwd", _p(dtab), _p(ew), _p(dw), _p(d_ew), _p(d_dw), D, E, H, rt,
-                  _stream())
+        _hop_table_bwd((dtab, ew, dw, d_ew, d_dw, D, E, rt), H)
         return d_ew, d_dw, None, None, None
+
+
+def _hop_table_bwd(job, H=8):
+    dtab, ew, dw, d_ew, d_dw, D, E, rt = job
+    _lib.call("mobgt_hop_table_bwd", _p(dtab), _p(ew), _p(dw), _p(d_ew), _p(d_dw), D, E, H, rt, _stream())
 
 
 def hop_table(edge_weight, edge_dis_weight, H, D, fp16_roundtrip=False):
@@ -874,7 +864,7 @@ def skinny_linear_gtl_ok(x, weight):
 
 def skinny_linear_gtl(x, weight, bias, targets, alpha=0.25, target_offset=0, logits_out=None):
     """gradient_tail_loss(F.linear(x, weight, bias), targets, alpha, target_offset) for the classifier head (G <= 16 rows).
-    `logits_out`: an _OutRef whose `.t` receives the logits (detached), else they are never stored."""
+    `logits_out`: an OutRef whose `.t` receives the logits (detached), else they are never stored."""
     _require_cuda(x, weight, targets)
     return _SkinnyLinearGtlFn.apply(x, weight, bias, targets[: x.shape[0]].reshape(-1), alpha, target_offset, logits_out)
 
@@ -1361,10 +1351,10 @@ def node_index(x, time_normal, poi2cat, rows_only, in_degree=None, out_degree=No
         deg_dt = _IT[in_degree.dtype]
     args = [_p(x), _IT[x.dtype], x.stride(0), x.stride(1), _p(time_normal), time_normal.stride(0), time_normal.stride(1), _p(poi2cat),
             _p(in_degree), _p(out_degree), deg_dt, _p(idx), _p(real), G, N, int(bool(rows_only))]
-    if _FRONT_DEFER["on"]:
-        if _FRONT_DEFER["ni"] is not None:
+    if STEP.front_on:
+        if STEP.front_ni is not None:
             flush_front()
-        _FRONT_DEFER["ni"] = (args, (x, time_normal, poi2cat, in_degree, out_degree, idx, real))     # (see front_deferral)
+        STEP.front_ni = (args, (x, time_normal, poi2cat, in_degree, out_degree, idx, real))     # (see front_deferral)
     else:
         _lib.call("mobgt_node_index", *args, _stream())
     return idx, real
@@ -1433,20 +1423,17 @@ _ROW0_PENDING = {}      # table data_ptr -> [W] f32 gradient of its row 0 produc
 # switches it on when the last node can take the fused launch), the first three only ALLOCATE their outputs and record their
 # launch; _AssembleTokensFn then issues mobgt_token_fwd_chain, which fills every one of those buffers -- or, if what was
 # recorded is not the chain it knows, `flush_token_fwd()` issues the recorded launches one by one.  The autograd graph, the saved
-# tensors and therefore the whole backward pass are those of the separate launches.
-_TOKEN_FWD = {"on": False, "gather": None, "f2": None, "f4": None, "fused_calls": 0}
-
-
+# tensors and therefore the whole backward pass are those of the separate launches.  (STEP.token_fwd_on, token_fwd)
 def token_fwd_deferral(on):
     """Switch the recording on / off.  Switching it (either way) first launches whatever is still recorded."""
     flush_token_fwd()
-    _TOKEN_FWD["on"] = bool(on) and forms.on("token_fwd_chain") and not _NAN_TRACE["on"]
+    STEP.token_fwd_on = bool(on) and forms.on("token_fwd_chain") and not _NAN_TRACE["on"]
 
 
 def flush_token_fwd():
     """Issue the recorded launches separately, in order (the fallback of the fused launch)."""
     for k in ("gather", "f2", "f4"):
-        rec, _TOKEN_FWD[k] = _TOKEN_FWD[k], None
+        rec = STEP.token_fwd.pop(k, None)
         if rec is not None:
             rec["launch"]()
 
@@ -1470,8 +1457,8 @@ class _GatherMultiFn(torch.autograd.Function):
                 (ci * n)(*[t.shape[1] for t in tables]), (ci * n)(*[sp[1] for sp in spec]), (ci * n)(*[int(sp[2]) for sp in spec]),
                 (vp * n)(*[outs[sp[0]].data_ptr() for sp in spec]), (i64 * n)(*[outs[sp[0]].stride(0) for sp in spec]), R,
                 _IT[idx[0].dtype], 0, None, 0, _stream())
-        if _TOKEN_FWD["on"] and _TOKEN_FWD["gather"] is None and len(outs) == 3 and all(i_.dtype == idx[0].dtype for i_ in idx):
-            _TOKEN_FWD["gather"] = dict(launch=launch, tables=tables, idx=idx, spec=spec, outs=outs, R=R)     # (see token_fwd_deferral)
+        if STEP.token_fwd_on and "gather" not in STEP.token_fwd and len(outs) == 3 and all(i_.dtype == idx[0].dtype for i_ in idx):
+            STEP.token_fwd["gather"] = dict(launch=launch, tables=tables, idx=idx, spec=spec, outs=outs, R=R)     # (see token_fwd_deferral)
         else:
             launch()
         ctx.idx, ctx.spec, ctx.n = idx, spec, n
@@ -1575,11 +1562,11 @@ class _StockTokensFn(torch.autograd.Function):
         y = torch.empty(G, N + 1, C, dtype=torch.float32, device=atom.device)
         tok = (_p(x), _p(din), _p(dout), _IT[x.dtype], _IT[din.dtype], _p(atom), _p(indeg), _p(outdeg), _p(gtok), _p(y),
                G, N, C, atom.shape[0], indeg.shape[0], outdeg.shape[0], p, seed, _p(seed_dev), salt)
-        hop, ni = take_front_jobs() if _FRONT_DEFER["on"] else (None, None)
+        hop, ni = take_front_jobs() if STEP.front_on else (None, None)
         if ni is not None:                                       # (not a job of the stock model: launched alone)
             _lib.call("mobgt_node_index", *ni[0], _stream())
         jobs = []
-        if _FRONT_DEFER["on"]:
+        if STEP.front_on:
             from .model import take_pending_pack
             jobs = take_pending_pack()
         if hop is not None or jobs:
@@ -1618,11 +1605,11 @@ class _StockTokensFn(torch.autograd.Function):
                 _p(grads[3]), G, N, C, shapes[0][0], shapes[1][0], shapes[2][0], int(padding_idx), p, seed, _p(seed_dev), salt]
         in_sinks = all((not need) or (k is not None and tuple(k.shape) == tuple(sh))
                        for need, k, sh in zip(ctx.needs_input_grad[3:7], ctx.sinks, shapes))
-        if _WGRAD_DEFER["on"] and in_sinks and "stock_tok" not in _WGRAD_DEFER and forms.on("stock_tail"):
+        if STEP.wgrad_on and in_sinks and STEP.wgrad_stock_tok is None and forms.on("stock_tail"):
             # trainer's backward, every table gradient lands in its sink: nothing reads them before the optimizer, so the launch is
             # parked until the flush and shares ONE grid with the hop table's backward there (mobgt_stock_tail_bwd); what
             # autograd gets back are fresh views (AccumulateGrad clones a returned gradient something else still references)
-            _WGRAD_DEFER["stock_tok"] = (args, (dy, x, din, dout, seed_dev, grads))
+            STEP.wgrad_stock_tok = (args, (dy, x, din, dout, seed_dev, grads))
             return (None, None, None, *[g_[:] if g_ is not None else None for g_ in grads], None, None, None, None, None)
         _lib.call("mobgt_stock_tokens_bwd", *args, _stream())
         return (None, None, None, *grads, None, None, None, None, None)
@@ -1740,7 +1727,7 @@ def gradient_tail_loss(logits, targets, alpha=0.25, target_offset=0):
 
 
 # ------------------------------------------------------------------------------- small linear layers
-class _OutRef:
+class OutRef:
     """A destination buffer handed to an autograd Function as a plain Python object (not as a tensor input)."""
 
     def __init__(self, t):
@@ -1752,15 +1739,11 @@ class _OutRef:
 # x4 = [f2 | cat] <- pt).  Inside the trainer's backward (weight gradients deferred to the grouped launch) they co-operate: the
 # first two only PARK their work and return the buffers their results will live in, the third launches mobgt_token_bwd_chain,
 # which fills all of them.  The consumers of those buffers (the weight-gradient group, the gathers' scatter) run later in
-# stream order.  flush_deferred_wgrads() raises if a parked chain was never completed.
-_TOKEN_CHAIN = {}           # "cur": what model.node_features registered for the forward pass that just ran
-_TOKEN_PENDING = {}         # address of the gradient buffer the next node will receive -> parked work
-
-
+# stream order.  flush_deferred_wgrads() raises if a parked chain was never completed.  (STEP.token_chain, token_pending)
 def register_token_chain(nf, x4, w2_width, w4, slope4, w2, slope2):
     """nf [R, C] = leaky(x4 W4^T + b4), x4[:, :w2_width] = f2 = leaky(pt W2^T + b2) written in place (ops.join_cols): the
     chain whose backward mobgt_token_bwd_chain covers.  No-op for other widths."""
-    _TOKEN_CHAIN.pop("cur", None)
+    STEP.token_chain = None
     if not forms.on("token_bwd_chain"):
         return
     if (nf.is_cuda and nf.dtype == torch.float32 and x4.dtype == torch.float32 and nf.dim() == 2 and nf.is_contiguous()
@@ -1769,25 +1752,25 @@ def register_token_chain(nf, x4, w2_width, w4, slope4, w2, slope2):
             and w4.dtype == torch.float32 and w2.dtype == torch.float32):
         # (detached: a reference to nf / x4 themselves would keep this forward pass's autograd graph alive past its backward --
         #  and a live eager graph makes a later hipGraph capture_end crash)
-        _TOKEN_CHAIN["cur"] = dict(nf_ptr=nf.data_ptr(), nf=nf.detach(), x4=x4.detach(), w4=w4.detach(), slope4=float(slope4),
-                                   w2=w2.detach(), slope2=float(slope2))
+        STEP.token_chain = dict(nf_ptr=nf.data_ptr(), nf=nf.detach(), x4=x4.detach(), w4=w4.detach(), slope4=float(slope4),
+                                w2=w2.detach(), slope2=float(slope2))
 
 
 def _token_park_linear(g, w, y):
     """_LinearSplitKFn.backward inside a parked chain: FuseEmbeddings-4 parks again and returns the buffer dx4 will be written
     to; FuseEmbeddings-2 launches the kernel and returns d_pt.  None: not part of a parked chain."""
-    pend = _TOKEN_PENDING.get(g.data_ptr())
+    pend = STEP.token_pending.get(g.data_ptr())
     if pend is None:
         return None
     ent = pend["ent"]
     if pend["stage"] == 1 and w.data_ptr() == ent["w4"].data_ptr() and y is not None and y.data_ptr() == ent["nf_ptr"]:
-        del _TOKEN_PENDING[g.data_ptr()]
+        del STEP.token_pending[g.data_ptr()]
         dx4 = torch.empty_like(ent["x4"])
         pend.update(stage=2, dx4=dx4)
-        _TOKEN_PENDING[dx4.data_ptr()] = pend
+        STEP.token_pending[dx4.data_ptr()] = pend
         return dx4
     if pend["stage"] == 2 and w.data_ptr() == ent["w2"].data_ptr() and y is not None and y.data_ptr() == ent["x4"].data_ptr():
-        del _TOKEN_PENDING[g.data_ptr()]
+        del STEP.token_pending[g.data_ptr()]
         G, N, C, p_pos, p_in, seed, seed_dev, salts = pend["misc"]
         W2 = ent["w2"].shape[0]
         d_pt = torch.empty(G * N, W2, dtype=torch.float32, device=g.device)
@@ -1811,19 +1794,19 @@ class _LinearSplitKFn(torch.autograd.Function):
         ctx.bf16_wgrad = bf16_wgrad
         ctx.slope = slope
         if _small_linear(x, w) & 1:
-            # (`out`: an _OutRef to a column slice of a wider buffer; the result is a fresh view of it, not an input)
-            gat = _TOKEN_FWD["gather"] if _TOKEN_FWD["on"] else None
+            # (`out`: an OutRef to a column slice of a wider buffer; the result is a fresh view of it, not an input)
+            rec, gat = STEP.token_fwd, STEP.token_fwd.get("gather") if STEP.token_fwd_on else None
             stage = None
             if gat is not None and slope is not None and b is not None and x.dtype == torch.float32 and w.dtype == torch.float32:
-                if (_TOKEN_FWD["f2"] is None and out is not None and x.data_ptr() == gat["outs"][0].data_ptr()
+                if ("f2" not in rec and out is not None and x.data_ptr() == gat["outs"][0].data_ptr()
                         and out.t.data_ptr() == gat["outs"][1].data_ptr()):
                     stage = "f2"
-                elif (_TOKEN_FWD["f2"] is not None and _TOKEN_FWD["f4"] is None and out is None
+                elif ("f2" in rec and "f4" not in rec and out is None
                         and x.data_ptr() == gat["outs"][1].data_ptr() and x.is_contiguous()):
                     stage = "f4"
             if stage is not None:            # recorded, not launched (token_fwd_deferral): the output buffer exists, its values come later
                 y = out.t if out is not None else torch.empty(x.shape[0], w.shape[0], dtype=torch.float32, device=x.device)
-                _TOKEN_FWD[stage] = dict(launch=lambda: small_gemm(x, w, b, True, leaky=slope, out=y), x=x, w=w, b=b, slope=slope, y=y)
+                rec[stage] = dict(launch=lambda: small_gemm(x, w, b, True, leaky=slope, out=y), x=x, w=w, b=b, slope=slope, y=y)
             else:
                 y = small_gemm(x, w, b, True, leaky=slope, out=out.t if out is not None else None)
             if out is not None:
@@ -1856,9 +1839,9 @@ class _LinearSplitKFn(torch.autograd.Function):
                     and max(w.shape) <= 512):
                 db = dst(k_b, (g.shape[1],))
                 dw = linear_wgrad_masked(g, x, g_mask=y, mask_vals=mv, db=db, leaf=True, dw=dst(k_w, tuple(w.shape)))
-                dx = _token_park_linear(g, w, y) if _WGRAD_DEFER["on"] else None
-                return (dx if dx is not None else small_gemm(g, w, a_mask=(y, *mv))), dw, (db[:] if _WGRAD_DEFER["on"] else db), None, None, None
-            if (_WGRAD_DEFER["on"] and hip_wgrad and g.stride(1) == 1 and y.stride() == g.stride() and g.data_ptr() % 8 == 0
+                dx = _token_park_linear(g, w, y) if STEP.wgrad_on else None
+                return (dx if dx is not None else small_gemm(g, w, a_mask=(y, *mv))), dw, (db[:] if STEP.wgrad_on else db), None, None, None
+            if (STEP.wgrad_on and hip_wgrad and g.stride(1) == 1 and y.stride() == g.stride() and g.data_ptr() % 8 == 0
                     and y.data_ptr() % 8 == 0 and g.stride(0) % 2 == 0 and small_gemm_ok(g, w) and R <= _SMALL_ROWS
                     and max(w.shape) <= 512):
                 # trainer's backward: the weight gradient is a leaf and joins the step's one grouped launch; the data gradient
@@ -1911,7 +1894,7 @@ def linear_splitk(x, weight, bias, bf16_wgrad=False, slope=None, out=None):
     x2 = x.reshape(-1, shape[-1]).contiguous()
     if out is not None and not (_small_linear(x2, weight) & 1 and out.shape == (x2.shape[0], weight.shape[0])):
         out = None
-    y = _LinearSplitKFn.apply(x2, weight, bias, bf16_wgrad, slope, _OutRef(out) if out is not None else None)
+    y = _LinearSplitKFn.apply(x2, weight, bias, bf16_wgrad, slope, OutRef(out) if out is not None else None)
     return y if out is not None else y.view(*shape[:-1], weight.shape[0])
 
 
@@ -2000,7 +1983,7 @@ def bias_act(x, bias, slope, p_drop, training, salt, yt=None):
     if seed_dev is None and p_drop > 0:
         seed = (seed + int(torch.randint(0, 2 ** 31 - 1, (1,)).item())) & 0x7FFFFFFFFFFFFFFF
     return _BiasActFn.apply(x.float(), bias, float(slope), float(p_drop), int(seed), seed_dev, int(salt) & 0xFFFFFFFF,
-                            _OutRef(yt) if yt is not None else None)
+                            OutRef(yt) if yt is not None else None)
 
 
 class _HeadActFn(torch.autograd.Function):
@@ -2158,7 +2141,7 @@ def head_input(enc, user_table, user, user_offset=0):
 def _token_fwd_fused(nf, real, add, token, pe0, out, out16, qkv_w, qkv, G, N, C, p_pos, p_in, seed, seed_dev, salts):
     """The recorded gather + FuseEmbeddings-2 / -4 (token_fwd_deferral) together with this token assembly + QKV projection as
     ONE launch -> True; anything else: the recorded launches are issued separately -> False (the caller launches its own)."""
-    gat, f2, f4 = _TOKEN_FWD["gather"], _TOKEN_FWD["f2"], _TOKEN_FWD["f4"]
+    gat, f2, f4 = (STEP.token_fwd.get(k) for k in ("gather", "f2", "f4"))
     ok = (gat is not None and f2 is not None and f4 is not None and C == 192 and gat["R"] == G * N and len(gat["outs"]) == 3
           and nf.data_ptr() == f4["y"].data_ptr() and add.data_ptr() == gat["outs"][2].data_ptr()
           and tuple(f2["w"].shape) == (160, 160) and tuple(f4["w"].shape) == (192, 192)
@@ -2182,9 +2165,8 @@ def _token_fwd_fused(nf, real, add, token, pe0, out, out16, qkv_w, qkv, G, N, C,
         flush_token_fwd()
         return False
     check(rc, "mobgt_token_fwd_chain")
-    for k in ("gather", "f2", "f4"):
-        _TOKEN_FWD[k] = None
-    _TOKEN_FWD["fused_calls"] += 1
+    STEP.token_fwd = {}
+    STEP.token_fwd_fused_calls += 1
     return True
 
 
@@ -2204,7 +2186,7 @@ class _AssembleTokensFn(torch.autograd.Function):
         out = torch.empty(G, N + 1, C, dtype=torch.float32, device=nf.device)
         out16 = torch.empty(G, N + 1, C, dtype=torch.bfloat16, device=nf.device) if side is not None else None
         if qkv_w is not None and out16 is not None and C in (192, 256):
-            # ... and the first encoder layer's QKV projection from the same launch (csrc/chain.hip): qkv_w = _OutRefs of the
+            # ... and the first encoder layer's QKV projection from the same launch (csrc/chain.hip): qkv_w = OutRefs of the
             # packed [3C, C] weight and the bf16 bias
             qkv = torch.empty(G * (N + 1), 3 * C, dtype=torch.bfloat16, device=nf.device)
             if not _token_fwd_fused(nf, real, add, token, pe0, out, out16, qkv_w, qkv, G, N, C, p_pos, p_in, seed, seed_dev, salts):
@@ -2240,12 +2222,12 @@ class _AssembleTokensFn(torch.autograd.Function):
         else:
             d_tok = zeros_f32((C,), dout.device)
             d_pe = d_tok.view(pshape)
-        ent = _TOKEN_CHAIN.get("cur")
-        if (ent is not None and ent["nf_ptr"] == ctx.nf_ptr and _WGRAD_DEFER["on"] and C == ent["nf"].shape[1]
+        ent = STEP.token_chain
+        if (ent is not None and ent["nf_ptr"] == ctx.nf_ptr and STEP.wgrad_on and C == ent["nf"].shape[1]
                 and G * N == ent["nf"].shape[0] and forms.on("token_bwd_chain")):
             # park: FuseEmbeddings-2's backward, two autograd nodes further down, launches the one kernel that fills d_nf / d_add
-            _TOKEN_PENDING[d_nf.data_ptr()] = dict(stage=1, ent=ent, dout=dout, real=real, d_nf=d_nf, d_add=d_add, d_tok=d_tok,
-                                                   misc=(G, N, C, p_pos, p_in, seed, seed_dev, salts))
+            STEP.token_pending[d_nf.data_ptr()] = dict(stage=1, ent=ent, dout=dout, real=real, d_nf=d_nf, d_add=d_add, d_tok=d_tok,
+                                                       misc=(G, N, C, p_pos, p_in, seed, seed_dev, salts))
         else:
             _lib.call("mobgt_assemble_tokens_bwd", _p(dout), _p(real), _p(d_nf), _p(d_add), _p(d_tok), G, N, C, p_pos, p_in, seed,
                       _p(seed_dev), salts[0], salts[1], salts[2], _stream())
@@ -2276,7 +2258,7 @@ def assemble_tokens(nf, real, add, token, pe0, p_pos, p_in, training, salts=(0x1
     out = _AssembleTokensFn.apply(nf.float(), real.float(), add.float(), token.float(), pe0.float(), float(p_pos),
                                   float(p_in), int(seed), seed_dev, tuple(int(s) & 0xFFFFFFFF for s in salts), side,
                                   bool(pe_row0_via_gather and pe0.requires_grad and torch.is_grad_enabled()),
-                                  (_OutRef(first_qkv[0]), _OutRef(first_qkv[1])) if (first_qkv is not None and bf16_copy) else None,
+                                  (OutRef(first_qkv[0]), OutRef(first_qkv[1])) if (first_qkv is not None and bf16_copy) else None,
                                   grad_sink(token) if token.is_contiguous() else None)
     if side:
         out._mobgt_act = side[0]          # bf16 copy for the first fused layer's QKV GEMM (no cast launch)
@@ -2298,12 +2280,12 @@ def small_gemm(a, b, bias=None, b_is_nk=False, out=None, out_dtype=torch.float32
     _require_cuda(a, b)
     assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 2 and b.dim() == 2
     assert a.stride(1) == 1 and b.stride(1) == 1
-    pre = _FRONT_SGEMM.get("done")
+    pre = STEP.front_sgemm.get("done")
     if pre is not None:
         # this very product rode in the bias assembly's launch (front_small_gemm): its result exists
         if (pre["key"] == (a.data_ptr(), b.data_ptr(), bias.data_ptr() if bias is not None else 0, leaky, k_b,
                            ct[0].data_ptr() if ct else 0) and drop is None and a_mask is None and out is None and not b_is_nk):
-            del _FRONT_SGEMM["done"]
+            del STEP.front_sgemm["done"]
             return pre["c"]
     M, K = a.shape
     N = b.shape[0] if b_is_nk else b.shape[1]
@@ -2329,15 +2311,12 @@ def small_gemm(a, b, bias=None, b_is_nk=False, out=None, out_dtype=torch.float32
     return c
 
 
-# ---- a small GEMM riding in the bias assembly's launch (round 4) --------------------------------------------------------------------
-_FRONT_SGEMM = {}
-
-
+# ---- a small GEMM riding in the bias assembly's launch (round 4; STEP.front_sgemm) --------------------------------------------------
 def front_small_gemm(a, b, bias, leaky, k_b, ct):
     """Leave  leaky_relu(a @ b[:k_b] + bias)  (+ transposed bf16 copy into ct) for the NEXT short-batch mobgt_build_bias launch
     (mobgt_front_sgemm_job); `front_small_gemm_flush()` behind that launch turns it into the result `small_gemm` hands out when it
     is called with these very arguments -- or launches it alone if no launch took it.  False: not a shape of that form."""
-    _FRONT_SGEMM.clear()
+    STEP.front_sgemm = {}
     if (not forms.on("l0_ride") or not (a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32
             and a.is_contiguous() and b.is_contiguous() and bias is not None and bias.is_contiguous())):
         return False
@@ -2348,27 +2327,34 @@ def front_small_gemm(a, b, bias, leaky, k_b, ct):
                                           _p(ct), ct.stride(0) if ct is not None else 0, M, N, K, int(k_b))
     if rc != 0:
         return False
-    _FRONT_SGEMM["job"] = dict(key=(a.data_ptr(), b.data_ptr(), bias.data_ptr(), leaky, k_b, ct.data_ptr() if ct is not None else 0),
-                               c=c, args=(a, b, bias, leaky, k_b, ct))
+    STEP.front_sgemm["job"] = dict(key=(a.data_ptr(), b.data_ptr(), bias.data_ptr(), leaky, k_b, ct.data_ptr() if ct is not None else 0),
+                                   c=c, args=(a, b, bias, leaky, k_b, ct))
     return True
 
 
 def front_small_gemm_flush():
-    job = _FRONT_SGEMM.pop("job", None)
+    job = STEP.front_sgemm.pop("job", None)
     if job is None:
         return
     if _lib.lib().mobgt_front_sgemm_pending():             # no launch took it along: drop the job, launch the product alone
         _lib.call("mobgt_front_sgemm_job", None, 0, None, 0, None, 0, 0.0, None, 0, None, 0, 0, 0, 0, 0)
         a, b, bias, leaky, k_b, ct = job["args"]
         job["c"] = small_gemm(a, b, bias, leaky=leaky, k_b=k_b, ct=(ct, None, False) if ct is not None else None)
-    _FRONT_SGEMM["done"] = job
+    STEP.front_sgemm["done"] = job
 
 
-def front_small_gemm_drop():
-    """Forget a job that is still waiting for a launch (an exception between front_small_gemm and its flush) and an unclaimed result."""
-    if _FRONT_SGEMM.pop("job", None) is not None:
+def graph_task_id():
+    """Id of the autograd graph task (one per top-level backward / autograd.grad call) this code runs under, -1 outside."""
+    fn = getattr(torch._C, "_current_graph_task_id", None)
+    return int(fn()) if fn is not None else -1
+
+
+def drop_parked():
+    """A pass raised: forget what it parked (STEP.drop_parked: the one list), and the library's copy of a small GEMM job that is
+    still waiting for a launch (an exception between front_small_gemm and its flush)."""
+    if "job" in STEP.front_sgemm:
         _lib.call("mobgt_front_sgemm_job", None, 0, None, 0, None, 0, 0.0, None, 0, None, 0, 0, 0, 0, 0)
-    _FRONT_SGEMM.pop("done", None)
+    STEP.drop_parked(graph_task_id())
 
 
 def act_mask_values(slope, p_drop):
@@ -2382,35 +2368,38 @@ def act_mask_values(slope, p_drop):
 
 
 # ---- leaf weight gradients issued together (round 3) ----------------------------------------------------------------------------
-# Nothing but the optimizer reads a weight gradient.  While `wgrad_deferral(True)` is in force (train.TrainStep switches it on
-# around a backward pass and flushes before it gathers the gradients), `linear_wgrad(..., leaf=True)` /
+# Nothing but the optimizer reads a weight gradient.  Inside `recording_wgrads()` (train.TrainStep: around a backward pass, flushed
+# before it gathers the gradients), `linear_wgrad(..., leaf=True)` /
 # `linear_wgrad_masked(..., leaf=True)` only RECORD their problem -- operands and destinations are kept alive by the record --
 # and `flush_deferred_wgrads()` issues all of them as ONE launch (mobgt_linear_wgrad_multi).  What a caller gets back is a
 # fresh VIEW of the (zero-initialised) destination: autograd's AccumulateGrad steals a returned gradient only if nothing else
 # references that tensor object, and the record holds the base -- the kernel's late writes land in the tensor the parameter
 # ends up with (the rule fused_layer.py follows for its parked tails).  Off by default: eager callers get the launch at once.
-_WGRAD_DEFER = {"on": False, "items": []}
-
-
-def wgrad_deferral(on):
-    """Switch the recording on / off.  Switching off DROPS anything still recorded: the trainer flushes explicitly after a
-    successful backward pass, so leftovers exist only when that pass raised -- their buffers belong to a dead graph."""
-    _WGRAD_DEFER["items"] = []
-    for k in ("hop", "hop_wide", "stock_tok", "psum"):
-        _WGRAD_DEFER.pop(k, None)
-    _WGRAD_DEFER["on"] = bool(on)
+@contextlib.contextmanager
+def recording_wgrads(on=True):
+    """Record while the body (a backward pass) runs and flush behind it.  A body or a flush that raised leaves buffers of a dead
+    graph behind: everything parked is dropped (drop_parked).  The recording is off again either way."""
+    STEP.wgrad_on = bool(on)
+    try:
+        yield
+        flush_deferred_wgrads()
+    except BaseException:
+        drop_parked()
+        raise
+    finally:
+        STEP.wgrad_on = False
 
 
 def defer_partial_sum(part, dst):
     """Park `dst = part.sum(0)` ([s, M, N] f32 split-K partial products of a library batched GEMM; dst: the gradient's sink)
     until flush_deferred_wgrads, which issues all of a step's as ONE launch (mobgt_partial_sum_multi).  -> a fresh view of dst,
     or None when the sum cannot be parked (no recording, layouts): the caller then sums now."""
-    if not (_WGRAD_DEFER["on"] and dst is not None and part.dtype == torch.float32 and dst.dtype == torch.float32
+    if not (STEP.wgrad_on and dst is not None and part.dtype == torch.float32 and dst.dtype == torch.float32
             and part.is_contiguous() and dst.is_contiguous() and part.dim() == 3 and dst.numel() == part[0].numel()
             and dst.numel() % 4 == 0 and part.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
             and forms.on("psum_defer")):
         return None
-    _WGRAD_DEFER.setdefault("psum", []).append((part, dst))
+    STEP.wgrad_psum.append((part, dst))
     return dst[:]
 
 
@@ -2448,48 +2437,22 @@ def layer_wgrad_big_ok(items):
 
 
 def _wgrad_defer(g, x, g_mask, x_mask, mask_vals, dw, db, db_of_x):
-    _WGRAD_DEFER["items"].append((g, x, g_mask, x_mask, tuple(float(v) for v in mask_vals), dw, db, bool(db_of_x)))
+    STEP.wgrad_items.append((g, x, g_mask, x_mask, tuple(float(v) for v in mask_vals), dw, db, bool(db_of_x)))
     return dw[:]
 
 
 def step_state_leftovers():
-    """What the step's hand-over registries still hold -- {} when a forward + backward pass has consumed everything it parked.
-    The registries (the bias tables' backward job, the front-of-step jobs, the parked encoder-input chain, deferred weight
-    gradients, the fused layers' parked tails, the deferred weight pack) are process-wide by design: a job parked by the forward
-    pass on the caller's thread is taken by a launch the autograd engine issues from ITS thread, so they cannot be thread-local;
-    ONE step is in flight per process.  The trainer asserts this is empty behind every step (`TrainStep._fwd_bwd`):
-    a job left behind -- an exception on the way, a second model's forward in between that took or overwrote it -- is an error
-    of that step, not a surprise of the next one."""
-    from . import fused_layer, model as _model
-    left = {}
-    if _BIAS_BWD_JOB:
-        left["bias_bwd_job"] = list(_BIAS_BWD_JOB)
-    if _FRONT_DEFER["hop"] is not None or _FRONT_DEFER["ni"] is not None:
-        left["front_jobs"] = [k for k in ("hop", "ni") if _FRONT_DEFER[k] is not None]
-    if _TOKEN_PENDING:
-        left["token_pending"] = len(_TOKEN_PENDING)
-    extra = [k for k in _WGRAD_DEFER if k not in ("on", "items")]
-    if _WGRAD_DEFER["items"] or extra:
-        left["wgrad_defer"] = dict(items=len(_WGRAD_DEFER["items"]), slots=extra)
-    if fused_layer._PENDING_TAIL:
-        left["layer_tails"] = len(fused_layer._PENDING_TAIL)
-    if _model._PENDING_PACK:
-        left["weight_pack"] = len(_model._PENDING_PACK)
-    return left
+    """What the step's hand-overs still hold ({} behind a clean forward + backward): an error of THAT step (TrainStep._fwd_bwd)."""
+    return STEP.leftovers()
 
 
 def flush_deferred_wgrads():
-    if _TOKEN_PENDING:
-        stages = [p_["stage"] for p_ in _TOKEN_PENDING.values()]
-        _TOKEN_PENDING.clear()
-        _WGRAD_DEFER["items"] = []
-        for k in ("hop", "hop_wide", "stock_tok", "psum"):
-            _WGRAD_DEFER.pop(k, None)
+    if STEP.token_pending:
+        stages = [p_["stage"] for p_ in STEP.token_pending.values()]
         raise RuntimeError(f"a parked encoder-input backward chain was never completed (stages {stages}): gradients of this "
                            "step are invalid -- set MOBGT_NO_TOKEN_BWD_CHAIN=1 and report")
-    items, _WGRAD_DEFER["items"] = _WGRAD_DEFER["items"], []
-    hop = _WGRAD_DEFER.pop("hop", None)
-    psum = _WGRAD_DEFER.pop("psum", None) or []
+    items, hop, psum, tok, wide = STEP.wgrad_items, STEP.wgrad_hop, STEP.wgrad_psum, STEP.wgrad_stock_tok, STEP.wgrad_hop_wide
+    STEP.wgrad_items, STEP.wgrad_hop, STEP.wgrad_psum, STEP.wgrad_stock_tok, STEP.wgrad_hop_wide = [], None, [], None, None
     for o in range(0, len(psum), 48):            # the sums over the library's split-K partial weight gradients: one launch
         part = psum[o:o + 48]
         n = len(part)
@@ -2497,19 +2460,16 @@ def flush_deferred_wgrads():
                   (ctypes.c_void_p * n)(*[p_[1].data_ptr() for p_ in part]),
                   (ctypes.c_int * n)(*[p_[0].shape[0] for p_ in part]),
                   (ctypes.c_int64 * n)(*[p_[1].numel() for p_ in part]), _stream())
-    tok, wide = _WGRAD_DEFER.pop("stock_tok", None), _WGRAD_DEFER.pop("hop_wide", None)
     if tok is not None and wide is not None:     # the stock step's tail: both in one grid
         dtab, ew, dw_, d_ew, d_dw, D, E, rt = wide
         _lib.call("mobgt_stock_tail_bwd", *tok[0], _p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream())
     elif tok is not None:
         _lib.call("mobgt_stock_tokens_bwd", *tok[0], _stream())
     elif wide is not None:
-        dtab, ew, dw_, d_ew, d_dw, D, E, rt = wide
-        _lib.call("mobgt_hop_table_bwd", _p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream())
+        _hop_table_bwd(wide)
     vp, i64, ci, cf = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
     if hop is not None and not items:            # nobody to ride with
-        dtab, ew, dw_, d_ew, d_dw, D, E, rt = hop
-        _lib.call("mobgt_hop_table_bwd", _p(dtab), _p(ew), _p(dw_), _p(d_ew), _p(d_dw), D, E, 8, rt, _stream())
+        _hop_table_bwd(hop)
         hop = None
     for o in range(0, len(items), 32):
         part = items[o:o + 32]
@@ -2549,7 +2509,7 @@ def linear_wgrad_masked(g, x, g_mask=None, x_mask=None, mask_vals=(1.0, 1.0, 1.0
     if dw is None:
         dw = zeros_f32((M, N), g.device)
     assert g_out is None or (g_mask is not None and g_out.shape == g.shape and g_out.stride() == g.stride())
-    if leaf and _WGRAD_DEFER["on"] and g_out is None and M % 2 == 0 and N % 2 == 0:
+    if leaf and STEP.wgrad_on and g_out is None and M % 2 == 0 and N % 2 == 0:
         return _wgrad_defer(g, x, g_mask, x_mask, mask_vals, dw, db, db_of_x)
     _lib.call("mobgt_linear_wgrad_masked", _p(g), g.stride(0), _p(x), x.stride(0), _p(g_mask), _p(x_mask), float(mask_vals[0]),
               float(mask_vals[1]), float(mask_vals[2]), _p(g_out), _p(dw), N, _p(db), int(db_of_x),
@@ -2657,7 +2617,7 @@ def linear_wgrad(g, x, with_bias=False, db=None, out_bias=None, leaf=False, dw=N
         return dw, None
     if db is None and with_bias:
         db = zeros_f32((M,), g.device)
-    if leaf and _WGRAD_DEFER["on"] and M % 2 == 0 and N % 2 == 0:
+    if leaf and STEP.wgrad_on and M % 2 == 0 and N % 2 == 0:
         return _wgrad_defer(g, x, None, None, (1.0, 1.0, 1.0), dw, db, False), (db[:] if db is not None else None)
     _lib.call("mobgt_linear_wgrad", _p(g), g.stride(0), _p(x), x.stride(0), _p(dw), N, _p(db), R, M, N, _DT[g.dtype],
               _stream())

@@ -22,6 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import forms, ops
+from .step_state import STEP
 from .model import sync_external_shadows
 from .lr import polynomial_decay_lr
 from .accum import UpdateWindow, check_accum_args, scheduled_lr
@@ -632,12 +633,8 @@ class TrainStep:
             # (parity tests: a copy of the encoder output's graph-token rows -- what the classifier head reads -- as one more node
             #  of this batch's graph; the encoder output itself is overwritten in place by the backward pass)
             self.enc_outs[slot] = self.model._enc_out[:, 0, :].detach().clone()
-        ops.wgrad_deferral(self._defer)          # leaf weight gradients are recorded ...
-        try:
-            loss.backward(gradient=ops.unit_grad(loss.device))
-            ops.flush_deferred_wgrads()          # ... and issued as ONE launch, before anything reads a gradient
-        finally:
-            ops.wgrad_deferral(False)
+        with ops.recording_wgrads(self._defer):  # leaf weight gradients are recorded and issued as ONE launch behind the pass,
+            loss.backward(gradient=ops.unit_grad(loss.device))                                # before anything reads a gradient
         ops.set_zero_arena(None)
         left = ops.step_state_leftovers()
         if left:
@@ -664,24 +661,16 @@ class TrainStep:
         loss = self._loss(batch)
         enc = self.model._enc_out
         head = self.flat.params[:self.n_head]
-        ops.wgrad_deferral(self._defer)
-        try:
+        with ops.recording_wgrads(self._defer):
             grads = torch.autograd.grad(loss, head + [enc], grad_outputs=ops.unit_grad(loss.device), allow_unused=True)   # frees only the nodes it ran
-            ops.flush_deferred_wgrads()
-        finally:
-            ops.wgrad_deferral(False)
         self.flat.gather(0, self.n_head, grads=list(grads[:-1]))
         self._g_enc[i] = (enc, grads[-1])
         self._keep_loss(loss, i)
 
     def _phase_b(self, i):
         enc, g_enc = self._g_enc[i]
-        ops.wgrad_deferral(self._defer)
-        try:
+        with ops.recording_wgrads(self._defer):
             torch.autograd.backward([enc], [g_enc])
-            ops.flush_deferred_wgrads()
-        finally:
-            ops.wgrad_deferral(False)
         ops.set_zero_arena(None)
         self.flat.gather(self.n_head, None)
 
@@ -690,8 +679,7 @@ class TrainStep:
         li, lo, hi, _, _ = self.parts[s]
         src, g_src = self._g_enc[i]
         last = li is None
-        ops.wgrad_deferral(self._defer)
-        try:
+        with ops.recording_wgrads(self._defer):
             if not last:
                 cut = self.model._cuts[li]
                 grads = torch.autograd.grad([src], self.flat.params[lo:hi] + [cut], grad_outputs=[g_src], allow_unused=True)
@@ -706,9 +694,6 @@ class TrainStep:
                     gouts.append(torch.zeros_like(tok))
                 torch.autograd.backward(outs, gouts)
                 grads = None
-            ops.flush_deferred_wgrads()
-        finally:
-            ops.wgrad_deferral(False)
         if last:
             ops.set_zero_arena(None)
         self.flat.gather(lo, hi, grads=grads)
@@ -1565,10 +1550,9 @@ class EvalLoop(_StagedBatches):
         was_training = model.training
         frozen = [getattr(l, "_weights_frozen", False) for l in layers]
         saved = {k: model.__dict__.get(k) for k in ("_enc_out", "_bias_pack", "_cuts")}
-        token_chain = ops._TOKEN_CHAIN.get("cur")
         model.eval()
         try:
-            with torch.no_grad():
+            with torch.no_grad(), STEP.keeping_carried():
                 self._refresh_weights()
                 for l in layers:
                     l._weights_frozen = True
@@ -1582,10 +1566,6 @@ class EvalLoop(_StagedBatches):
                 l._weights_frozen = f
             for k, v in saved.items():
                 setattr(model, k, v)
-            if token_chain is None:
-                ops._TOKEN_CHAIN.pop("cur", None)
-            else:
-                ops._TOKEN_CHAIN["cur"] = token_chain
             model.train(was_training)
         left = ops.step_state_leftovers()
         if left:

@@ -298,6 +298,7 @@ def test_encoder_input_backward_as_one_launch_equals_the_three_launches(monkeypa
     parameter gradient of one dropout-on S-FSQ batch, same masks; f32 products in another summation order.  The first pass
     takes the one launch (mobgt_token_bwd_chain is called once), the second never."""
     from mobgt_amd import _lib, ops, workloads
+    from mobgt_amd.step_state import STEP
     uni, model, coll = workloads.build("fsq", "cuda", seed=1, model_overrides=dict(n_layers=2))
     batch = coll(workloads.make_pool("fsq", 1, 16, uni)[0])
     model.train()
@@ -322,15 +323,11 @@ def test_encoder_input_backward_as_one_launch_equals_the_three_launches(monkeypa
             del launches[:]
             for p in model.parameters():
                 p.grad = None
-            ops.wgrad_deferral(True)
-            try:
+            with ops.recording_wgrads():             # (flushes behind the body)
                 loss = model.training_step(batch, 0)
-                parked_before = len(ops._TOKEN_PENDING)
+                parked_before = len(STEP.token_pending)
                 loss.backward()
-                assert not ops._TOKEN_PENDING, "the parked chain must have been completed inside backward"
-                ops.flush_deferred_wgrads()
-            finally:
-                ops.wgrad_deferral(False)
+                assert not STEP.token_pending, "the parked chain must have been completed inside backward"
             torch.cuda.synchronize()
             res.append({n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None})
             assert parked_before == 0
@@ -355,10 +352,10 @@ def test_encoder_input_backward_as_one_launch_equals_the_three_launches(monkeypa
         assert err <= (2e-3 if through else 2e-2) * sc + 1e-9, (n, err, sc)
     print("largest relative difference %.2e" % worst)
     # the one-launch form really ran: its registration exists for this forward pass and the switch removes it
-    assert ops._TOKEN_CHAIN.get("cur") is None                  # (last pass ran with the switch on)
+    assert STEP.token_chain is None                             # (last pass ran with the switch on)
     monkeypatch.setenv("MOBGT_NO_TOKEN_BWD_CHAIN", "0")
     model.training_step(batch, 0)
-    assert ops._TOKEN_CHAIN.get("cur") is not None
+    assert STEP.token_chain is not None
 
 
 def test_bias_tables_backward_as_passenger_of_the_category_gcn_launch(monkeypatch):
@@ -414,6 +411,7 @@ def test_encoder_input_forward_in_one_launch_is_bit_identical_to_the_four_launch
     eval logits bit-identical; gradients to the run-to-run noise of the atomics in the backward pass.  (Train-mode LOGITS are
     not compared: the encoder layers draw fresh host seeds per forward pass.)"""
     from mobgt_amd import ops, workloads
+    from mobgt_amd.step_state import STEP
     uni, model, coll = workloads.build("fsq", "cuda", seed=1, model_overrides=dict(n_layers=2))
     batch = coll(workloads.make_pool("fsq", 1, 16, uni)[0])
     seen = []
@@ -432,7 +430,7 @@ def test_encoder_input_forward_in_one_launch_is_bit_identical_to_the_four_launch
             ops.set_dropout_state(torch.tensor([3], dtype=torch.int64, device="cuda"), 11)
             for p in model.parameters():
                 p.grad = None
-            before = ops._TOKEN_FWD["fused_calls"]
+            before = STEP.token_fwd_fused_calls
             del seen[:]
             try:
                 logits = model(batch)[0]
@@ -441,7 +439,7 @@ def test_encoder_input_forward_in_one_launch_is_bit_identical_to_the_four_launch
             finally:
                 ops.set_dropout_state(None, None)
             torch.cuda.synchronize()
-            took = ops._TOKEN_FWD["fused_calls"] - before
+            took = STEP.token_fwd_fused_calls - before
             assert took == (2 if off == "0" else 0), (mode, off, took)
             res[(mode, off)] = (logits.detach().float().clone(), seen[0], {n: p.grad.detach().float().clone()
                                                                           for n, p in model.named_parameters() if p.grad is not None})
@@ -802,8 +800,8 @@ def _assert_same_grads(a, b, what):
 
 
 def test_eval_forward_between_a_training_forward_and_its_backward_leaves_the_gradients_alone():
-    """ADVICE r3 / VERDICT r4 weak #11: the step's deferral registries are process-global (ops._BIAS_BWD_JOB, _FRONT_DEFER,
-    model._PENDING_PACK, the fused layers' parked tails, gcn._prelaunched).  A forward pass of ANOTHER batch in eval mode between a
+    """ADVICE r3 / VERDICT r4 weak #11: the step's deferral registries are process-global (step_state.STEP: the bias tables'
+    backward job, the front jobs, the weight pack, the fused layers' parked tails, the prelaunched GCN product).  A forward pass of ANOTHER batch in eval mode between a
     training forward and its backward (a validation step inside a training step, a metric hook) must not take, overwrite or
     complete any job that belongs to the pending backward: same gradients as the undisturbed step, up to run-to-run noise."""
     from mobgt_amd import ops
@@ -831,6 +829,53 @@ def test_eval_forward_between_a_training_forward_and_its_backward_leaves_the_gra
             res.append((float(loss), _grads_of(model)))
         assert res[0][0] == res[1][0]
         _assert_same_grads(res[1][1], res[0][1], "eval forward in between")
+    finally:
+        ops.set_dropout_state(None, 0)
+
+
+def test_a_backward_that_raises_leaves_nothing_parked_and_the_next_step_is_a_clean_step():
+    """A Python exception inside the backward pass (a tensor hook on the encoder output: host side, nothing on the device fails)
+    ends the step half way: the bias tables' backward job and the head's recorded weight gradients are parked, their takers never
+    run.  ops.recording_wgrads drops all of it (STEP.drop_parked), so nothing is left over and the next step of the same model
+    and batch has the gradients of an undisturbed step."""
+    from mobgt_amd import ops
+    model, (b0, _) = _fsq_small()
+    seed_dev = torch.tensor([17], dtype=torch.int64, device=DEV)
+    for m in model.modules():
+        if hasattr(m, "seed_dev"):
+            m.seed_dev = seed_dev
+    ops.set_dropout_state(seed_dev, 3)
+    model.train()
+
+    class Boom(Exception):
+        pass
+
+    def step(hook=None):
+        for p in model.parameters():
+            p.grad = None
+        with ops.recording_wgrads():
+            loss = model.training_step(b0, 0)
+            if hook is not None:
+                model._enc_out.register_hook(hook)
+            loss.backward()
+        torch.cuda.synchronize()
+        return _grads_of(model)
+
+    def boom(_g):
+        raise Boom("from the encoder output's hook")
+    try:
+        clean = step()
+        assert ops.step_state_leftovers() == {}
+        raised = False
+        try:                            # (not pytest.raises: nothing may keep the dead pass's frames, and with them its graph, alive)
+            step(boom)
+        except Boom:
+            raised = True
+        assert raised
+        assert ops.step_state_leftovers() == {}
+        after = step()
+        assert ops.step_state_leftovers() == {}
+        _assert_same_grads(after, clean, "the step after a backward that raised")
     finally:
         ops.set_dropout_state(None, 0)
 
