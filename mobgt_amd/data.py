@@ -9,6 +9,8 @@ SPD / path / first-D-hop edge features / degrees, and a gather from a precompute
 the kernels are templated on the index type, and `.long()` views give the reference dtypes when needed.
 Every field equals what the reference pipeline produces for the same trajectories (tests/test_gpu_data.py).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -131,6 +133,63 @@ class DeviceCollator:
         h = self.pack_host(trajs, idx0, n_pad=n_pad)
         d = {k: torch.from_numpy(v).to(self.device, non_blocking=True) for k, v in h.items()}
         return self.finish(d)
+
+    # ---- what the loops over fresh batches (train._StagedBatches) ask of a collator: the input form is the collator's business.
+    # Here: trajectory dicts, staged as RawLayout's arrays.  SessionCollator overrides these for check-in sessions.
+    def nodes_of(self, sample):
+        """Node count of one sample of the dataset (what its batch's bucket is chosen by)."""
+        return len(sample["node_name"])
+
+    def keeps(self, sample):
+        """Whether a sample enters a batch: longer ones than max_node are dropped (as the reference's collator does)."""
+        return sample is not None and self.nodes_of(sample) <= self.max_node
+
+    @staticmethod
+    def lengths_of(dataset):
+        """Node counts of a whole dataset (data.balanced_batches deals by them)."""
+        return [len(t["node_name"]) for t in dataset]
+
+    def new_stage(self, lay, side, host=True):
+        """One staging buffer pair of a (G, N) bucket: a pinned host buffer for the raw part and a device buffer of the whole
+        layout (`side`: with the derived fields, whose views finish_into fills)."""
+        raw_bytes = lay.raw_bytes if side else lay.nbytes
+        dev = torch.zeros(lay.nbytes, dtype=torch.uint8, device=self.device)
+        st = dict(pin=None, np=None, dev=dev, dev_views=lay.views_torch(dev) if side else None, work=None,
+                  ready=torch.cuda.Event(), free=None, used=False, index=None, batch=None, layout=lay, raw_bytes=raw_bytes)
+        if host:
+            self._host_stage(st)
+        return st
+
+    @staticmethod
+    def _host_stage(st):
+        st["pin"] = torch.zeros(st["raw_bytes"], dtype=torch.uint8).pin_memory()
+        st["np"] = st["layout"].views_np(st["pin"].numpy())
+
+    def stage_host(self, st, samples, idx0, N):
+        """Host half of staging a batch: the samples into the stage's pinned buffer -> the host arrays limit_violation reads."""
+        return self.pack_host(samples, idx0=idx0, n_pad=N, out=st["np"])
+
+    def limit_violation(self, h, L):
+        """The first field of stage_host's arrays that holds an index outside the model's tables (L = model.index_limits()):
+        (field, index, table rows), or None.  Checked on the host, before anything is launched."""
+        nz = h["counts"] != 0
+        if "x" in L and int(h["x"].max()) > L["x"]:
+            return "x", int(h["x"].max()), L["x"] + 1
+        if "user" in L and int(h["user"].max()) > L["user"]:
+            return "user", int(h["user"].max()), L["user"] + 1
+        if "y" in L and int(h["y"].max()) > L["y"]:
+            return "y", int(h["y"].max()), L["y"] + 1
+        if "edge" in L and int(h["counts"].max()) + 3 >= L["edge"]:
+            return "edge_input", int(h["counts"].max()) + 3, L["edge"]
+        if "deg" in L and max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1 >= L["deg"]:
+            return "degree", max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1, L["deg"]
+        if "slots" in L and int(float(h["time_normal"].max()) * 48) >= L["slots"]:
+            return "time_normal", float(h["time_normal"].max()), L["slots"]
+        return None
+
+    def upload(self, st):
+        """Device half, on the CURRENT stream (the loop's copy stream): the staged host bytes -> the raw fields of st["dev"]."""
+        st["dev"][:st["pin"].numel()].copy_(st["pin"], non_blocking=True)
 
     def can_finish_into(self):
         return self.coords is None and (self.bin_table is None or (self.bin_table.dtype == torch.int16 and self.bin_table.is_contiguous()))
@@ -347,3 +406,296 @@ def shard_indices(n_samples, rank, world_size, epoch=0, seed=0, shuffle=True):
     total = (n_samples + world_size - 1) // world_size * world_size
     order += order[: total - len(order)]
     return order[rank:total:world_size]
+
+
+# ---- check-in sessions as the input form ----------------------------------------------------------------------------------------
+# What a user has, and what a recommender is served with, is a session: a user id and a visit-ordered list of check-ins, the
+# last one the target.  The reference turns sessions into the trajectory dicts above with a pandas loop
+# (gen_pickles.py:735-833); here sessions_to_trajectories does it in numpy (the host reference, the offline converter and the
+# fall-back) and SessionCollator on the device (csrc_data/sessions.hip through _lib_data).
+SessionRecord = collections.namedtuple("SessionRecord", "user checkins n mult")
+SessionRecord.__doc__ = """One session of a SessionDataset: user id, checkins [L + 1, 3] int32 rows (poi, time slot, category) in visit
+order (the last row is the target), n = distinct POIs of the history checkins[:L], mult = how often its most visited POI occurs."""
+
+
+def session_graph(hist):
+    """History check-ins [L, 3] (poi, time slot, category) in visit order -> the graph fields of gen_pickles.py:755-832:
+    nodes are the distinct POIs ordered by their LAST occurrence (:789-791 drop_duplicates(keep='last')), so node n - 1 is the
+    last check-in's POI; edge_type[a, b] counts the transitions a -> b (:783-785), self transitions on the diagonal, nothing
+    clipped; time / cat are the values at the node's last occurrence (:786-787); time_normal = 0 for slot 0, else
+    float32(time / 48) with a double quotient (:805-809, :828)."""
+    hist = np.asarray(hist)
+    poi = hist[:, 0].astype(np.int64)
+    L = len(poi)
+    uniq, first_rev, inv = np.unique(poi[::-1], return_index=True, return_inverse=True)
+    last = L - 1 - first_rev                                          # last position of every distinct POI (in POI order)
+    order = np.argsort(last)
+    pos = last[order]                                                 # the nodes' positions, ascending
+    rank = np.empty(len(uniq), dtype=np.int64)
+    rank[order] = np.arange(len(uniq))
+    node = rank[inv.reshape(-1)[::-1]]                                # node index of every check-in
+    edge = np.zeros((len(uniq), len(uniq)), dtype=np.int64)
+    np.add.at(edge, (node[:-1], node[1:]), 1)
+    time = hist[pos, 1].astype(np.int64)
+    with np.errstate(divide="ignore"):
+        time_normal = np.where(time == 0, 0.0, time / 48).astype(np.float32)
+    return dict(node_name=poi[pos], edge_type=edge, time=time, time_normal=time_normal, cat=hist[pos, 2].astype(np.int64))
+
+
+def _validated(s, what):
+    """(user, checkins) -> (user, integer array [L + 1, 3] whose values fit int32), or ValueError naming `what`."""
+    try:
+        user, checkins = s
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: expected (user, checkins)") from None
+    c = np.asarray(checkins)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError(f"{what}: checkins must be [L + 1, 3] rows of (poi, time slot, category), got shape {c.shape}")
+    if c.shape[0] < 2:
+        raise ValueError(f"{what} has {c.shape[0]} check-in(s): a history of at least one and a target are needed")
+    if not np.issubdtype(c.dtype, np.integer) or not isinstance(user, (int, np.integer)):
+        raise ValueError(f"{what}: user and checkins must be integers (got {type(user).__name__}, {c.dtype})")
+    if c.min() < np.iinfo(np.int32).min or c.max() > np.iinfo(np.int32).max:
+        raise ValueError(f"{what}: a value does not fit int32")
+    return int(user), c
+
+
+def _as_record(s, what="a session"):
+    """A SessionRecord passes (its dataset validated it); a raw (user, checkins) pair is validated as SessionDataset does."""
+    if isinstance(s, SessionRecord):
+        return s
+    user, c = _validated(s, what)
+    _, cnt = np.unique(c[:-1, 0], return_counts=True)
+    return SessionRecord(user, c, len(cnt), int(cnt.max()))
+
+
+def sessions_to_trajectories(sessions):
+    """Sessions -- (user, checkins [L + 1, 3]) pairs, SessionRecords or a SessionDataset -- -> the list of trajectory dicts in
+    the gen_pickles.py:820-832 format (numpy arrays, as synth.make_trajectory's): what gen_poigraph_d1228_nyc_avg_maxtime
+    writes for them, field by field and bit by bit (tests/test_host_sessions.py, golden G12)."""
+    out = []
+    for s in sessions:
+        r = _as_record(s)
+        c = np.asarray(r.checkins)
+        d = session_graph(c[:-1])
+        d["target"] = np.array([int(c[-1, 0])], dtype=np.int64)       # :761, :824
+        d["user"] = np.array([int(r.user)], dtype=np.int64)           # :829
+        out.append(d)
+    return out
+
+
+class SessionDataset:
+    """A dataset of sessions for SessionCollator and the loops: validated once, stored packed (one [sum(L + 1), 3] int32 array
+    plus offsets), with every session's n (distinct POIs of its history: what buckets and max_node go by) and the largest
+    multiplicity of a POI in it (a bound on its edge counts).  ds[i] is a light SessionRecord over views of the packed array."""
+
+    def __init__(self, sessions):
+        users, rows, offs, n, mult = [], [], [0], [], []
+        for i, s in enumerate(sessions):
+            user, c = _validated(s, f"session {i}")
+            _, cnt = np.unique(c[:-1, 0], return_counts=True)
+            users.append(user)
+            rows.append(c.astype(np.int32))
+            offs.append(offs[-1] + c.shape[0])
+            n.append(len(cnt))
+            mult.append(int(cnt.max()))
+        self.seq = np.concatenate(rows) if rows else np.zeros((0, 3), dtype=np.int32)
+        self.offsets = np.asarray(offs, dtype=np.int64)
+        self.users = np.asarray(users, dtype=np.int64)
+        self.n = np.asarray(n, dtype=np.int32)
+        self.mult = np.asarray(mult, dtype=np.int32)
+
+    def __len__(self):
+        return len(self.users)
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        i %= len(self)
+        return SessionRecord(int(self.users[i]), self.seq[self.offsets[i]:self.offsets[i + 1]], int(self.n[i]), int(self.mult[i]))
+
+    @property
+    def max_n(self):
+        """The longest trajectory graph of the dataset (nodes)."""
+        return int(self.n.max()) if len(self) else 0
+
+
+class SessionLayout:
+    """What travels to the device for a batch of sessions, in ONE byte buffer: y and idx at RawLayout's offsets (one device
+    copy moves both), then user, len and seq [G, Lp, 3]; every field 16-byte aligned."""
+
+    def __init__(self, G):
+        self.G = G = int(G)
+        a16 = lambda v: (v + 15) // 16 * 16
+        self.idx_off = a16(8 * G)
+        self.head_bytes = self.idx_off + 8 * G                        # [y | idx]: RawLayout's first two fields, same offsets
+        self.user_off = a16(self.head_bytes)
+        self.len_off = self.user_off + a16(4 * G)
+        self.seq_off = self.len_off + a16(4 * G)
+        assert RawLayout(G, 1).offsets["idx"][0] == self.idx_off and RawLayout(G, 1).offsets["y"][0] == 0
+
+    def nbytes(self, Lp):
+        return self.seq_off + (12 * self.G * int(Lp) + 15) // 16 * 16
+
+    def views_np(self, buf, Lp):
+        G = self.G
+        return dict(y=buf[:8 * G].view(np.int64), idx=buf[self.idx_off:self.idx_off + 8 * G].view(np.int64),
+                    user=buf[self.user_off:self.user_off + 4 * G].view(np.int32).reshape(G, 1),
+                    len=buf[self.len_off:self.len_off + 4 * G].view(np.int32),
+                    seq=buf[self.seq_off:self.seq_off + 12 * G * Lp].view(np.int32).reshape(G, Lp, 3))
+
+
+class SessionCollator(DeviceCollator):
+    """callable(list of sessions or SessionRecords) -> the DeviceBatch1 DeviceCollator returns for the converted dicts
+    (sessions_to_trajectories): seq / len / user / y / idx are packed on the host and copied in one piece, the raw graph
+    fields are built on the device (mobgt_sessions_to_raw, include/mobgt_data.h) straight into RawLayout's views, then the
+    existing finish.  The constructor is DeviceCollator's.  A batch beyond the kernel's limits (history longer than
+    _lib_data.MAX_LP, padded N over _lib_data.MAX_N) is converted on the host and takes DeviceCollator's path.
+
+    The host checks what the kernel would refuse (lengths, node counts against n_pad), so the kernel's per-graph status is
+    not read back on this path."""
+
+    # ---- host packing ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def pack_sessions(recs, idx0, v):
+        """Records -> the numpy views of a SessionLayout buffer (padding rows of seq zeroed: the whole buffer is copied)."""
+        for g, r in enumerate(recs):
+            L = len(r.checkins) - 1
+            v["seq"][g, :L] = r.checkins[:L]
+            v["seq"][g, L:] = 0
+            v["len"][g] = L
+            v["user"][g, 0] = r.user + 1                              # wrapper.py:39
+            v["y"][g] = r.checkins[L, 0]                              # collator.py:367
+        G = len(recs)
+        v["idx"][...] = np.arange(idx0, idx0 + G, dtype=np.int64) if np.isscalar(idx0) else np.asarray(idx0, dtype=np.int64)
+        v["n"] = np.array([r.n for r in recs], dtype=np.int32)
+        v["recs"] = recs
+        return v
+
+    @staticmethod
+    def fits_kernel(Lp, N):
+        from . import _lib_data
+        return Lp <= _lib_data.MAX_LP and N <= _lib_data.MAX_N
+
+    def to_raw(self, sdev, slay, Lp, buf, raw, status):
+        """On the current stream: the session bytes on the device (a SessionLayout buffer) -> every raw field of `raw`
+        (RawLayout's torch views of the byte buffer `buf`): one kernel launch and two small device copies (y | idx, user)."""
+        from . import _lib_data
+        from .ops import _p, _stream
+        G, N = raw["counts"].shape[:2]
+        _lib_data.launch("mobgt_sessions_to_raw", sdev.data_ptr() + slay.seq_off, sdev.data_ptr() + slay.len_off, _p(raw["counts"]),
+                         _p(raw["x"]), _p(raw["time"]), _p(raw["cat"]), _p(raw["time_normal"]), _p(raw["n_nodes"]), _p(status),
+                         G, Lp, N, _stream())
+        buf[:slay.head_bytes].copy_(sdev[:slay.head_bytes], non_blocking=True)      # (y, idx: RawLayout's first two fields)
+        raw["user"].view(-1).copy_(sdev[slay.user_off:slay.user_off + 4 * G].view(torch.int32), non_blocking=True)
+
+    def __call__(self, sessions, idx0=0, n_pad=None):
+        recs = [_as_record(s, f"session {i}") for i, s in enumerate(sessions) if s is not None]
+        recs = [r for r in recs if r.n <= self.max_node]
+        G = len(recs)
+        if G == 0:
+            raise ValueError("SessionCollator: no session to collate (none given, or every one longer than max_node)")
+        n_max = max(r.n for r in recs)
+        N = n_max if n_pad is None else int(n_pad)
+        if N < n_max:
+            raise ValueError(f"n_pad {N} is smaller than the longest trajectory ({n_max})")
+        Lp = max(len(r.checkins) - 1 for r in recs)
+        if not self.fits_kernel(Lp, N):
+            return DeviceCollator.__call__(self, sessions_to_trajectories(recs), idx0, n_pad=n_pad)
+        lay, slay = RawLayout(G, N), SessionLayout(G)
+        host = np.zeros(slay.nbytes(Lp), dtype=np.uint8)
+        self.pack_sessions(recs, idx0, slay.views_np(host, Lp))
+        dev = torch.empty(lay.nbytes + host.size + 4 * G, dtype=torch.uint8, device=self.device)
+        sdev = dev[lay.nbytes:lay.nbytes + host.size]
+        sdev.copy_(torch.from_numpy(host), non_blocking=True)
+        raw = lay.views_torch(dev)
+        self.to_raw(sdev, slay, Lp, dev, raw, dev[lay.nbytes + host.size:].view(torch.int32))
+        return self.finish(raw)
+
+    # ---- the loops' hooks (DeviceCollator has the dict forms) ----------------------------------------------------------------
+    def nodes_of(self, sample):
+        return _as_record(sample).n
+
+    @staticmethod
+    def lengths_of(dataset):
+        """A SessionDataset recorded every session's n when it validated them; any other sequence of sessions is measured."""
+        return [int(v) for v in dataset.n] if isinstance(dataset, SessionDataset) else [_as_record(s).n for s in dataset]
+
+    def new_stage(self, lay, side, host=True):
+        """DeviceCollator's stage, with the session bytes in place of its pinned raw arrays: a pinned SessionLayout buffer and
+        its device twin, both grown to the longest history the bucket has seen.  The pinned raw buffer exists only once a
+        batch of the bucket had to fall back to host conversion."""
+        st = super().new_stage(lay, side, host=False)
+        st.update(slay=SessionLayout(lay.G), spin=None, sdev=None, cap=0, Lp=0, mode=None,
+                  raw_dev=st["dev_views"] if side else lay.views_torch(st["dev"]),
+                  status=torch.zeros(lay.G, dtype=torch.int32, device=self.device))
+        return st
+
+    def stage_host(self, st, samples, idx0, N):
+        recs = [_as_record(s) for s in samples]
+        Lp = max(len(r.checkins) - 1 for r in recs)
+        if not self.fits_kernel(Lp, N):
+            if st["pin"] is None:
+                self._host_stage(st)
+            st["mode"] = "dicts"
+            return self.pack_host(sessions_to_trajectories(recs), idx0=idx0, n_pad=N, out=st["np"])
+        if Lp > st["cap"]:
+            if st["sdev"] is not None:
+                torch.cuda.synchronize(self.device)                   # (rare: nothing may still read the buffers that go)
+            st["cap"] = max(64, 1 << (Lp - 1).bit_length())
+            st["spin"] = torch.zeros(st["slay"].nbytes(st["cap"]), dtype=torch.uint8).pin_memory()
+            st["sdev"] = torch.zeros(st["slay"].nbytes(st["cap"]), dtype=torch.uint8, device=self.device)
+        st["mode"], st["Lp"] = "sessions", Lp
+        return self.pack_sessions(recs, idx0, st["slay"].views_np(st["spin"].numpy(), Lp))
+
+    def limit_violation(self, h, L):
+        """DeviceCollator's checks, same order and same messages, on the packed sequences: x, user, y and the time slots from
+        the check-ins; edge counts and degrees through bounds that cost nothing -- a count cannot exceed the largest
+        multiplicity of a POI in the session, a degree cannot exceed n -- and exactly (session_graph, numpy) only for a
+        session whose bound fails.  A session under the bound is under the limit, so the exact maximum over the failing
+        ones is the batch's."""
+        if "counts" in h:
+            return super().limit_violation(h, L)
+        recs = h["recs"]
+        xmax = int(h["seq"][:, :, 0].max())
+        if "x" in L and xmax > L["x"]:
+            return "x", xmax, L["x"] + 1
+        if "user" in L and int(h["user"].max()) > L["user"]:
+            return "user", int(h["user"].max()), L["user"] + 1
+        if "y" in L and int(h["y"].max()) > L["y"]:
+            return "y", int(h["y"].max()), L["y"] + 1
+        if "edge" in L:
+            big = [r for r in recs if r.mult + 3 >= L["edge"]]
+            if big:
+                cmax = max(int(session_graph(r.checkins[:-1])["edge_type"].max()) for r in big)
+                if cmax + 3 >= L["edge"]:
+                    return "edge_input", cmax + 3, L["edge"]
+        if "deg" in L:
+            big = [r for r in recs if r.n + 1 >= L["deg"]]
+            if big:
+                nzs = [session_graph(r.checkins[:-1])["edge_type"] != 0 for r in big]
+                dmax = max(max(int(z.sum(0).max()), int(z.sum(1).max())) for z in nzs)
+                if dmax + 1 >= L["deg"]:
+                    return "degree", dmax + 1, L["deg"]
+        if "slots" in L:
+            # (a node keeps the slot of its LAST visit: the largest slot of the history bounds the largest of the nodes)
+            big = [r for r in recs if _slot_of(int(r.checkins[:-1, 1].max())) >= L["slots"]]
+            if big:
+                tmax = max(float(session_graph(r.checkins[:-1])["time_normal"].max()) for r in big)
+                tmax = max(tmax, 0.0)                                 # (the padded batch's maximum includes the padding's 0)
+                if int(tmax * 48) >= L["slots"]:
+                    return "time_normal", tmax, L["slots"]
+        return None
+
+    def upload(self, st):
+        if st["mode"] == "dicts":
+            return super().upload(st)
+        nb = st["slay"].nbytes(st["Lp"])
+        st["sdev"][:nb].copy_(st["spin"][:nb], non_blocking=True)
+        self.to_raw(st["sdev"], st["slay"], st["Lp"], st["dev"], st["raw_dev"], st["status"])
+
+
+def _slot_of(t):
+    """The time-slot index the model looks up for a raw slot value t: int(float32(t / 48) * 48), 0 for t = 0."""
+    return int(float(np.float32(t / 48)) * 48) if t != 0 else 0

@@ -681,9 +681,11 @@ class Graphormer(nn.Module):
         near = (pos, chord2_max, mode, words): only POIs within a radius of the row's anchor are listed.  pos =
         ops.pack_positions(coords, V, offset), chord2_max = ops.chord2_of_km(r), mode "last" / "any", words an int32
         [>= G, >= ceil(V / 32)] device buffer: the step launches ops.near_words on batched_data.x into it (inside a captured
-        graph when the step is captured; a shared `allow` is ANDed in) and ranks with the rows' own words.  A trajectory graph
-        stores distinct POIs, not the visit order: "last" is the trajectory's last node (node_name[-1]), not the last check-in
-        when the walk ended on a revisit; "any" -- within r of anywhere the user has been -- does not depend on order."""
+        graph when the step is captured; a shared `allow` is ANDed in) and ranks with the rows' own words.  "last" is the
+        trajectory's last node (node_name[-1]): for graphs made from sessions (data.SessionCollator, sessions_to_trajectories,
+        gen_pickles.py) nodes are ordered by their last visit, so it is the last history check-in; a hand-made dict stores
+        distinct POIs in the order given, where it need not be.  "any" -- within r of anywhere the user has been -- does not
+        depend on order."""
         if self.training:
             raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
         with torch.no_grad():
@@ -698,8 +700,9 @@ class Graphormer(nn.Module):
                   **kw):
         """train.PredictLoop(self, collator, dataset, k=k, exclude_visited=..., candidates=..., within_km=..., coords=...,
         near=..., **kw).run(): (sample_index [n], ids [n, k], vals [n, k]) on the device.  within_km: only POIs within that many
-        km of the trajectory's last node (near="last"; not the last check-in when the walk ended on a revisit) or of any of its
-        POIs (near="any"); coords [P + 1, 2] lat / lon in degrees, default the collator's."""
+        km of the trajectory's last node (near="last": the last history check-in for sessions and graphs made from them, see
+        recommend_step) or of any of its POIs (near="any"); coords [P + 1, 2] lat / lon in degrees, default the collator's.
+        dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator."""
         from .train import PredictLoop
         max_batches = kw.pop("max_batches", None)
         return PredictLoop(self, collator, dataset, k=k, exclude_visited=exclude_visited, candidates=candidates,
@@ -709,7 +712,7 @@ class Graphormer(nn.Module):
                  near="last", **kw):
         """train.EvalLoop(self, collator, dataset, exclude_visited=..., candidates=..., split_revisits=..., within_km=...,
         coords=..., near=..., **kw).run(): the reference's validation / test protocol over a whole split, optionally over
-        restricted lists (within_km / coords / near as in recommend) and split by revisits."""
+        restricted lists (within_km / coords / near as in recommend) and split by revisits.  dataset / collator as in recommend."""
         from .train import EvalLoop
         max_batches = kw.pop("max_batches", None)
         return EvalLoop(self, collator, dataset, exclude_visited=exclude_visited, candidates=candidates,

@@ -188,6 +188,34 @@ def make_trajectory(rng, P, n_nodes, n_user, cat_of_poi=None, extra_visits=0.3):
                 time=slot.astype(np.int64), time_normal=time_normal, user=np.array([user], dtype=np.int64), cat=cat)
 
 
+def make_session(rng, P, n_nodes, n_user, cat_of_poi=None, extra_visits=0.3):
+    """One check-in session (user, checkins [L + 1, 3] int32 rows of (poi, time slot, category), the last row the target):
+    make_trajectory's walk -- every one of n_nodes distinct POIs once, then mostly local revisits -- kept as the visit-ordered
+    list it is, which is what a user has before gen_pickles.py:735-833 (data.sessions_to_trajectories) makes a graph of it."""
+    n_nodes = int(min(n_nodes, P))
+    pois = rng.choice(P, size=n_nodes, replace=False) + 1
+    walk = list(range(n_nodes))
+    cur = n_nodes - 1
+    for _ in range(rng.poisson(extra_visits * n_nodes)):
+        if rng.rand() < 0.7:
+            cur = int(np.clip(cur + rng.randint(-3, 4), 0, n_nodes - 1))
+        else:
+            cur = int(rng.randint(0, n_nodes))
+        walk.append(cur)
+    poi = np.append(pois[np.asarray(walk)], rng.randint(1, P + 1))   # history + target
+    slot = rng.randint(0, 48, size=len(poi))
+    cat = cat_of_poi[poi - 1] if cat_of_poi is not None else rng.randint(1, 9, size=len(poi))
+    return int(rng.randint(0, n_user)), np.stack([poi, slot, cat], 1).astype(np.int32)
+
+
+def make_sessions(seed, G, P, n_user, cat_of_poi=None, n_nodes: Optional[List[int]] = None, dist="fsq", hi=256):
+    """G seeded sessions with make_batch_of_trajectories' node-count distribution."""
+    rng = np.random.RandomState(seed)
+    if n_nodes is None:
+        n_nodes = sample_num_nodes(rng, G, dist=dist, hi=hi)
+    return [make_session(rng, P, int(n), n_user, cat_of_poi) for n in n_nodes]
+
+
 def trajectory_to_item(traj, idx=0):
     """Raw dict -> PyG-like item, exactly as `owndata.py:343-357` does (torch tensors)."""
     import torch

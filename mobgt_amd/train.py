@@ -1176,14 +1176,8 @@ class _StagedBatches:
             s = dict(layout=lay, buf=buf, views=views, index=None, stages=[], turn=0, side=side,
                      batch=self.collator.batch_from_views(views) if side else views,
                      copy_bytes=lay.copy_bytes if side else lay.nbytes)
-            raw_bytes = lay.raw_bytes if side else lay.nbytes
             for _ in range(2):
-                pin = torch.zeros(raw_bytes, dtype=torch.uint8).pin_memory()
-                dev = torch.zeros(lay.nbytes, dtype=torch.uint8, device=self.device)
-                dv = lay.views_torch(dev) if side else None
-                s["stages"].append(dict(pin=pin, np=lay.views_np(pin.numpy()), dev=dev, dev_views=dv,
-                                        work=None, ready=torch.cuda.Event(), free=None, used=False, index=None,
-                                        batch=None))
+                s["stages"].append(self.collator.new_stage(lay, side))      # (pinned host buffer + device staging buffer)
             # (the zero fills above are queued on the current stream, behind whatever it still runs; the copy stream writes the
             #  staging buffers next and must not overtake them -- a fill landing after the copy left a batch of zeros)
             self.copy_stream.wait_stream(torch.cuda.current_stream())
@@ -1197,48 +1191,33 @@ class _StagedBatches:
         if self.limits is None:
             # (the model says which fields it indexes tables with -- model.index_limits(); a model without the hook is not checked)
             self.limits = m.index_limits() if hasattr(m, "index_limits") else {}
-        L = self.limits
-        nz = h["counts"] != 0
-        bad = None
-        if "x" in L and int(h["x"].max()) > L["x"]:
-            bad = ("x", int(h["x"].max()), L["x"] + 1)
-        elif "user" in L and int(h["user"].max()) > L["user"]:
-            bad = ("user", int(h["user"].max()), L["user"] + 1)
-        elif "y" in L and int(h["y"].max()) > L["y"]:
-            bad = ("y", int(h["y"].max()), L["y"] + 1)
-        elif "edge" in L and int(h["counts"].max()) + 3 >= L["edge"]:
-            bad = ("edge_input", int(h["counts"].max()) + 3, L["edge"])
-        elif "deg" in L and max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1 >= L["deg"]:
-            bad = ("degree", max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1, L["deg"])
-        elif "slots" in L and int(float(h["time_normal"].max()) * 48) >= L["slots"]:
-            bad = ("time_normal", float(h["time_normal"].max()), L["slots"])
+        bad = self.collator.limit_violation(h, self.limits)      # (the collator knows its host arrays: dicts or sessions)
         if bad:
             raise IndexError(f"batch.{bad[0]} has index {bad[1]}, out of range for a table of {bad[2]} rows")
 
     def _kept(self, traj):
-        """Whether a trajectory enters a batch: longer ones than collator.max_node are dropped (as the reference's collator does)."""
-        return traj is not None and len(traj["node_name"]) <= self.collator.max_node
+        """Whether a sample enters a batch: longer ones than collator.max_node are dropped (as the reference's collator does)."""
+        return self.collator.keeps(traj)
 
     def _stage(self, ids):
-        """Host half of a step's input: raw trajectories -> the bucket's pinned buffer -> async copy to a device staging
-        buffer on the copy stream.  Returns (slot, stage)."""
+        """Host half of a step's input: raw samples (trajectory dicts, or sessions with a SessionCollator) -> the bucket's
+        pinned buffer -> async copy to a device staging buffer on the copy stream.  Returns (slot, stage)."""
         from .data import bucket_nodes
         trajs = [self.dataset[i] for i in ids]
         trajs = [t for t in trajs if self._kept(t)]
         G = len(trajs)
         if G == 0:
             return None                                # (every trajectory filtered out: the reference's collator skips such a batch too, collator.py:313)
-        N = bucket_nodes(max(len(t["node_name"]) for t in trajs), self.buckets)
+        N = bucket_nodes(max(self.collator.nodes_of(t) for t in trajs), self.buckets)
         slot = self._slot(G, N)
         st = slot["stages"][slot["turn"]]
         slot["turn"] ^= 1
         if st["free"] is not None:
             st["free"].synchronize()                   # its previous device-to-device copy has been executed
-        self.collator.pack_host(trajs, idx0=ids[:G] if len(ids) == G else 0, n_pad=N, out=st["np"])
-        self._check_host(st["np"])
+        self._check_host(self.collator.stage_host(st, trajs, ids[:G] if len(ids) == G else 0, N))
         st["used"] = True
         with torch.cuda.stream(self.copy_stream):
-            st["dev"][:st["pin"].numel()].copy_(st["pin"], non_blocking=True)
+            self.collator.upload(st)                   # (H2D; from sessions: + the kernel that builds the raw fields)
             if slot["side"]:
                 st["work"] = self.collator.finish_into(st["dev_views"], st["work"])
             st["ready"].record(self.copy_stream)
@@ -1300,10 +1279,11 @@ class EpochLoop(_StagedBatches):
 
     # ---- data order -----------------------------------------------------------------------------------------------------
     def batches_of_epoch(self, epoch):
-        from .data import balanced_batches, shard_indices
+        from .data import DeviceCollator, balanced_batches, shard_indices
         if self.balance:
             if self._lengths is None:
-                self._lengths = [len(t["node_name"]) for t in self.dataset]
+                # (the collator knows its dataset's form; a loop set up for its order alone has none: trajectory dicts)
+                self._lengths = (getattr(self, "collator", None) or DeviceCollator).lengths_of(self.dataset)
             steps = balanced_batches(self._lengths, self.world, self.batch_size, epoch=epoch, seed=self.seed, shuffle=self.shuffle,
                                      buckets=self.buckets, window=self.balance_window)
             return [s[self.rank] for s in steps]
@@ -1430,9 +1410,14 @@ class EvalLoop(_StagedBatches):
     within_km=r ranks each target among the POIs within r km of the row's anchor (ops.near_words inside the captured graph, then
     the per-row form of ops.rank_metrics_masked); it combines with the other restrictions.  coords: [P + 1, 2] lat / lon in
     degrees, row 0 the pad POI (default: the collator's coords; neither: ValueError).  near="last": the anchor is the
-    trajectory's last node -- a trajectory graph stores distinct POIs, not the visit order, so this is node_name[-1], not the
-    last check-in when the walk ended on a revisit; near="any": within r of any POI of the trajectory, which does not depend on
-    order.  A target outside its row's radius is unreachable and counts in n only."""
+    trajectory's last node, node_name[-1] -- the last history check-in for a SessionDataset and for dicts made from sessions
+    (nodes ordered by last visit); a hand-made dict stores distinct POIs in the order given, where the last node need not be the
+    last check-in; near="any": within r of any POI of the trajectory, which does not depend on order.  A target outside its
+    row's radius is unreachable and counts in n only.
+
+    dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator -- the
+    loops reach the input form through the collator only (nodes_of, keeps, lengths_of, new_stage, stage_host, limit_violation,
+    upload)."""
 
     def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
                  side_collate=True, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
@@ -1610,7 +1595,7 @@ class PredictLoop(EvalLoop):
     read at a fixed address).  Rows with fewer than k candidates end in ids -1 / vals -inf, as dropped trajectories do.
 
     within_km=r limits each list to the POIs within r km of the row's anchor, with coords and near as in EvalLoop (near="last":
-    the trajectory's last node, node_name[-1], which is not the last check-in when the walk ended on a revisit; near="any":
+    the trajectory's last node, node_name[-1]: the last history check-in when the graphs come from sessions; near="any":
     within r of any POI of the trajectory).  The rows' candidate words are built inside the captured graph (ops.near_words) from
     positions packed once here, and combine with exclude_visited and candidates."""
 
