@@ -201,22 +201,36 @@ class Graphormer(nn.Module):
         C_X = (np.arange(1, num_cats + 1)[:, None] == uniq[None, :]).astype(np.float32)
         self.register_buffer("X", torch.from_numpy(X), persistent=False)
         self.register_buffer("C_X", torch.from_numpy(C_X), persistent=False)
-        self.sparse_adj = not isinstance(uni.graph_dist, np.ndarray)
+        graph_dist, radius_graph = uni.graph_dist, None
+        from .geo import RadiusGraph
+        if isinstance(graph_dist, RadiusGraph):
+            # built from coordinates on the device (geo.radius_graph): the adjacency tensors are registered as they lie there;
+            # everything computed ONCE from the graph on the host (D_AX, the dense D_A of the bitmask configuration) is computed
+            # from its host copy exactly as for a universe read from disk, so every buffer has the bits it has today.  The
+            # bitmask configuration needs the bit words and the bf16 GCN; anything else takes the CSR path
+            radius_graph = graph_dist
+            if gcn_dtype == torch.bfloat16 and "mask" in radius_graph.forms:
+                graph_dist = radius_graph.to_dense01()
+            else:
+                radius_graph.require("csr")
+                graph_dist = radius_graph.to_scipy()
+        self.sparse_adj = not isinstance(graph_dist, np.ndarray)
         if self.sparse_adj:
             # P too large for a dense P x P adjacency (S-BIG: 100 000 POIs): the same (D+I)^-1 (A+I) as CSR, its transpose
             # as CSR, A.X once on the host (scipy); the GCN then runs on csrc/spmm.hip (modelGNN.CsrAdj)
             from scipy import sparse
             from .modelGNN import CsrAdj
-            a = sparse.csr_matrix(uni.graph_dist, dtype=np.float64)
+            a = sparse.csr_matrix(graph_dist, dtype=np.float64)
             deg = np.asarray(a.sum(axis=1)).reshape(-1) + 1.0
             a_hat = sparse.diags(1.0 / deg) @ (a + sparse.identity(P, format="csr"))
             self.register_buffer("D_AX", torch.from_numpy(np.asarray(a_hat @ X.astype(np.float64), dtype=np.float32)), persistent=False)
-            for name, t in zip(("D_A_rowptr", "D_A_col", "D_A_val", "D_AT_rowptr", "D_AT_col", "D_AT_val"), CsrAdj.from_scipy(a_hat)):
+            for name, t in zip(("D_A_rowptr", "D_A_col", "D_A_val", "D_AT_rowptr", "D_AT_col", "D_AT_val"),
+                               radius_graph.csr_adj() if radius_graph is not None else CsrAdj.from_scipy(a_hat)):
                 self.register_buffer(name, t, persistent=False)
             self.D_A = self.D_A_T = None
             self.D_mask = self.D_mask_t = self.D_scale = None
         else:
-            d_a = torch.from_numpy(calculate_laplacian_matrix(uni.graph_dist)).float()
+            d_a = torch.from_numpy(calculate_laplacian_matrix(graph_dist)).float()
             # A.X for the constant POI feature matrix, once, in fp32 (see modelGNN.GCN.forward)
             d_ax = d_a @ torch.from_numpy(X)
             self.register_buffer("D_A", d_a.to(gcn_dtype), persistent=False)
@@ -229,7 +243,7 @@ class Graphormer(nn.Module):
             packed = None
             if gcn_dtype == torch.bfloat16:
                 from .modelGNN import MaskAdj
-                packed = MaskAdj.from_dense01(uni.graph_dist)
+                packed = radius_graph.mask_adj() if radius_graph is not None else MaskAdj.from_dense01(graph_dist)
             if packed is not None and d_ax.shape[1] % 16:
                 # bitmask configuration: A X zero-padded to whole 16-deep k-steps (303 -> 304 columns) for the first
                 # GraphConvolution's GEMM + activation node (modelGNN._ConvActFn); GCN.forward slices it for any other path
