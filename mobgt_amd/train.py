@@ -23,6 +23,7 @@ import torch.distributed as dist
 
 from . import forms, ops
 from .step_state import STEP
+from .step_graphs import Entry, StepGraphs, group_key
 from .model import sync_external_shadows
 from .lr import polynomial_decay_lr
 from .accum import UpdateWindow, check_accum_args, scheduled_lr
@@ -379,6 +380,7 @@ class TrainStep:
         n = self.flat.flat.numel()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.shadow_flat = None
         self.shadow_flat = self._attach_shadows()
         self._step_base = None
         self.betas, self.eps = (0.9, 0.999), 1e-8
@@ -393,7 +395,9 @@ class TrainStep:
         self.window = UpdateWindow(self.accumulate)
         self._set_lr()
         self.use_graph = use_graph
-        self.graphs = {}
+        self.graphs = StepGraphs()                            # every captured hipGraph of this trainer (step_graphs.py)
+        self.fused_opt = False                                # prepare(): AdamW rides at the end of every batch's step graph
+        self.faults_recovered = 0
         self._loss_ref = torch.zeros((), device=dev)          # the loss tensor of the step that ran last
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # MOBGT_FORCE_COMM=1 (tests): a process group of ONE rank takes the data-parallel path -- buckets, exchange on the
@@ -418,12 +422,10 @@ class TrainStep:
         if self.overlap and self._accum:
             raise NotImplementedError("TrainStep: accumulate > 1 / clip_norm are not built for the `overlap` form of the data-parallel "
                                       "step (its exchange runs beside the backward of every micro-step); use the default form")
-        self.graphs_b, self._g_enc, self._loss_slots, self.enc_outs = {}, {}, {}, {}
-        self._loss_slots_nocomm = {}
+        self.enc_outs = {}
         self._plan_buckets()
         self.one_graph = bool(self.ddp and use_graph and not self.overlap and dist.get_backend() == "nccl"
                               and not forms.on("ddp_host_exchange"))
-        self.graphs_nocomm = {}
         self.comm = True        # False: skip the gradient exchange (bench.py measures the exposed all-reduce time that way)
         self._prepared = False
         self.comm_buf = (torch.empty(self.flat.flat.numel(), dtype=grad_comm_dtype, device=dev)
@@ -433,7 +435,7 @@ class TrainStep:
         # the scale 1/k * coef the optimizer applies, and the per-UPDATE counter AdamW's t and the in-kernel schedule read.
         # With k = 1 (clipping only) the flat gradient buffer itself is what the update consumes.
         self.acc = self.partials = self.grad_norm = self.scale_dev = self.upd_dev = None
-        self.upd_graph, self.upd_graph_nocomm, self.exchanges_done = None, None, 0
+        self.exchanges_done = 0
         if self._accum:
             n = self.flat.flat.numel()
             from . import _lib
@@ -501,7 +503,7 @@ class TrainStep:
         h = hashlib.sha256()
         for p, off in zip(self.flat.params, self.flat.offsets):
             h.update(("%s:%d:%d;" % (names.get(id(p), "?"), off, p.numel())).encode())
-        h.update(("n=%d;head=%d;parts=%s" % (self.flat.flat.numel(), self.n_head_elems, [p[1:] for p in getattr(self, "parts", [])])).encode())
+        h.update(("n=%d;head=%d;parts=%s" % (self.flat.flat.numel(), self.n_head_elems, [p[1:] for p in self.parts])).encode())
         return h.digest()[:8]
 
     def check_layout_across_ranks(self):
@@ -544,7 +546,7 @@ class TrainStep:
         """Re-derive the bf16 shadow weights from the fp32 masters.  The optimizer kernel keeps them current step by
         step; anything ELSE that writes parameters after this TrainStep was built (checkpoint load, broadcast, manual
         edits) must call this (checkpoint.load_lightning_checkpoint and train.broadcast_parameters do)."""
-        if getattr(self, "shadow_flat", None) is not None:
+        if self.shadow_flat is not None:
             with torch.no_grad():
                 self.shadow_flat.copy_(self.flat_params.tensor)
 
@@ -626,13 +628,15 @@ class TrainStep:
         _lib.call("mobgt_step_prologue_skip", _p(self.flat.flat), self.flat.flat.numel(), lo, hi, _p(self.arena.buf),
                   self.arena.buf.numel(), _p(self.seed_dev), _stream())
 
-    def _fwd_bwd(self, batch, slot=None):
+    def _fwd_bwd(self, batch, rows=None):
+        """Prologue, forward, loss, backward -> the detached loss: it stays where the loss kernel wrote it (inside a capture the
+        graph's static output, no copy launch)."""
         self._prologue()
         loss = self._loss(batch)
-        if slot is not None and self.keep_head_rows and getattr(self.model, "_enc_out", None) is not None:
+        if rows is not None and self.keep_head_rows and getattr(self.model, "_enc_out", None) is not None:
             # (parity tests: a copy of the encoder output's graph-token rows -- what the classifier head reads -- as one more node
             #  of this batch's graph; the encoder output itself is overwritten in place by the backward pass)
-            self.enc_outs[slot] = self.model._enc_out[:, 0, :].detach().clone()
+            self.enc_outs[rows] = self.model._enc_out[:, 0, :].detach().clone()
         with ops.recording_wgrads(self._defer):  # leaf weight gradients are recorded and issued as ONE launch behind the pass,
             loss.backward(gradient=ops.unit_grad(loss.device))                                # before anything reads a gradient
         ops.set_zero_arena(None)
@@ -641,22 +645,15 @@ class TrainStep:
             raise RuntimeError(f"mobgt: the step left parked work behind {left} -- its gradients are incomplete (another model's "
                                "forward / backward inside this step?)")
         self.flat.gather()
-        self._keep_loss(loss, slot)
-
-    def _keep_loss(self, loss, slot):
-        """The loss scalar stays where the loss kernel wrote it (a graph's static output), no copy launch."""
-        loss = loss.detach()
-        if slot is None:
-            self._loss_ref = loss
-        else:
-            self._loss_slots[slot] = loss
+        return loss.detach()
 
     @property
     def loss_out(self):
         return self._loss_ref
 
-    # ---- the same step in two phases (data parallel): [forward, loss, head backward] | [rest of the backward]
-    def _phase_a(self, batch, i):
+    # ---- the same step in two phases (data parallel): [forward, loss, head backward] | [rest of the backward]; what one phase
+    # hands to the next is (a tensor of the autograd graph, its gradient)
+    def _phase_a(self, batch):
         self._prologue()
         loss = self._loss(batch)
         enc = self.model._enc_out
@@ -664,26 +661,26 @@ class TrainStep:
         with ops.recording_wgrads(self._defer):
             grads = torch.autograd.grad(loss, head + [enc], grad_outputs=ops.unit_grad(loss.device), allow_unused=True)   # frees only the nodes it ran
         self.flat.gather(0, self.n_head, grads=list(grads[:-1]))
-        self._g_enc[i] = (enc, grads[-1])
-        self._keep_loss(loss, i)
+        return loss.detach(), (enc, grads[-1])
 
-    def _phase_b(self, i):
-        enc, g_enc = self._g_enc[i]
+    def _phase_b(self, hand):
+        enc, g_enc = hand
         with ops.recording_wgrads(self._defer):
             torch.autograd.backward([enc], [g_enc])
         ops.set_zero_arena(None)
         self.flat.gather(self.n_head, None)
 
-    def _phase_b_part(self, i, s):
-        """Part s of phase B (see _plan_buckets): from the gradient the previous part left at its cut down to this part's cut."""
+    def _phase_b_part(self, hand, s):
+        """Part s of phase B (see _plan_buckets): from the gradient the previous part left at its cut down to this part's cut
+        -> the hand-over to part s + 1."""
         li, lo, hi, _, _ = self.parts[s]
-        src, g_src = self._g_enc[i]
+        src, g_src = hand
         last = li is None
         with ops.recording_wgrads(self._defer):
             if not last:
                 cut = self.model._cuts[li]
                 grads = torch.autograd.grad([src], self.flat.params[lo:hi] + [cut], grad_outputs=[g_src], allow_unused=True)
-                self._g_enc[i] = (cut, grads[-1])
+                hand = (cut, grads[-1])
                 grads = list(grads[:-1])
             else:
                 # (the bias tables' node hangs off every layer through the pack's token, not off the encoder input: name it)
@@ -697,6 +694,7 @@ class TrainStep:
         if last:
             ops.set_zero_arena(None)
         self.flat.gather(lo, hi, grads=grads)
+        return hand
 
     def _warmup(self, i, check=False):
         """One eager pass of batch i on the capture stream (allocator, lazy initialisations) that does not count as a training
@@ -741,36 +739,6 @@ class TrainStep:
         if check and extra:
             raise RuntimeError(f"TrainStep.add_batch: this batch reaches parameters the trainer was not built for: {extra[:5]}")
 
-    def _capture(self, i, warm=True):
-        batch = self.batches[i]
-        if warm:
-            self._warmup(i)
-        g = torch.cuda.CUDAGraph()
-        # private memory pool per graph: the graphs are replayed in data order, not capture order, and a shared
-        # pool is only safe for capture-order replay (measured: NaNs on the second lap with a shared pool)
-        if not self.overlap:
-            with self._capturing(g):
-                self._fwd_bwd(batch, slot=i)
-            return g
-        # two graphs over ONE autograd graph: phase B is captured right after phase A and replays its kernels on the
-        # activations phase A's replay leaves at the same addresses (A's private pool; nothing else writes there)
-        with self._capturing(g):
-            self._phase_a(batch, i)
-        if self.parts:
-            gbs = []
-            for s in range(len(self.parts)):
-                gb = torch.cuda.CUDAGraph()
-                with self._capturing(gb):
-                    self._phase_b_part(i, s)
-                gbs.append(gb)
-            self.graphs_b[i] = gbs
-            return g
-        gb = torch.cuda.CUDAGraph()
-        with self._capturing(gb):
-            self._phase_b(i)
-        self.graphs_b[i] = [gb]
-        return g
-
     def _exchange(self, buf=None):
         """Sum of the flat gradient buffer (`buf`: the window's accumulator instead) over the ranks and the average, issued on the
         CURRENT stream (eager, or as nodes of the step graph being captured): through the bf16 exchange buffer when there is one
@@ -789,69 +757,100 @@ class TrainStep:
         else:                                  # (one forced rank: the collective itself, no division)
             dist.all_reduce(buf, op=dist.ReduceOp.SUM)
 
+    # ---- captures: one routine per kind of entry (step_graphs.py), each returns the Entry it captured ----------------------
+    def _capture_step(self, j, comm, warm=True):
+        """("step", j, comm).  fused_opt: the whole step as ONE graph -- forward + backward [+ the gradient exchange on this stream:
+        `comm`] + AdamW; host exchange: forward + backward; overlap: phase A, then phase B whole or in its parts."""
+        batch = self.batches[j]
+        if warm:
+            self._warmup(j)
+        g = torch.cuda.CUDAGraph()
+        # private memory pool per graph: the graphs are replayed in data order, not capture order, and a shared
+        # pool is only safe for capture-order replay (measured: NaNs on the second lap with a shared pool)
+        if not self.overlap:
+            with self._capturing(g):
+                loss = self._fwd_bwd(batch, rows=j)
+                if comm:
+                    self._exchange()
+                if self.fused_opt:
+                    self._opt_step()
+            return Entry((g,), loss)
+        # several graphs over ONE autograd graph: phase B is captured right after phase A and replays its kernels on the
+        # activations phase A's replay leaves at the same addresses (A's private pool; nothing else writes there)
+        with self._capturing(g):
+            loss, hand = self._phase_a(batch)
+        gbs = []
+        for s in range(max(1, len(self.parts))):
+            gbs.append(torch.cuda.CUDAGraph())
+            with self._capturing(gbs[-1]):
+                hand = self._phase_b_part(hand, s) if self.parts else self._phase_b(hand)
+        return Entry((g, *gbs), loss)
+
+    def _capture_opt(self):
+        g = torch.cuda.CUDAGraph()
+        with self._capturing(g):
+            self._opt_step()
+        return Entry((g,), None)
+
     def prepare(self):
-        """Capture one forward/backward graph per batch and one optimizer graph."""
+        """Capture every batch's step (or micro-step) and, in the forms that replay them, the optimizer / update graphs."""
         if not self.use_graph:
             return
-        self.pool = torch.cuda.graph_pool_handle()
+        self.fused_opt = not self._accum and not self.overlap and (not self.ddp or self.one_graph)
+        self._capture_all(first=True)
+        self._prepared = True
+
+    def _capture_all(self, first=False):
+        """The eager capture loop of prepare() (`first`: with the one-off first calls) and recapture(): per batch a warm-up pass
+        and ONE capture.  Single process, or the exchange captured (`one_graph`): the optimizer rides at the end of every batch's
+        graph -- one graph launch per step instead of two (the boundary between two replayed graphs idles the device for
+        ~8.7 us: `tools/prof_gaps.sh`); the other forms replay a stand-alone optimizer / update graph, captured behind the batches."""
+        for j in range(len(self.batches)):
+            self._warmup(j)
+            if first and j == 0:
+                self._first_calls()
+            self._capture_batch(j)
         if self._accum:
-            return self._prepare_accum()
-        for i in range(len(self.batches)):
-            self.graphs[i] = self._capture(i)
-        # One eager optimizer call before the capture (first-launch initialisation must not happen inside a capture),
-        # made side-effect free: parameters, shadows and both Adam moments are put back, so the first replayed step is
-        # AdamW's t = 1 on fresh moments, exactly like torch.optim.AdamW's first step -- on every rank alike.
+            self.graphs.get(("update", self.one_graph), self._capture_update, self.one_graph)
+        elif not self.fused_opt:
+            self.graphs.get(("opt",), self._capture_opt)
+
+    def _capture_batch(self, j):
+        """The entry every step of batch j replays by default, behind that batch's warm-up pass."""
+        if self._accum:
+            return self.graphs.get(("micro", j), self._capture_micro, j, False)
+        return self.graphs.get(("step", j, self.one_graph), self._capture_step, j, self.one_graph, False)
+
+    def _first_calls(self):
+        """One eager pass over the optimizer's / the update's launches and the collective on these buffers before ANY capture
+        that holds them (first-launch initialisation must not happen inside a capture), made side-effect free: parameters,
+        shadows, both Adam moments, the accumulator and the update counter are put back, so the first replayed update is AdamW's
+        t = 1 on fresh moments, exactly like torch.optim.AdamW's first step -- on every rank alike."""
         with self._on_stream():
             with torch.no_grad():
                 saved = self.flat_params.tensor.detach().clone()
-                self._step_base = int(self.seed_dev.item()) - 1
-                self._opt_step()
+                if self._accum:
+                    if self.one_graph:
+                        self._exchange(self._gsrc)
+                    self._accumulate()
+                    self._update_kernels()
+                    if self.acc is not None:
+                        self.acc.zero_()
+                    self.upd_dev.zero_()
+                else:
+                    self._step_base = int(self.seed_dev.item()) - 1
+                    self._opt_step()
+                    if self.one_graph:
+                        self._exchange()
                 self.flat_params.tensor.copy_(saved)
                 self.exp_avg.zero_()
                 self.exp_avg_sq.zero_()
                 self.flat.flat.zero_()
                 self.sync_shadows()
-            # every later prologue (one per replayed step) advances the counter by one: t = counter - base = 1, 2, ...
-            self._step_base = int(self.seed_dev.item())
+            if not self._accum:
+                # every later prologue (one per replayed step) advances the counter by one: t = counter - base = 1, 2, ...
+                self._step_base = int(self.seed_dev.item())
         self._join()
-        self.opt_graph = torch.cuda.CUDAGraph()
-        with self._capturing(self.opt_graph):
-            self._opt_step()
-        # Single process, no all-reduce between backward and optimizer: the optimizer rides at the end of every batch's
-        # graph -- one graph launch per step instead of two (the boundary between two replayed graphs idles the device
-        # for ~8.7 us: `tools/prof_gaps.sh`).  Every warm-up has run by now, so this second capture only records.
-        self.fused_opt = (not self.overlap and (not self.ddp or self.one_graph))
-        if self.fused_opt:
-            if self.one_graph:
-                with self._on_stream():            # (the collective's first call on these buffers: outside any capture)
-                    saved = self.flat.flat.clone()
-                    self._exchange()
-                    self.flat.flat.copy_(saved)
-                self._join()
-            for i in range(len(self.batches)):
-                self._capture_with_opt(i)
-        self._prepared = True
-
-    def _capture_with_opt(self, i, comm=None):
-        """The whole step of batch i as ONE graph: forward + backward [+ gradient exchange on this stream: `one_graph`] + AdamW."""
-        comm = self.one_graph if comm is None else comm
-        g = torch.cuda.CUDAGraph()
-        main = comm or not self.one_graph
-        kept = self._loss_slots.get(i)
-        with self._capturing(g):
-            self._fwd_bwd(self.batches[i], slot=i)
-            if comm:
-                self._exchange()
-            self._opt_step()
-        if main:
-            self.graphs[i] = g
-        else:
-            # (ADVICE r5: the no-exchange twin writes its loss into its OWN static tensor -- the main graph's slot keeps pointing at
-            #  the main graph's output, whichever of the two was captured last)
-            self.graphs_nocomm[i] = g
-            self._loss_slots_nocomm[i] = self._loss_slots[i]
-            if kept is not None:
-                self._loss_slots[i] = kept
 
     # ---- accumulation windows and global-norm clipping (DESIGN 13) ----------------------------------------------------------
     # A micro-step is [prologue, forward, backward, accumulate]: ONE graph per batch whatever its position in the window (the
@@ -887,78 +886,46 @@ class TrainStep:
                   _p(self.scale_dev), 1 if self.acc is not None else 0, self.betas[0], self.betas[1],
                   self.eps, float(self.model.weight_decay), _stream())
 
-    def _capture_micro(self, i, warm=True):
+    def _capture_micro(self, j, warm=True):
+        """("micro", j)"""
         if warm:
-            self._warmup(i)
+            self._warmup(j)
         g = torch.cuda.CUDAGraph()
         with self._capturing(g):
-            self._fwd_bwd(self.batches[i], slot=i)
+            loss = self._fwd_bwd(self.batches[j], rows=j)
             self._accumulate()
-        return g
+        return Entry((g,), loss)
 
     def _capture_update(self, comm):
+        """("update", comm): [the captured exchange,] norm, finish, AdamW.  Does not depend on a batch."""
         g = torch.cuda.CUDAGraph()
         with self._capturing(g):
             if comm:
                 self._exchange(self._gsrc)
             self._update_kernels()
-        return g
-
-    def _prepare_accum(self):
-        # one eager pass over the new launches (and the collective on these buffers) before ANY capture that holds them (first
-        # launches must not happen inside a capture), made side-effect free: parameters, moments, accumulator and the update
-        # counter are put back -- the first update is AdamW's t = 1
-        with self._on_stream():
-            with torch.no_grad():
-                saved = self.flat_params.tensor.detach().clone()
-                if self.one_graph:
-                    self._exchange(self._gsrc)
-                self._accumulate()
-                self._update_kernels()
-                self.flat_params.tensor.copy_(saved)
-                self.exp_avg.zero_()
-                self.exp_avg_sq.zero_()
-                self.flat.flat.zero_()
-                if self.acc is not None:
-                    self.acc.zero_()
-                self.upd_dev.zero_()
-                self.sync_shadows()
-        self._join()
-        for i in range(len(self.batches)):
-            self.graphs[i] = self._capture_micro(i)
-        self.fused_opt = False
-        self.upd_graph = self._capture_update(comm=self.one_graph)
-        self.upd_graph_nocomm = None
-        self._prepared = True
+        return Entry((g,), None)
 
     def _update(self):
         """The optimizer update that ends a window (the host bookkeeping -- `self.window` -- has been done by the caller)."""
         comm = self.ddp and self.comm
         if comm:
             self.exchanges_done += 1
-        if self.use_graph and self.one_graph:
-            if comm:
-                self.upd_graph.replay()                          # (the captured exchange, norm, finish, AdamW)
-            else:
-                if self.upd_graph_nocomm is None:
-                    self.upd_graph_nocomm = self._capture_update(comm=False)
-                self.upd_graph_nocomm.replay()
+        captured = bool(comm and self.use_graph and self.one_graph)
+        if comm and not captured:
+            self._exchange(self._gsrc)                           # (issued by the host: gloo, MOBGT_DDP_HOST_EXCHANGE, eager)
+        if self.use_graph:                                       # (the twin without the exchange: captured on first use)
+            self.graphs.get(("update", captured), self._capture_update, captured).graphs[0].replay()
         else:
-            if comm:
-                self._exchange(self._gsrc)                       # (issued by the host: gloo, MOBGT_DDP_HOST_EXCHANGE, eager)
-            if self.use_graph:
-                self.upd_graph.replay()
-            else:
-                self._update_kernels()
+            self._update_kernels()
         self._set_lr()
 
     def _step_accum(self, i):
         j = i % len(self.batches)
         if self.use_graph:
-            self._loss_ref = self._loss_slots[j]
-            self.graphs[j].replay()
+            graphs, self._loss_ref = self.graphs.get(("micro", j), self._capture_micro, j, False)
+            graphs[0].replay()
         else:
-            self._fwd_bwd(self.batches[j])
+            self._loss_ref = self._fwd_bwd(self.batches[j])
             self._accumulate()
         if self.window.step(self.sched_state):
             self._update()
@@ -976,33 +943,29 @@ class TrainStep:
     # lives on the host -- the dropout stream, AdamW's t and the learning-rate schedule are device counters the step's own
     # kernels advance -- so k consecutive steps on pre-collated batches can be ONE graph: k x (forward, backward [, exchange],
     # AdamW), one replay, no host round trip between them.  The graph holds k steps' activations (S-FSQ: ~30 MB per step).
-    def _capture_group(self, i0, k):
-        if not (self.use_graph and self._prepared and getattr(self, "fused_opt", False) and self.sched_dev is not None):
+    def _capture_group(self, batches, comm):
+        """("group", batches, comm): the steps of those batches, one behind the other, as ONE graph."""
+        if not (self._prepared and self.fused_opt and self.sched_dev is not None):
             raise RuntimeError("TrainStep.step_group needs prepare(), hipGraphs, the one-graph step form and the device-side schedule")
-        nb = len(self.batches)
         g = torch.cuda.CUDAGraph()
         with self._capturing(g):
-            for j in range(k):
-                self._fwd_bwd(self.batches[(i0 + j) % nb], slot=("group", i0, k, j))
-                if self.one_graph:
+            for j in batches:
+                loss = self._fwd_bwd(self.batches[j])
+                if comm:
                     self._exchange()
                 self._opt_step()
-        self.graphs_group[(i0, k)] = g
+        return Entry((g,), loss)
 
     def step_group(self, i, k):
         """Steps i, i + 1, ... i + k - 1 (batches taken cyclically from the pre-collated pool, like k calls of `step`) as ONE
         graph replay; -> the last step's loss tensor.  Same arithmetic, same counters, same order as k single steps."""
         if self._accum:
             raise NotImplementedError("TrainStep.step_group is not built for accumulate > 1 / clip_norm: call step() per micro-step")
-        nb = len(self.batches)
-        key = (i % nb, int(k))
-        if not hasattr(self, "graphs_group"):
-            self.graphs_group = {}
-        if key not in self.graphs_group:
-            self._capture_group(*key)
-        self._loss_ref = self._loss_slots[("group", key[0], key[1], key[1] - 1)]
-        self.graphs_group[key].replay()
-        self.window.updated(self.sched_state, key[1])
+        comm = self.ddp and self.comm
+        key = group_key(i, int(k), len(self.batches), comm)
+        graphs, self._loss_ref = self.graphs.get(key, self._capture_group, key[1], comm)
+        graphs[0].replay()
+        self.window.updated(self.sched_state, int(k))
         self._set_lr()
         return self.loss_out
 
@@ -1012,17 +975,8 @@ class TrainStep:
         optimizer state and the step counter are left as they are."""
         if not (self.use_graph and self._prepared):
             return
-        self.graphs_nocomm.clear()
-        if self._accum:                                  # (every micro-step graph, and the update graphs with them)
-            for i in range(len(self.batches)):
-                self.graphs[i] = self._capture_micro(i)
-            self.upd_graph = self._capture_update(comm=self.one_graph)
-            self.upd_graph_nocomm = None
-            return
-        for i in range(len(self.batches)):
-            self.graphs[i] = self._capture(i)
-            if self.fused_opt:
-                self._capture_with_opt(i)
+        self.graphs.clear()          # (what is captured on first use -- the twins without exchange, groups -- comes back that way)
+        self._capture_all()
 
     def check_faults(self, on_fault="raise"):
         """Workgroups that gave up waiting for their cluster partners / at a grid barrier since the last check ({} = none;
@@ -1068,7 +1022,7 @@ class TrainStep:
         forms.set("safe_forms", True)
         ops.set_peer_wait_limit(0, 0)
         self.recapture()
-        self.faults_recovered = getattr(self, "faults_recovered", 0) + 1
+        self.faults_recovered += 1
         loss = self.step(i)
         self.check_faults(on_fault="raise")
         return loss
@@ -1084,12 +1038,7 @@ class TrainStep:
             self.batches.pop()
             raise
         if self.use_graph and self._prepared:
-            if self._accum:
-                self.graphs[i] = self._capture_micro(i, warm=False)     # (the update graphs do not depend on the batch)
-            elif self.fused_opt:
-                self._capture_with_opt(i)               # (the whole step as one graph: no forward / backward-only graph beside it)
-            else:
-                self.graphs[i] = self._capture(i, warm=False)
+            self._capture_batch(i)                      # (nothing else in the cache depends on the number of batches)
         return i
 
     def step(self, i):
@@ -1097,62 +1046,48 @@ class TrainStep:
         `accumulate` / `clip_norm`: one micro-step; the window's last one also updates.  -> this batch's loss."""
         if self._accum:
             return self._step_accum(i)
+        j = i % len(self.batches)
         if self.use_graph:
-            self._loss_ref = self._loss_slots[i % len(self.batches)]
-        if self.one_graph and self.use_graph and getattr(self, "fused_opt", False):
-            j = i % len(self.batches)
-            if self.comm:
-                self.graphs[j].replay()                         # (forward, backward, the captured exchange, AdamW)
+            # (comm: the exchange as a node of the graph; bench.py runs the same step without it, captured on first use)
+            comm = self.one_graph and self.comm
+            graphs, self._loss_ref = self.graphs.get(("step", j, comm), self._capture_step, j, comm, False)
+            if self.overlap:
+                self._replay_overlap(graphs)
             else:
-                if j not in self.graphs_nocomm:                 # (bench.py: the same step without its exchange)
-                    self._capture_with_opt(j, comm=False)
-                self._loss_ref = self._loss_slots_nocomm[j]     # (the loss of the graph that is replayed)
-                self.graphs_nocomm[j].replay()
-            self.window.updated(self.sched_state)
-            self._set_lr()
-            return self.loss_out
-        if self.overlap:
-            j = i % len(self.batches)
-            na = self.n_head_elems
-            comm = self.ddp and self.comm
-            self.graphs[j].replay()
-            cb = self.comm_buf
-            # element ranges completed by phase A and by each part of phase B: every one is all-reduced (RCCL's stream) as soon
-            # as the replay that completes it has been enqueued, i.e. beside the replay of the next part
-            bounds = [(0, na)] + ([(e0, e1) for _, _, _, e0, e1 in self.parts] if self.parts else [(na, self.flat.flat.numel())])
-            works = []
-
-            def exchange(e0, e1):
-                if comm and e1 > e0:
-                    if cb is not None:
-                        cb[e0:e1].copy_(self.flat.flat[e0:e1])
-                    works.append(dist.all_reduce((cb if cb is not None else self.flat.flat)[e0:e1], op=dist.ReduceOp.SUM, async_op=True))
-            exchange(*bounds[0])
-            for gb, (e0, e1) in zip(self.graphs_b[j], bounds[1:]):
-                gb.replay()
-                exchange(e0, e1)
-            if comm:
-                for w in works:
-                    w.wait()
-                if cb is not None:
-                    torch.mul(cb, 1.0 / self.world, out=self.flat.flat)          # widen + average in one pass
-                else:
-                    self.flat.flat.div_(self.world)
+                graphs[0].replay()
         else:
+            self._loss_ref = self._fwd_bwd(self.batches[j])
+        if not self.fused_opt:
+            if self.ddp and self.comm and not self.overlap:
+                self._exchange()                                    # (issued by the host: gloo, MOBGT_DDP_HOST_EXCHANGE, eager)
             if self.use_graph:
-                self.graphs[i % len(self.batches)].replay()
+                self.graphs.get(("opt",), self._capture_opt).graphs[0].replay()
             else:
-                self._fwd_bwd(self.batches[i % len(self.batches)])
-            if self.ddp and self.comm:
-                self._exchange()
-        if self.use_graph:
-            if not getattr(self, "fused_opt", False):
-                self.opt_graph.replay()
-        else:
-            self._opt_step()
+                self._opt_step()
         self.window.updated(self.sched_state)
         self._set_lr()
         return self.loss_out
+
+    def _replay_overlap(self, graphs):
+        """Phase A, then the parts of phase B: every element range of the flat buffer is all-reduced (RCCL's stream) as soon as the
+        replay that completes it has been enqueued, i.e. beside the replay of the next part."""
+        na, cb = self.n_head_elems, self.comm_buf
+        comm = self.ddp and self.comm
+        bounds = [(0, na)] + ([(e0, e1) for _, _, _, e0, e1 in self.parts] if self.parts else [(na, self.flat.flat.numel())])
+        works = []
+        for g, (e0, e1) in zip(graphs, bounds):
+            g.replay()
+            if comm and e1 > e0:
+                if cb is not None:
+                    cb[e0:e1].copy_(self.flat.flat[e0:e1])
+                works.append(dist.all_reduce((cb if cb is not None else self.flat.flat)[e0:e1], op=dist.ReduceOp.SUM, async_op=True))
+        if comm:
+            for w in works:
+                w.wait()
+            if cb is not None:
+                torch.mul(cb, 1.0 / self.world, out=self.flat.flat)          # widen + average in one pass
+            else:
+                self.flat.flat.div_(self.world)
 
 
 class _StagedBatches:

@@ -381,7 +381,7 @@ def test_default_arguments_are_the_plain_step_and_launch_nothing_new(monkeypatch
         torch.cuda.synchronize()
         monkeypatch.setattr(_lib, "lib", lambda: real)
         assert float(rm.abs().max()) > 0
-        assert ts.acc is None and ts.partials is None and ts.grad_norm is None and ts.upd_dev is None and ts.upd_graph is None
+        assert ts.acc is None and ts.partials is None and ts.grad_norm is None and ts.upd_dev is None and not ts.graphs.of("update")
         assert ts.fused_opt and ts.updates_done == 5 and ts.window_pos == 0 and ts.sched_state["step_count"] == 6
         ts.flush()
         assert ts.updates_done == 5
@@ -471,7 +471,7 @@ def test_guarded_step_rerun_counts_the_micro_step_once(monkeypatch):
                 ts.guarded_step(i)
                 trace.append((ts.window_pos, ts.updates_done, int(ts.upd_dev.item()), int(ts.seed_dev.item()), ts.sched_state["step_count"]))
             monkeypatch.setattr(ops, "peer_wait_faults", real)
-            assert getattr(ts, "faults_recovered", 0) == (1 if tag == "faulted" else 0)
+            assert ts.faults_recovered == (1 if tag == "faulted" else 0)
             runs[tag] = (trace, (ts.flat_params.tensor.detach() - p0).double(), ts.acc.clone(), float(ts.grad_norm))
             forms.set("safe_forms", None)
             ops.set_peer_wait_limit(0)

@@ -141,7 +141,7 @@ def test_epoch_over_the_s_gow_pool_visits_the_distributed_samplers_set(rank, wor
     assert all(k[1] in BUCKETS for k in keys) and len(keys) == res["graphs"]
     lens = [len(data[i]["node_name"]) for i in res["sample_ids"]]
     assert max(k[1] for k in keys) == bucket_nodes(max(lens))
-    assert len(keys) <= len(loop.ts.graphs) <= 2 * len(keys)       # (round 4: one step graph per staging buffer of a bucket)
+    assert len(keys) <= len(loop.ts.graphs.of("step")) <= 2 * len(keys)       # (round 4: one step graph per staging buffer of a bucket)
     assert np.isfinite(float(loop.ts.loss_out.item()))
     # same epoch seed + rank -> the torch sampler itself
     from torch.utils.data.distributed import DistributedSampler

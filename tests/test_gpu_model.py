@@ -390,7 +390,7 @@ def test_two_phase_backward_matches_single_phase(monkeypatch):
         ts.prepare()
         assert ts.overlap == (mode == "force")
         if mode == "force":          # (round 4: phase B in parts -- [layer 1], [layer 0], [everything below the encoder])
-            assert [p[0] for p in ts.parts] == [1, 0, None] and len(ts.graphs_b[0]) == 3
+            assert [p[0] for p in ts.parts] == [1, 0, None] and len(ts.graphs.of("step")[("step", 0, False)].graphs) == 1 + 3
         losses = []
         for i in range(3):
             losses.append(float(ts.step(i)))
