@@ -7,7 +7,15 @@ the result there in the forms the GCN kernels read: the bit words of modelGNN.Ma
 
 The rule (include/mobgt_geo.h): pair (i, j), i != j, is an edge iff 0 < |u_i - u_j|^2 <= 4 sin^2(r / 2R) in f64, u the unit
 vectors of the two POIs, R = 6371 km.  It agrees with `0 < haversine <= r` except for pairs within rounding (~1e-9 km) of
-the radius or of distance zero; POIs with identical coordinates are not neighbours, as in the reference."""
+the radius or of distance zero; POIs with identical coordinates are not neighbours, as in the reference.
+
+The distance bins from coordinates: `poi_pos`, the distance-bin index of every POI pair.  The reference takes the
+Freedman-Diaconis bin count from two percentiles and the maximum of a (P+1) x (P+1) f64 distance matrix (collator.py:301-308) and
+digitizes the matrix against np.histogram's edges (collator.py:429-437).  `distance_bins` derives the same bin count, the same
+edges and the int16 bin table DeviceCollator(bin_table=) reads from the unit vectors on the device (csrc_bins/bins.hip through
+_lib_bins): order statistics of the squared chord by a radix select that stores nothing of size P^2, then a search of every
+pair's squared chord among the edges mapped to squared chords.  `distance_bins_host` is the same rule in numpy."""
+import dataclasses
 import math
 
 import numpy as np
@@ -250,3 +258,205 @@ def radius_graph_host(coords_deg, radius_km=3.0, forms=FORMS, pad_row=False):
         g.rowptr, g.col = row_offsets(g.deg), t(np.concatenate(cols))
         g.val = torch.repeat_interleave(g.scale(), g.deg.long() + 1)
     return g
+
+
+# ---- the distance bins ----------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class DistanceBins:
+    """The distance bins of P POIs (POI 1..P in row order): what collator.py:301-308 and :429-437 compute from the distance matrix.
+
+    num_bins    the Freedman-Diaconis bin count
+    edges       f64 [num_bins + 1] km: np.histogram's edges, poi_pos = np.digitize(distance, edges)
+    thresholds  f64 [num_bins + 1]: the edges as squared chords of unit vectors (the first 0, the last the farthest pair's own)
+    table       int16 [(P+1), (P+1)] | None: poi_pos of every pair, row / column 0 = the pad POI (DeviceCollator(bin_table=))"""
+    P: int
+    num_bins: int
+    edges: np.ndarray
+    thresholds: np.ndarray
+    table: object = None
+
+
+def chord2_to_km(c2):
+    """Squared chord of two unit vectors -> great-circle distance: 2 R arcsin(sqrt(c2) / 2)."""
+    return 2.0 * EARTH_RADIUS_KM * np.arcsin(np.minimum(np.sqrt(np.asarray(c2, dtype=np.float64)) / 2.0, 1.0))
+
+
+def _select(digit_counts, digit_bits, n, ranks, info=None):
+    """The host loop of the radix select: the order statistics at 0-based `ranks` of a multiset of n non-negative f64, which
+    order as their 64-bit patterns.  digit_counts(prefix, prefix_bits) -> int64 [2^digit_bits]: how many elements whose pattern
+    starts with `prefix` have each next digit.  64 / digit_bits calls per rank; ranks that share a prefix share the call."""
+    seen = {}
+    out = np.empty(len(ranks), dtype=np.uint64)
+    for q, rank in enumerate(ranks):
+        rank = int(rank)
+        if not 0 <= rank < n:
+            raise ValueError(f"ranks: {rank} is not in 0 .. {n - 1}")
+        prefix = below = 0
+        for bits in range(0, 64, digit_bits):
+            if (prefix, bits) not in seen:
+                seen[prefix, bits] = np.cumsum(digit_counts(prefix, bits))
+            cum = seen[prefix, bits]
+            digit = int(np.searchsorted(cum, rank - below, side="right"))            # the first digit with cum > rank - below
+            if digit >= cum.size or (bits == 0 and int(cum[-1]) != n):
+                raise RuntimeError(f"radix select: the histogram below prefix {prefix:#x} ({bits} bits) holds {int(cum[-1])} "
+                                   f"elements, rank {rank} of {n} is not among them")
+            below += int(cum[digit - 1]) if digit else 0
+            prefix = (prefix << digit_bits) | digit
+        out[q] = prefix
+    if info is not None:
+        info["launches"] = info.get("launches", 0) + len(seen)
+    return out.view(np.float64)
+
+
+def _bins_from(P, order_stats, table):
+    """The host side of collator.py:301-308: (num_bins, edges km, thresholds) from five order statistics of the squared chord.
+    order_stats(ranks) -> f64 [len(ranks)]."""
+    from ._lib_bins import MAX_THRESHOLDS
+    n = P * P
+    ranks, frac = [], []
+    for q in (0.75, 0.25):                                             # np.percentile(x, [75, 25]), method "linear"
+        v = q * (n - 1)
+        k = math.floor(v)
+        ranks += [k, min(k + 1, n - 1)]
+        frac.append(v - k)
+    ranks.append(n - 1)                                                # np.max(x); np.min(x) is the diagonal's 0
+    c2 = np.asarray(order_stats(ranks), dtype=np.float64)
+    km = chord2_to_km(c2)
+    lerp = lambda a, b, t: a + (b - a) * t if t < 0.5 else b - (b - a) * (1.0 - t)
+    iqr = lerp(km[0], km[1], frac[0]) - lerp(km[2], km[3], frac[1])
+    if not (np.isfinite(iqr) and iqr > 0.0):
+        raise ValueError(f"distance bins: the interquartile range of the pair distances is {iqr} km, the Freedman-Diaconis bin "
+                         "width needs a positive one")
+    binsize = 2.0 * iqr * np.power(float(P), -1 / 3)                   # len(x) = the rows of the matrix
+    num_bins = int(np.ceil(km[4] / binsize))
+    if table and num_bins + 1 > MAX_THRESHOLDS:
+        raise ValueError(f"distance bins: {num_bins} bins do not fit the int16 table ({MAX_THRESHOLDS} thresholds at most); "
+                         "table=False gives the edges")
+    edges = np.linspace(0.0, km[4], num_bins + 1)                      # np.histogram(x, num_bins)[1]
+    thresholds = 4.0 * np.sin(edges / (2.0 * EARTH_RADIUS_KM)) ** 2
+    thresholds[0] = 0.0                                                # zero-distance pairs: bin 1
+    thresholds[-1] = c2[4]                                             # the farthest pair: bin num_bins + 1, as np.digitize has it
+    if np.any(np.diff(thresholds) < 0.0):
+        raise ValueError("distance bins: the thresholds are not non-decreasing")
+    return num_bins, edges, thresholds
+
+
+def _launch_bins(name, *args):
+    from . import _lib_bins
+    _lib_bins.launch(name, *args)
+
+
+def chord2_digit_counts(unit, prefix, prefix_bits, counts=None):
+    """-> counts int64 [RADIX] on the device (mobgt_bins_chord2_digits): one level of the radix select."""
+    from ._lib_bins import RADIX
+    from .ops import _p, _stream
+    P = unit.shape[0]
+    _check(unit, torch.float64, (P, 3), "unit")
+    counts = torch.empty(RADIX, dtype=torch.int64, device=unit.device) if counts is None else counts
+    _check(counts, torch.int64, (RADIX,), "counts")
+    _launch_bins("mobgt_bins_chord2_digits", _p(unit), P, int(prefix), int(prefix_bits), _p(counts), _stream())
+    return counts
+
+
+def chord2_order_stats(unit, ranks, info=None):
+    """unit f64 [P, 3] on the device -> np f64 [len(ranks)]: the order statistics at the 0-based `ranks` of the multiset of the
+    squared chords of all P^2 ordered pairs (the diagonal and both orders included), bit-exact.  At most 64 / DIGIT_BITS
+    launches and 2 KB read-backs per rank; `info["launches"]` counts them."""
+    from ._lib_bins import DIGIT_BITS, RADIX
+    P = unit.shape[0]
+    counts = torch.empty(RADIX, dtype=torch.int64, device=unit.device)
+    with torch.cuda.device(unit.device):
+        return _select(lambda prefix, bits: chord2_digit_counts(unit, prefix, bits, counts).cpu().numpy(), DIGIT_BITS, P * P, ranks,
+                       info)
+
+
+def bin_table(unit, thresholds, table=None):
+    """-> table int16 [(P+1), (P+1)] on the device (mobgt_bins_table): np.searchsorted(thresholds, c2, side="right") of every
+    pair, row / column 0 = the pad POI.  `thresholds`: f64 on the host; that they never decrease is checked here (the kernel
+    cannot).  `table`: a buffer to write into."""
+    from ._lib_bins import MAX_THRESHOLDS, MIN_THRESHOLDS
+    from .ops import _p, _stream
+    P = unit.shape[0]
+    _check(unit, torch.float64, (P, 3), "unit")
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if thr.ndim != 1 or not MIN_THRESHOLDS <= thr.size <= MAX_THRESHOLDS:
+        raise ValueError(f"thresholds: expected {MIN_THRESHOLDS} .. {MAX_THRESHOLDS} f64, got shape {thr.shape}")
+    if np.isnan(thr).any() or np.any(np.diff(thr) < 0.0):
+        raise ValueError("thresholds: not non-decreasing")
+    table = torch.empty(P + 1, P + 1, dtype=torch.int16, device=unit.device) if table is None else table
+    _check(table, torch.int16, (P + 1, P + 1), "table")
+    with torch.cuda.device(unit.device):
+        _launch_bins("mobgt_bins_table", _p(unit), P, _p(torch.tensor(thr, device=unit.device)), thr.size, _p(table), _stream())
+    return table
+
+
+def _bin_coords(coords_deg, pad_row):
+    c = _coords(coords_deg, pad_row)
+    if c.shape[0] < 2:
+        raise ValueError(f"distance bins: {c.shape[0]} POI, the percentiles of the pair distances need at least 2")
+    return c
+
+
+def distance_bins(coords_deg, device="cuda", pad_row=False, table=True):
+    """coords [P, 2] latitude / longitude in degrees, POI 1..P in row order (or [P + 1, 2] with `pad_row`: row 0 is the pad
+    POI) -> DistanceBins: the reference's num_bins and edges (collator.py:301-308) and, with `table`, the int16 bin table
+    (collator.py:429-437) on `device`.  Nothing of size P^2 exists on the host; table=False allocates nothing of size P^2 at
+    all and has no limit on the bin count (P = 100 000: the edges for DeviceCollator(coords=, bin_edges=))."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("distance_bins runs on the GPU; the host form is distance_bins_host")
+    c = _bin_coords(coords_deg, pad_row)
+    P = c.shape[0]
+    with torch.cuda.device(device):
+        unit = unit_vectors(torch.tensor(c, device=device))
+        num_bins, edges, thr = _bins_from(P, lambda ranks: chord2_order_stats(unit, ranks), table)
+        return DistanceBins(P, num_bins, edges, thr, bin_table(unit, thr) if table else None)
+
+
+# ---- the distance bins: the host form ---------------------------------------------------------------------------------------------
+_HOST_DIGIT_BITS = 16
+
+
+def _chord2_rows_host(u, r0, r1):
+    """c2 of rows r0 .. r1 - 1 against every column: include/mobgt_bins.h's expression, every operation rounded once."""
+    dx, dy, dz = (u[r0:r1, None, k] - u[None, :, k] for k in range(3))
+    return ((dx * dx) + (dy * dy)) + (dz * dz)
+
+
+def chord2_order_stats_host(unit, ranks):
+    """chord2_order_stats in numpy: the same select with 16-bit digits, blocked over rows."""
+    u = np.ascontiguousarray(unit, dtype=np.float64)
+    P = u.shape[0]
+    step = max(1, 4_000_000 // P)
+
+    def digit_counts(prefix, bits):
+        counts = np.zeros(1 << _HOST_DIGIT_BITS, dtype=np.int64)
+        for r0 in range(0, P, step):
+            key = _chord2_rows_host(u, r0, r0 + step).reshape(-1).view(np.uint64)
+            if bits:
+                key = key[(key >> np.uint64(64 - bits)) == np.uint64(prefix)]
+            digit = (key >> np.uint64(64 - bits - _HOST_DIGIT_BITS)) & np.uint64((1 << _HOST_DIGIT_BITS) - 1)
+            counts += np.bincount(digit.astype(np.int64), minlength=counts.size)
+        return counts
+
+    return _select(digit_counts, _HOST_DIGIT_BITS, P * P, ranks)
+
+
+def distance_bins_host(coords_deg, pad_row=False, table=True, unit=None):
+    """The same rule in numpy f64 -> DistanceBins with a CPU tensor as its table.  Blocked over rows: never P x P in f64 at once.
+    `unit`: run on these [P, 3] unit vectors instead of unit_vectors_host(coords)."""
+    c = _bin_coords(coords_deg, pad_row)
+    P = c.shape[0]
+    u = unit_vectors_host(c) if unit is None else np.ascontiguousarray(unit, dtype=np.float64)
+    if u.shape != (P, 3):
+        raise ValueError(f"unit: expected shape {(P, 3)}, got {u.shape}")
+    num_bins, edges, thr = _bins_from(P, lambda ranks: chord2_order_stats_host(u, ranks), table)
+    out = None
+    if table:
+        out = np.empty((P + 1, P + 1), dtype=np.int16)
+        out[0, :] = out[:, 0] = np.searchsorted(thr, 0.0, side="right")
+        step = max(1, 4_000_000 // P)
+        for r0 in range(0, P, step):
+            out[1 + r0:1 + r0 + step, 1:] = np.searchsorted(thr, _chord2_rows_host(u, r0, r0 + step), side="right")
+        out = torch.from_numpy(out)
+    return DistanceBins(P, num_bins, edges, thr, out)
