@@ -21,6 +21,7 @@ extern "C" {
 #define MOBGT_CPU_ERECURSION 3   /* the path matrix does not terminate (the reference: RecursionError) */
 #define MOBGT_CPU_ENOMEM 4
 
+#define MOBGT_CPU_ABI_VERSION 1
 int mobgt_cpu_abi_version(void);
 
 /* graphormer/algos.pyx:9-54  floyd_warshall(adjacency_matrix) -> (M, path).

@@ -62,7 +62,7 @@ bool walk_path(const int64_t* path, int n, int a, int b, std::vector<int32_t>& s
 }
 }  // namespace
 
-extern "C" int mobgt_cpu_abi_version(void) { return 1; }
+extern "C" int mobgt_cpu_abi_version(void) { return MOBGT_CPU_ABI_VERSION; }
 
 extern "C" int mobgt_floyd_warshall_cpu(const int64_t* adj, int n, int64_t* M, int64_t* path) {
     if (n < 0) return MOBGT_CPU_EBADDIM;

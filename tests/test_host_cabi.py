@@ -10,7 +10,7 @@ import sys
 
 import pytest
 
-from mobgt_amd import _cabi, _lib, _lib_cpu, ops
+from mobgt_amd import _cabi, _lib, _lib_cpu, _native, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "mobgt_amd")
@@ -70,12 +70,12 @@ def test_every_export_is_declared():
         shutil.which("llvm-nm", path=os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"))
     if nm is None:
         pytest.skip("neither nm nor llvm-nm is installed")
-    for mod in (_lib, _lib_cpu):
-        mod.build()
-        out = subprocess.check_output([nm, "-D", "--defined-only", mod.LIB_PATH], text=True)
+    assert len(_native.LIBRARIES) == 5
+    for library in _native.LIBRARIES:
+        out = subprocess.check_output([nm, "-D", "--defined-only", library.build()], text=True)
         exported = set(re.findall(r"\s[A-Za-z]\s+(mobgt_\w+)$", out, re.M))
         assert exported, out[:200]
-        assert exported == set(mod.SIGNATURES), sorted(exported ^ set(mod.SIGNATURES))
+        assert exported == set(library.SIGNATURES), sorted(exported ^ set(library.SIGNATURES))
 
 
 def _sources():
@@ -97,7 +97,15 @@ def test_no_call_site_is_left_on_check_of_lib():
     assert not found, found
 
 
+def test_only_native_defines_build_and_lib():
+    """A loader module declares a `_native.Library`; none carries a copy of its build() or lib()."""
+    defs = {f: re.findall(r"^\s*def (build|lib)\b", text, re.M) for f, text in _sources() if f.startswith(("_lib", "_native"))}
+    assert sorted(defs) == ["_lib.py", "_lib_bins.py", "_lib_cpu.py", "_lib_data.py", "_lib_geo.py", "_native.py"]
+    assert sorted(defs.pop("_native.py")) == ["build", "lib"] and not any(defs.values()), defs
+
+
 def test_binding_imports_without_torch_and_without_the_libraries():
     code = ("import sys; import mobgt_amd._lib as a, mobgt_amd._lib_cpu as b; assert 'torch' not in sys.modules; "
-            "assert len(a.SIGNATURES) > 100 and b.SIGNATURES and not __import__('os').path.exists(a.LIB_PATH)")
+            "import mobgt_amd._lib_data as c, mobgt_amd._lib_geo as d, mobgt_amd._lib_bins as e; assert 'torch' not in sys.modules; "
+            "assert len(a.SIGNATURES) > 100 and all(m.SIGNATURES for m in (b, c, d, e)) and not __import__('os').path.exists(a.LIB_PATH)")
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, MOBGT_HIP_LIB=os.path.join(ROOT, "no_such.so")))

@@ -17,7 +17,7 @@ P = float(os.environ.get("P", 0.1))
 res = {n: [] for n in names}
 for rnd in range(int(os.environ.get("ROUNDS", 3))):
     for n in names:
-        _lib._lib = handles[n]
+        _lib.LIBRARY.handle = handles[n]
         f, b, _ = bench.time_attention(16, 8, 785, 32, torch.bfloat16, torch.bfloat16, reps=24, p_drop=P, backward=True)
         res[n].append((f * 1e6, b * 1e6))
 for n in names:
