@@ -16,13 +16,14 @@
 // `stride`-th threshold in LDS (at most COARSE of them: all of them up to 2048 thresholds); a pair searches those, then the
 // stride - 1 thresholds between two of them in global memory (they stay in L2: 256 KB at most).  A lane owns four int16 that
 // share an aligned 8-byte word of the table and stores them at once if the row holds all four, one by one at the row's head
-// and tail.
+// and tail.  chord2, the search and the store are bins_search.h's, shared with csrc_pairbins/batch.hip.
 //
 // Built with -ffp-contract=off (Makefile): c2 is the header's bit-exact expression.  No workgroup reads what another writes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "mobgt_bins.h"
+#include "bins_search.h"
 
 namespace {
 
@@ -34,17 +35,9 @@ constexpr int TILE = MOBGT_BINS_TILE;              // columns per LDS tile
 constexpr int RADIX = MOBGT_BINS_RADIX;
 constexpr int PEEL = 4;                            // digits a wave adds with one lane each before the per-lane atomics
 constexpr int TROWS = 8;                           // table rows per workgroup (table_kernel)
-constexpr int COARSE = 2048;                       // thresholds in LDS (table_kernel)
-constexpr int VEC = 4;                             // int16 per lane and store (table_kernel)
 static_assert(RADIX == 1 << MOBGT_BINS_DIGIT_BITS && 64 % MOBGT_BINS_DIGIT_BITS == 0, "whole digits");
 static_assert(TILE % 64 == 0 && RADIX == TPB, "a step is one wave wide; the flush takes one bucket per thread");
 static_assert((uint64_t)ROWS * MOBGT_BINS_MAX_P < (1ull << 32), "a workgroup's pairs fit a 32-bit count");
-
-// The header's c2: every operation rounded once (contraction is off for this file).
-__device__ __forceinline__ double chord2(double xi, double yi, double zi, double xj, double yj, double zj) {
-    const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
 
 __global__ __launch_bounds__(TPB) void digits_kernel(const double* __restrict__ unit, int64_t P, uint64_t prefix, int prefix_bits,
                                                      unsigned long long* __restrict__ counts) {
@@ -113,22 +106,7 @@ __global__ __launch_bounds__(TPB) void table_kernel(const double* __restrict__ u
     for (int q = t; q < ncoarse; q += TPB) s_c[q] = thr[(int64_t)q * stride];
     __syncthreads();
 
-    // #{k : thr[k] <= c2}
-    auto count = [&](double c2) -> int {
-        int lo = 0, hi = ncoarse;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (s_c[mid] <= c2) lo = mid + 1; else hi = mid;
-        }
-        if (stride == 1 || lo == 0) return lo;
-        // thr[(lo - 1) * stride] <= c2, and c2 < thr[lo * stride] if there is one
-        int a = (lo - 1) * stride + 1, b = lo * stride < nthr ? lo * stride : nthr;
-        while (a < b) {
-            const int mid = (a + b) >> 1;
-            if (thr[mid] <= c2) a = mid + 1; else b = mid;
-        }
-        return a;
-    };
+    auto count = [&](double c2) -> int { return count_thresholds(s_c, ncoarse, thr, nthr, stride, c2); };
     const int16_t pad = (int16_t)count(0.0);
 
     const int64_t ld = P + 1;
@@ -148,17 +126,7 @@ __global__ __launch_bounds__(TPB) void table_kernel(const double* __restrict__ u
                 if (a > 0 && col >= 1 && col <= P)
                     v[k] = (int16_t)count(chord2(xa, ya, za, unit[3 * (col - 1)], unit[3 * (col - 1) + 1], unit[3 * (col - 1) + 2]));
             }
-            int16_t* dst = table + (g * VEC - skew);                    // 8-byte aligned
-            if (g * VEC >= f0 && g * VEC + VEC - 1 <= f1) {
-                uint2 w;
-                w.x = (uint32_t)(uint16_t)v[0] | ((uint32_t)(uint16_t)v[1] << 16);
-                w.y = (uint32_t)(uint16_t)v[2] | ((uint32_t)(uint16_t)v[3] << 16);
-                *reinterpret_cast<uint2*>(dst) = w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k)
-                    if (g * VEC + k >= f0 && g * VEC + k <= f1) dst[k] = v[k];
-            }
+            store_vec(table + (g * VEC - skew), v, g * VEC, f0, f1);                 // (the word's address: 8-byte aligned)
         }
     }
 }

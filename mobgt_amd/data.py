@@ -77,10 +77,15 @@ class DeviceCollator:
     applied to `preprocess_item`-ed items."""
 
     def __init__(self, device, bin_table=None, multi_hop_max_dist=20, rel_pos_max=1024, max_node=30000, coords=None,
-                 bin_edges=None):
+                 bin_edges=None, pair_bins=None):
         """`bin_table`: (P+1) x (P+1) precomputed distance-bin ids (make_bin_table).  For universes where that table
         cannot exist (P = 100 000), `coords` [(P+1), 2] lat / lon + `bin_edges`: poi_pos = digitize(haversine) is then
-        evaluated for the batch's pairs on the device."""
+        evaluated for the batch's pairs on the device with torch ops.  `pair_bins` (geo.pair_bins), instead of either: poi_pos
+        is the search of the pairs' squared chords among the edges as squared chords, one launch (mobgt_bins_batch) beside
+        mobgt_collate_finish, so the collate can run on a loop's copy stream (can_finish_into); `coords` given with it only
+        serves as the default coordinates of recommend / evaluate(within_km=)."""
+        if pair_bins is not None and (bin_table is not None or bin_edges is not None):
+            raise ValueError("DeviceCollator: pair_bins= replaces bin_table= and bin_edges=, give one of them")
         self.device = torch.device(device)
         self.D = int(multi_hop_max_dist)
         self.rel_pos_max = int(rel_pos_max)
@@ -91,7 +96,9 @@ class DeviceCollator:
         self.coords = self.bin_edges = None
         if coords is not None:
             self.coords = torch.as_tensor(np.radians(np.asarray(coords, dtype=np.float64))).to(self.device)
-            self.bin_edges = torch.as_tensor(np.asarray(bin_edges, dtype=np.float64)).to(self.device)
+            if pair_bins is None:
+                self.bin_edges = torch.as_tensor(np.asarray(bin_edges, dtype=np.float64)).to(self.device)
+        self.pair_bins = pair_bins.to(self.device) if pair_bins is not None else None
 
     def pack_host(self, trajs, idx0=0, n_pad=None, out=None):
         """Raw dicts -> padded numpy arrays (pinned-memory friendly); no graph algorithm runs on the host.
@@ -192,12 +199,15 @@ class DeviceCollator:
         st["dev"][:st["pin"].numel()].copy_(st["pin"], non_blocking=True)
 
     def can_finish_into(self):
+        if self.pair_bins is not None:
+            return True
         return self.coords is None and (self.bin_table is None or (self.bin_table.dtype == torch.int16 and self.bin_table.is_contiguous()))
 
     def finish_into(self, v, work=None):
         """`finish` writing into the pre-allocated views of a BatchLayout buffer (raw fields already in place): two / three
-        launches on the CURRENT stream, no allocation -- train.EpochLoop runs it on its copy stream for the next batch."""
-        from . import _lib
+        launches on the CURRENT stream (one more with pair_bins), no allocation -- train.EpochLoop runs it on its copy stream for
+        the next batch."""
+        from . import _lib, geo
         from .ops import _p, _stream
         G, N = v["counts"].shape[:2]
         lib = _lib.lib()
@@ -209,6 +219,8 @@ class DeviceCollator:
         bt = self.bin_table
         _lib.call("mobgt_collate_finish", _p(v["x"]), _p(v["n_nodes"]), _p(v["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
                   self.rel_pos_max, _p(v["attn_bias"]), _p(v["poi_pos"]), G, N, _stream())
+        if self.pair_bins is not None:
+            geo.batch_bins(self.pair_bins, v["x"], out=v["poi_pos"])
         return work
 
     @staticmethod
@@ -224,7 +236,8 @@ class DeviceCollator:
         T = N + 1
         sp = ops.spd_batched(counts, n_nodes, self.D)
         x = d["x"]
-        if (self.coords is None and x.dtype == torch.int32 and n_nodes.dtype == torch.int32 and x.is_contiguous()
+        if ((self.coords is None or self.pair_bins is not None) and x.dtype == torch.int32 and n_nodes.dtype == torch.int32
+                and x.is_contiguous()
                 and (self.bin_table is None or (self.bin_table.dtype == torch.int16 and self.bin_table.is_contiguous()))):
             # padding mask, rel_pos_max cut and the distance-bin gather in one launch (mobgt_collate_finish)
             from . import _lib
@@ -234,6 +247,9 @@ class DeviceCollator:
             bt = self.bin_table
             _lib.call("mobgt_collate_finish", _p(x), _p(n_nodes), _p(sp["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
                       self.rel_pos_max, _p(attn_bias), _p(poi_pos), G, N, _stream())
+            if self.pair_bins is not None:
+                from . import geo
+                geo.batch_bins(self.pair_bins, x, out=poi_pos)
             return DeviceBatch1(counts, n_nodes, idx=d["idx"], attn_bias=attn_bias, rel_pos=sp["rel_pos"],
                                 in_degree=sp["in_degree"], out_degree=sp["out_degree"], x=x, edge_input=sp["edge_input"],
                                 y=d["y"], time=d["time"], time_normal=d["time_normal"], user=d["user"], cat=d["cat"],
@@ -245,7 +261,10 @@ class DeviceCollator:
         if self.rel_pos_max <= 510:                                                  # collator.py:354-358
             far = sp["spd"] >= self.rel_pos_max
             attn_bias[:, 1:, 1:].masked_fill_(far, float("-inf"))
-        if self.bin_table is not None:
+        if self.pair_bins is not None:                                               # (ids of another dtype: the same launch)
+            from . import geo
+            poi_pos = geo.batch_bins(self.pair_bins, x[:, :, 0].to(torch.int32).contiguous())
+        elif self.bin_table is not None:
             xi = x[:, :, 0].long()
             poi_pos = self.bin_table[xi.unsqueeze(2), xi.unsqueeze(1)]
             real = xi != 0

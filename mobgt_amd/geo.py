@@ -14,7 +14,12 @@ Freedman-Diaconis bin count from two percentiles and the maximum of a (P+1) x (P
 digitizes the matrix against np.histogram's edges (collator.py:429-437).  `distance_bins` derives the same bin count, the same
 edges and the int16 bin table DeviceCollator(bin_table=) reads from the unit vectors on the device (csrc_bins/bins.hip through
 _lib_bins): order statistics of the squared chord by a radix select that stores nothing of size P^2, then a search of every
-pair's squared chord among the edges mapped to squared chords.  `distance_bins_host` is the same rule in numpy."""
+pair's squared chord among the edges mapped to squared chords.  `distance_bins_host` is the same rule in numpy.
+
+Where no table of all pairs can exist (P = 100 000), `pair_bins` keeps the unit vectors and the thresholds on the device and
+`batch_bins` runs the same search for the pairs of one batch only (csrc_pairbins/batch.hip through _pairbins): what
+DeviceCollator(pair_bins=) launches.
+`batch_bins_host` is that rule in numpy."""
 import dataclasses
 import math
 
@@ -374,15 +379,10 @@ def bin_table(unit, thresholds, table=None):
     """-> table int16 [(P+1), (P+1)] on the device (mobgt_bins_table): np.searchsorted(thresholds, c2, side="right") of every
     pair, row / column 0 = the pad POI.  `thresholds`: f64 on the host; that they never decrease is checked here (the kernel
     cannot).  `table`: a buffer to write into."""
-    from ._lib_bins import MAX_THRESHOLDS, MIN_THRESHOLDS
     from .ops import _p, _stream
     P = unit.shape[0]
     _check(unit, torch.float64, (P, 3), "unit")
-    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
-    if thr.ndim != 1 or not MIN_THRESHOLDS <= thr.size <= MAX_THRESHOLDS:
-        raise ValueError(f"thresholds: expected {MIN_THRESHOLDS} .. {MAX_THRESHOLDS} f64, got shape {thr.shape}")
-    if np.isnan(thr).any() or np.any(np.diff(thr) < 0.0):
-        raise ValueError("thresholds: not non-decreasing")
+    thr = _checked_thresholds(thresholds)
     table = torch.empty(P + 1, P + 1, dtype=torch.int16, device=unit.device) if table is None else table
     _check(table, torch.int16, (P + 1, P + 1), "table")
     with torch.cuda.device(unit.device):
@@ -411,6 +411,106 @@ def distance_bins(coords_deg, device="cuda", pad_row=False, table=True):
         unit = unit_vectors(torch.tensor(c, device=device))
         num_bins, edges, thr = _bins_from(P, lambda ranks: chord2_order_stats(unit, ranks), table)
         return DistanceBins(P, num_bins, edges, thr, bin_table(unit, thr) if table else None)
+
+
+# ---- the distance bins of one batch's pairs ---------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PairBins:
+    """What the search of one batch's pairs reads (DeviceCollator(pair_bins=)): the POIs' unit vectors and the bin edges as
+    squared chords, on one device.
+
+    unit        f64 [P, 3] tensor: row i is POI i + 1
+    thresholds  f64 [num_bins + 1] tensor, non-decreasing: poi_pos = #{k : thresholds[k] <= c2}
+    num_bins    the bin count: poi_pos of a real pair lies in 0 .. num_bins + 1"""
+    P: int
+    unit: torch.Tensor
+    thresholds: torch.Tensor
+    num_bins: int
+
+    @property
+    def device(self):
+        return self.unit.device
+
+    def to(self, device):
+        return PairBins(self.P, self.unit.to(device), self.thresholds.to(device), self.num_bins)
+
+
+def _checked_thresholds(thresholds):
+    """-> contiguous f64 array; the count and that they never decrease are checked here, on the host (the kernels cannot)."""
+    from ._lib_bins import MAX_THRESHOLDS, MIN_THRESHOLDS
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if thr.ndim != 1 or not MIN_THRESHOLDS <= thr.size <= MAX_THRESHOLDS:
+        raise ValueError(f"thresholds: expected {MIN_THRESHOLDS} .. {MAX_THRESHOLDS} f64, got shape {thr.shape}")
+    if np.isnan(thr).any() or np.any(np.diff(thr) < 0.0):
+        raise ValueError("thresholds: not non-decreasing")
+    return thr
+
+
+def pair_bins(coords_deg, bins=None, edges=None, device="cuda", pad_row=False):
+    """coords [P, 2] latitude / longitude in degrees, POI 1..P in row order (or [P + 1, 2] with `pad_row`) -> PairBins on `device`.
+    Exactly one of: `bins`, a DistanceBins of the same POIs, whose thresholds are taken as they are (the last is the farthest
+    pair's own squared chord); `edges`, plain bin edges in km (SparseUniverse.bin_edges), mapped through 4 sin^2(e / 2R) with the
+    first forced to 0.  On a GPU the unit vectors are mobgt_geo_unit_vectors' (the ones distance_bins took its thresholds from);
+    on the CPU unit_vectors_host's, for batch_bins_host."""
+    if (bins is None) == (edges is None):
+        raise ValueError("pair_bins: give exactly one of bins= (a DistanceBins) and edges= (bin edges in km)")
+    c = _coords(coords_deg, pad_row)
+    P = c.shape[0]
+    if bins is not None:
+        if bins.P != P:
+            raise ValueError(f"pair_bins: bins were built for {bins.P} POIs, coords hold {P}")
+        thr = np.asarray(bins.thresholds, dtype=np.float64)
+    else:
+        e = np.asarray(edges, dtype=np.float64)
+        thr = 4.0 * np.sin(e / (2.0 * EARTH_RADIUS_KM)) ** 2
+        if thr.ndim == 1 and thr.size:
+            thr[0] = 0.0                                               # zero-distance pairs: bin 1
+    thr = _checked_thresholds(thr)
+    device = torch.device(device)
+    if device.type == "cuda":
+        with torch.cuda.device(device):
+            unit = unit_vectors(torch.tensor(c, device=device))
+    else:
+        unit = torch.from_numpy(unit_vectors_host(c))
+    return PairBins(P, unit, torch.tensor(thr, device=device), thr.size - 1)
+
+
+def batch_bins(pair_bins, x, out=None):
+    """-> poi_pos int16 [G, N, N] on the device (mobgt_bins_batch): #{k : thresholds[k] <= c2} for every pair of POIs of each row
+    of `x` (int32 [G, N] or [G, N, 1] POI ids, 0 = pad), 0 for a pair with a pad or an id outside 1 .. P.  One launch on the
+    current stream, no allocation when `out` is given (any int16-aligned view, such as BatchLayout's)."""
+    from .ops import _p, _stream
+    if x.dim() == 3 and x.shape[2] == 1:
+        x = x[:, :, 0]
+    if x.dim() != 2:
+        raise ValueError(f"x: expected POI ids of shape [G, N] or [G, N, 1], got {tuple(x.shape)}")
+    G, N = x.shape
+    if pair_bins.unit.device.type != "cuda":
+        raise ValueError("batch_bins runs on the GPU; the host form is batch_bins_host")
+    _check(x, torch.int32, (G, N), "x")
+    out = torch.empty(G, N, N, dtype=torch.int16, device=x.device) if out is None else out
+    _check(out, torch.int16, (G, N, N), "out")
+    from . import _pairbins
+    _pairbins.launch("mobgt_bins_batch", _p(pair_bins.unit), pair_bins.P, _p(pair_bins.thresholds), pair_bins.thresholds.numel(), _p(x), G, N,
+                 _p(out), _stream())
+    return out
+
+
+def batch_bins_host(unit, thresholds, x):
+    """batch_bins in numpy -> int16 [G, N, N]: np.searchsorted(thresholds, c2, side="right") on _chord2_rows_host's expression
+    for the pairs whose ids both lie in 1 .. P, 0 elsewhere.  The kernel's reference and the CPU form."""
+    u = np.ascontiguousarray(unit, dtype=np.float64)
+    thr = _checked_thresholds(thresholds)
+    ids = np.asarray(x)
+    ids = ids[:, :, 0] if ids.ndim == 3 else ids
+    G, N = ids.shape
+    ok = (ids >= 1) & (ids <= u.shape[0])
+    out = np.zeros((G, N, N), dtype=np.int16)
+    for g in range(G):
+        ug = u[np.where(ok[g], ids[g].astype(np.int64) - 1, 0)]
+        pos = np.searchsorted(thr, _chord2_rows_host(ug, 0, N), side="right")
+        out[g] = np.where(ok[g][:, None] & ok[g][None, :], pos, 0)
+    return out
 
 
 # ---- the distance bins: the host form ---------------------------------------------------------------------------------------------

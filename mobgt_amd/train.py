@@ -1103,7 +1103,8 @@ class _StagedBatches:
         if s is None:
             # `side`: the device collate of the NEXT batch runs on the copy stream, beside the current step (whose kernels
             # leave most of the chip idle); the step graph then reads a collated static batch.  Collators that need torch
-            # ops (coordinate bins, S-BIG) keep the collate inside the step graph (batch_fn = finish).
+            # ops (coords= + bin_edges=, S-BIG's default) keep the collate inside the step graph (batch_fn = finish); a
+            # collator built with pair_bins= collates coordinate-bin universes here like any other.
             side = self.side_collate and self.collator.can_finish_into()
             lay = BatchLayout(G, N, self.collator.D) if side else RawLayout(G, N)
             buf = torch.zeros(lay.nbytes, dtype=torch.uint8, device=self.device)
@@ -1172,7 +1173,8 @@ class EpochLoop(_StagedBatches):
       its host-to-device copy and its device collate (`DeviceCollator.finish_into`: SPD / edge paths / degrees / distance
       bins) while the GPU runs the current step; then -- on the compute stream -- one device-to-device copy of the staged
       raw + derived bytes into the bucket's static batch and one graph replay.  Collators whose finish needs torch ops
-      (coordinate bins) keep the collate inside the step graph (`batch_fn = finish`).
+      (coordinate bins by coords= + bin_edges=; pair_bins= needs none) keep the collate inside the step graph
+      (`batch_fn = finish`).
     """
 
     def __init__(self, model, collator, dataset, batch_size=16, seed=1, use_graph=True, overlap=True, buckets=None, rank=None,
@@ -1330,7 +1332,8 @@ class EvalLoop(_StagedBatches):
       stream, host index checks; trajectories over `collator.max_node` are dropped;
     * per (G, bucket, forms.on("safe_forms")) ONE captured graph = eval forward + the fused classifier-ranking launches
       (Graphormer.metric_step) adding into ONE f64 accumulator; `use_graph=False` runs the same launches eagerly, and so do
-      collators whose finish needs torch ops (coordinate bins, S-BIG: see _launch);
+      collators whose finish needs torch ops (coordinate bins by coords= + bin_edges=, S-BIG's default: see _launch; a
+      collator built with pair_bins= is captured like a bin-table one);
     * `run()` reads the accumulator once (after one all-reduce of all its doubles when world > 1: every rank's samples pooled).
     The weights are read as they are when `run()` starts (bf16 shadows and MFMA packs re-derived there, outside any graph), so an
     evaluation between training epochs sees the current model; it leaves no state behind that the trainer's next step reads.
@@ -1427,7 +1430,7 @@ class EvalLoop(_StagedBatches):
             st["free"] = torch.cuda.Event()
         st["free"].record(cur)
         if not self.use_graph or not slot["side"]:
-            # Buckets whose collate needs torch ops (coordinate bins: S-BIG) run eagerly.  Captured with the collate inside, the
+            # Buckets whose collate needs torch ops (coords= + bin_edges=: S-BIG's default collator) run eagerly.  Captured with the collate inside, the
             # replay took 130 ms per 16 x 784 batch against 13 ms eager: inside the replayed graph the SPD kernel's split form
             # (workgroups that wait for each other, csrc/spd.hip) gave up on every call and its one-workgroup-per-graph redo
             # pass ran (fw_kernel: 75 ms per call, rocprofv3).  Why it gives up only there is not known.
@@ -1519,7 +1522,7 @@ class EvalLoop(_StagedBatches):
 class PredictLoop(EvalLoop):
     """Top-k next-POI recommendations over a whole split (Graphormer.recommend_step) on EvalLoop's device data path: the eval
     loader's order and sharding, EpochLoop's buckets and staging, one captured graph per (G, bucket, forms.on("safe_forms")) -- eager
-    for collators whose finish needs torch ops (S-BIG) -- and the weights as they are when run() starts.
+    for collators whose finish needs torch ops (coords= + bin_edges=, S-BIG's default) -- and the weights as they are when run() starts.
 
     A graph writes its batch's [G, k] ids / vals into buffers of its own (fixed pointers); a device-to-device copy on the same
     stream, outside the graph, then moves them to the batch's rows of the result.  Trajectories over collator.max_node, which
