@@ -718,3 +718,8 @@ class SessionCollator(DeviceCollator):
 def _slot_of(t):
     """The time-slot index the model looks up for a raw slot value t: int(float32(t / 48) * 48), 0 for t = 0."""
     return int(float(np.float32(t / 48)) * 48) if t != 0 else 0
+
+
+# ---- the POI table and the transition graphs from sessions (universe.py) ------------------------------------------------------------
+from .universe import (BuiltUniverse, TransitionGraph, UniverseCounts, build_universe, first_seen_ids, universe_counts,  # noqa: E402,F401
+                       universe_counts_host)
