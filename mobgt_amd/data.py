@@ -7,7 +7,8 @@ This is the default data path of the trainer / bench.  It r
 SPD / path / first-D-hop edge features / degrees, and a gather from a precomputed distance-bin table for
 `poi_pos`.  Index tensors stay narrow on the device (int16 / uint8 instead of the reference's int64):
 the kernels are templated on the index type, and `.long()` views give the reference dtypes when needed.
-Every field equals what the reference pipeline produces for the same trajectories (tests/test_gpu_data.py).
+Every field equals what the reference pipeline produces for the same trajectories
+(tests/test_gpu_model.py::test_device_collator_matches_reference_batch, tests/test_gpu_pair_bins.py).
 """
 import collections
 
@@ -99,6 +100,9 @@ class DeviceCollator:
             if pair_bins is None:
                 self.bin_edges = torch.as_tensor(np.asarray(bin_edges, dtype=np.float64)).to(self.device)
         self.pair_bins = pair_bins.to(self.device) if pair_bins is not None else None
+        # where poi_pos comes from, decided once: the chord search, the table, haversine + bucketize, or nowhere (all zeros)
+        self.poi_source = ("pair_bins" if pair_bins is not None else "table" if bin_table is not None
+                           else "haversine" if coords is not None else None)
 
     def pack_host(self, trajs, idx0=0, n_pad=None, out=None):
         """Raw dicts -> padded numpy arrays (pinned-memory friendly); no graph algorithm runs on the host.
@@ -179,13 +183,10 @@ class DeviceCollator:
     def limit_violation(self, h, L):
         """The first field of stage_host's arrays that holds an index outside the model's tables (L = model.index_limits()):
         (field, index, table rows), or None.  Checked on the host, before anything is launched."""
+        bad = self._id_violation(h["x"], h, L)
+        if bad:
+            return bad
         nz = h["counts"] != 0
-        if "x" in L and int(h["x"].max()) > L["x"]:
-            return "x", int(h["x"].max()), L["x"] + 1
-        if "user" in L and int(h["user"].max()) > L["user"]:
-            return "user", int(h["user"].max()), L["user"] + 1
-        if "y" in L and int(h["y"].max()) > L["y"]:
-            return "y", int(h["y"].max()), L["y"] + 1
         if "edge" in L and int(h["counts"].max()) + 3 >= L["edge"]:
             return "edge_input", int(h["counts"].max()) + 3, L["edge"]
         if "deg" in L and max(int(nz.sum(1).max()), int(nz.sum(2).max())) + 1 >= L["deg"]:
@@ -194,14 +195,25 @@ class DeviceCollator:
             return "time_normal", float(h["time_normal"].max()), L["slots"]
         return None
 
+    @staticmethod
+    def _id_violation(x, h, L):
+        """limit_violation's first three checks -- POI ids `x` (the dict form's h["x"], the session form's check-in column),
+        h["user"], h["y"] -- in that order."""
+        for field, ids in (("x", x), ("user", h["user"]), ("y", h["y"])):
+            if field in L and int(ids.max()) > L[field]:
+                return field, int(ids.max()), L[field] + 1
+        return None
+
     def upload(self, st):
         """Device half, on the CURRENT stream (the loop's copy stream): the staged host bytes -> the raw fields of st["dev"]."""
         st["dev"][:st["pin"].numel()].copy_(st["pin"], non_blocking=True)
 
     def can_finish_into(self):
-        if self.pair_bins is not None:
-            return True
-        return self.coords is None and (self.bin_table is None or (self.bin_table.dtype == torch.int16 and self.bin_table.is_contiguous()))
+        """Whether finish_into's launches give this collator's poi_pos: the chord search, mobgt_collate_finish's gather from a
+        contiguous int16 table, or its zeros.  Haversine bins, and any other table, need finish's torch form."""
+        if self.poi_source == "table":                                # (a table beside coords= keeps the torch form)
+            return self.coords is None and self.bin_table.dtype == torch.int16 and self.bin_table.is_contiguous()
+        return self.poi_source != "haversine"
 
     def finish_into(self, v, work=None):
         """`finish` writing into the pre-allocated views of a BatchLayout buffer (raw fields already in place): two / three
@@ -219,41 +231,34 @@ class DeviceCollator:
         bt = self.bin_table
         _lib.call("mobgt_collate_finish", _p(v["x"]), _p(v["n_nodes"]), _p(v["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
                   self.rel_pos_max, _p(v["attn_bias"]), _p(v["poi_pos"]), G, N, _stream())
-        if self.pair_bins is not None:
+        if self.poi_source == "pair_bins":
             geo.batch_bins(self.pair_bins, v["x"], out=v["poi_pos"])
         return work
 
     @staticmethod
     def batch_from_views(v):
-        return DeviceBatch1(v["counts"], v["n_nodes"], idx=v["idx"], attn_bias=v["attn_bias"], rel_pos=v["rel_pos"],
-                            in_degree=v["in_degree"], out_degree=v["out_degree"], x=v["x"], edge_input=v["edge_input"],
-                            y=v["y"], time=v["time"], time_normal=v["time_normal"], user=v["user"], cat=v["cat"],
-                            poi_pos=v["poi_pos"])
+        return DeviceBatch1(v["counts"], v["n_nodes"], **{f: v[f] for f in DeviceBatch1._fields})
 
     def finish(self, d):
-        counts, n_nodes = d["counts"], d["n_nodes"]
-        G, N = counts.shape[:2]
+        """Raw device arrays (pack_host's names) -> DeviceBatch1.  finish_into's launches into freshly allocated tensors when they
+        give this collator's poi_pos and the arrays are what the kernels read; the torch-op form otherwise."""
+        ops._require_cuda(d["counts"], d["n_nodes"])
+        if not (self.can_finish_into() and all(d[k].dtype == torch.int32 and d[k].is_contiguous() for k in ("counts", "x", "n_nodes"))):
+            return self._finish_torch(d)
+        G, N = d["counts"].shape[:2]
+        v = dict(d)
+        for name, dt, shape in BatchLayout.DERIVED + BatchLayout.SCRATCH:
+            v[name] = torch.empty(shape(G, N, self.D), dtype=TORCH_DTYPE[dt], device=self.device)
+        self.finish_into(v)
+        return self.batch_from_views(v)
+
+    def _finish_torch(self, d):
+        """finish in torch ops behind mobgt_spd_batched: for haversine bins, a table that is not contiguous int16, ids of
+        another dtype."""
+        n_nodes, x = d["n_nodes"], d["x"]
+        G, N = d["counts"].shape[:2]
         T = N + 1
-        sp = ops.spd_batched(counts, n_nodes, self.D)
-        x = d["x"]
-        if ((self.coords is None or self.pair_bins is not None) and x.dtype == torch.int32 and n_nodes.dtype == torch.int32
-                and x.is_contiguous()
-                and (self.bin_table is None or (self.bin_table.dtype == torch.int16 and self.bin_table.is_contiguous()))):
-            # padding mask, rel_pos_max cut and the distance-bin gather in one launch (mobgt_collate_finish)
-            from . import _lib
-            from .ops import _p, _stream
-            attn_bias = torch.empty(G, T, T, device=self.device)
-            poi_pos = torch.empty(G, N, N, dtype=torch.int16, device=self.device)
-            bt = self.bin_table
-            _lib.call("mobgt_collate_finish", _p(x), _p(n_nodes), _p(sp["spd"]), _p(bt), bt.shape[1] if bt is not None else 0,
-                      self.rel_pos_max, _p(attn_bias), _p(poi_pos), G, N, _stream())
-            if self.pair_bins is not None:
-                from . import geo
-                geo.batch_bins(self.pair_bins, x, out=poi_pos)
-            return DeviceBatch1(counts, n_nodes, idx=d["idx"], attn_bias=attn_bias, rel_pos=sp["rel_pos"],
-                                in_degree=sp["in_degree"], out_degree=sp["out_degree"], x=x, edge_input=sp["edge_input"],
-                                y=d["y"], time=d["time"], time_normal=d["time_normal"], user=d["user"], cat=d["cat"],
-                                poi_pos=poi_pos)
+        sp = ops.spd_batched(d["counts"], n_nodes, self.D)
         ar = torch.arange(T, device=self.device)
         real_tok = ar.view(1, T) <= n_nodes.view(G, 1)                # token 0 + n real nodes
         attn_bias = torch.zeros(G, T, T, device=self.device)
@@ -261,29 +266,24 @@ class DeviceCollator:
         if self.rel_pos_max <= 510:                                                  # collator.py:354-358
             far = sp["spd"] >= self.rel_pos_max
             attn_bias[:, 1:, 1:].masked_fill_(far, float("-inf"))
-        if self.pair_bins is not None:                                               # (ids of another dtype: the same launch)
+        if self.poi_source == "pair_bins":                                           # (the same launch: it zeroes the pad pairs)
             from . import geo
             poi_pos = geo.batch_bins(self.pair_bins, x[:, :, 0].to(torch.int32).contiguous())
-        elif self.bin_table is not None:
-            xi = x[:, :, 0].long()
-            poi_pos = self.bin_table[xi.unsqueeze(2), xi.unsqueeze(1)]
-            real = xi != 0
-            poi_pos = torch.where(real.unsqueeze(2) & real.unsqueeze(1), poi_pos, torch.zeros_like(poi_pos))
-        elif self.coords is not None:
-            xi = x[:, :, 0].long()
-            ll = self.coords[xi]                                                     # [G,N,2] radians, float64
-            lat1, lon1, lat2, lon2 = ll[:, :, None, 0], ll[:, :, None, 1], ll[:, None, :, 0], ll[:, None, :, 1]
-            h = torch.sin((lat2 - lat1) / 2) ** 2 + torch.cos(lat1) * torch.cos(lat2) * torch.sin((lon2 - lon1) / 2) ** 2
-            dist = 2 * 6371.0 * torch.asin(torch.sqrt(h.clamp(0.0, 1.0)))          # synth.haversine_km
-            poi_pos = torch.bucketize(dist, self.bin_edges, right=True).to(torch.int16)   # == np.digitize(dist, edges)
-            real = xi != 0
-            poi_pos = torch.where(real.unsqueeze(2) & real.unsqueeze(1), poi_pos, torch.zeros_like(poi_pos))
-        else:
+        elif self.poi_source is None:
             poi_pos = torch.zeros(G, N, N, dtype=torch.int16, device=self.device)
-        return DeviceBatch1(counts, n_nodes, idx=d["idx"], attn_bias=attn_bias, rel_pos=sp["rel_pos"],
-                            in_degree=sp["in_degree"], out_degree=sp["out_degree"], x=x, edge_input=sp["edge_input"],
-                            y=d["y"], time=d["time"], time_normal=d["time_normal"], user=d["user"], cat=d["cat"],
-                            poi_pos=poi_pos)
+        else:
+            xi = x[:, :, 0].long()
+            if self.poi_source == "table":
+                poi_pos = self.bin_table[xi.unsqueeze(2), xi.unsqueeze(1)]
+            else:
+                ll = self.coords[xi]                                                 # [G,N,2] radians, float64
+                lat1, lon1, lat2, lon2 = ll[:, :, None, 0], ll[:, :, None, 1], ll[:, None, :, 0], ll[:, None, :, 1]
+                h = torch.sin((lat2 - lat1) / 2) ** 2 + torch.cos(lat1) * torch.cos(lat2) * torch.sin((lon2 - lon1) / 2) ** 2
+                dist = 2 * 6371.0 * torch.asin(torch.sqrt(h.clamp(0.0, 1.0)))      # synth.haversine_km
+                poi_pos = torch.bucketize(dist, self.bin_edges, right=True).to(torch.int16)   # == np.digitize(dist, edges)
+            real = xi != 0
+            poi_pos = torch.where(real.unsqueeze(2) & real.unsqueeze(1), poi_pos, torch.zeros_like(poi_pos))
+        return self.batch_from_views(dict(d, attn_bias=attn_bias, poi_pos=poi_pos, **sp))
 
 
 # ---- bucketed shapes for a loop over FRESH batches (train.TrainStep.run_epoch) ------------------------------------------------
@@ -350,67 +350,55 @@ def bucket_nodes(n, buckets=BUCKETS):
     return (n + 255) // 256 * 256
 
 
+TORCH_DTYPE = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32, np.int16: torch.int16, np.uint8: torch.uint8}
+
+
 class RawLayout:
     """The raw (un-collated) arrays of one (G, N) bucket packed into ONE byte buffer, so that a step's input is one
     host-to-device copy: 8-byte fields first, every field 16-byte aligned."""
-    FIELDS = (("y", np.int64, lambda G, N: (G,)), ("idx", np.int64, lambda G, N: (G,)),
-              ("counts", np.int32, lambda G, N: (G, N, N)), ("x", np.int32, lambda G, N: (G, N, 1)),
-              ("time", np.int32, lambda G, N: (G, N, 1)), ("cat", np.int32, lambda G, N: (G, N, 1)),
-              ("time_normal", np.float32, lambda G, N: (G, N, 1)), ("n_nodes", np.int32, lambda G, N: (G,)),
-              ("user", np.int32, lambda G, N: (G, 1)))
+    FIELDS = (("y", np.int64, lambda G, N, D: (G,)), ("idx", np.int64, lambda G, N, D: (G,)),
+              ("counts", np.int32, lambda G, N, D: (G, N, N)), ("x", np.int32, lambda G, N, D: (G, N, 1)),
+              ("time", np.int32, lambda G, N, D: (G, N, 1)), ("cat", np.int32, lambda G, N, D: (G, N, 1)),
+              ("time_normal", np.float32, lambda G, N, D: (G, N, 1)), ("n_nodes", np.int32, lambda G, N, D: (G,)),
+              ("user", np.int32, lambda G, N, D: (G, 1)))
 
-    def __init__(self, G, N):
-        self.G, self.N = int(G), int(N)
-        self.offsets, off = {}, 0
-        for name, dt, shape in self.FIELDS:
-            shp = shape(self.G, self.N)
+    def __init__(self, G, N, D=0):
+        self.G, self.N, self.D = int(G), int(N), int(D)
+        self.offsets = {}
+        self.nbytes = self.raw_bytes = self._place(self.FIELDS, 0)
+
+    def _place(self, fields, off):
+        """Append `fields` to the layout from byte `off` on -> the (16-byte aligned) end."""
+        for name, dt, shape in fields:
+            shp = shape(self.G, self.N, self.D)
             nbytes = int(np.prod(shp)) * np.dtype(dt).itemsize
             self.offsets[name] = (off, nbytes, dt, shp)
             off = (off + nbytes + 15) // 16 * 16
-        self.nbytes = off
+        return off
 
     def views_np(self, buf):
-        """numpy views of a host uint8 array (e.g. `pinned_tensor.numpy()`)"""
-        return {k: buf[o:o + n].view(dt).reshape(shp) for k, (o, n, dt, shp) in self.offsets.items()}
+        """numpy views of the RAW part of a host uint8 array (e.g. `pinned_tensor.numpy()`, a staging buffer of raw_bytes)"""
+        return {k: buf[o:o + n].view(dt).reshape(shp) for k, (o, n, dt, shp) in self.offsets.items() if o + n <= self.raw_bytes}
 
     def views_torch(self, buf):
         """typed torch views of a (device) uint8 tensor"""
-        tdt = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32}
-        return {k: buf[o:o + n].view(tdt[dt]).view(*shp) for k, (o, n, dt, shp) in self.offsets.items()}
+        return {k: buf[o:o + n].view(TORCH_DTYPE[dt]).view(*shp) for k, (o, n, dt, shp) in self.offsets.items()}
 
 
 class BatchLayout(RawLayout):
     """RawLayout + everything the device collate derives from it, in one byte buffer: [raw fields | derived fields |
     scratch].  A staging copy of this buffer is filled on a side stream (H2D of the raw part, then the collate kernels)
     while the previous step runs; ONE device-to-device copy of [raw | derived] then refreshes the static buffer the bucket's
-    step graph reads."""
+    step graph reads.  DERIVED and SCRATCH are also what DeviceCollator.finish allocates, as tensors of their own."""
+    DERIVED = (("attn_bias", np.float32, lambda G, N, D: (G, N + 1, N + 1)), ("rel_pos", np.int16, lambda G, N, D: (G, N, N)),
+               ("poi_pos", np.int16, lambda G, N, D: (G, N, N)), ("edge_input", np.uint8, lambda G, N, D: (G, N, N, D, 1)),
+               ("in_degree", np.int16, lambda G, N, D: (G, N)), ("out_degree", np.int16, lambda G, N, D: (G, N)))
+    SCRATCH = (("spd", np.int16, lambda G, N, D: (G, N, N)), ("path", np.int16, lambda G, N, D: (G, N, N)))
 
     def __init__(self, G, N, D):
-        super().__init__(G, N)
-        self.D = int(D)
-        self.raw_bytes = self.nbytes
-        T = self.N + 1
-        off = self.nbytes
-        derived = (("attn_bias", np.float32, (self.G, T, T)), ("rel_pos", np.int16, (self.G, self.N, self.N)),
-                   ("poi_pos", np.int16, (self.G, self.N, self.N)), ("edge_input", np.uint8, (self.G, self.N, self.N, self.D, 1)),
-                   ("in_degree", np.int16, (self.G, self.N)), ("out_degree", np.int16, (self.G, self.N)))
-        scratch = (("spd", np.int16, (self.G, self.N, self.N)), ("path", np.int16, (self.G, self.N, self.N)))
-        for group in (derived, scratch):
-            for name, dt, shp in group:
-                nbytes = int(np.prod(shp)) * np.dtype(dt).itemsize
-                self.offsets[name] = (off, nbytes, dt, shp)
-                off = (off + nbytes + 15) // 16 * 16
-            if group is derived:
-                self.copy_bytes = off                      # [raw | derived]: what a step's graph reads
-        self.nbytes = off
-
-    def views_torch(self, buf):
-        tdt = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32, np.int16: torch.int16, np.uint8: torch.uint8}
-        return {k: buf[o:o + n].view(tdt[dt]).view(*shp) for k, (o, n, dt, shp) in self.offsets.items()}
-
-    def views_np(self, buf):
-        """numpy views of the RAW part of a host uint8 array (a pinned staging buffer of raw_bytes)"""
-        return {k: buf[o:o + n].view(dt).reshape(shp) for k, (o, n, dt, shp) in self.offsets.items() if o + n <= self.raw_bytes}
+        super().__init__(G, N, D)
+        self.copy_bytes = self._place(self.DERIVED, self.raw_bytes)   # [raw | derived]: what a step's graph reads
+        self.nbytes = self._place(self.SCRATCH, self.copy_bytes)
 
 
 def shard_indices(n_samples, rank, world_size, epoch=0, seed=0, shuffle=True):
@@ -664,7 +652,9 @@ class SessionCollator(DeviceCollator):
                 torch.cuda.synchronize(self.device)                   # (rare: nothing may still read the buffers that go)
             st["cap"] = max(64, 1 << (Lp - 1).bit_length())
             st["spin"] = torch.zeros(st["slay"].nbytes(st["cap"]), dtype=torch.uint8).pin_memory()
-            st["sdev"] = torch.zeros(st["slay"].nbytes(st["cap"]), dtype=torch.uint8, device=self.device)
+            # (not zeroed: upload copies every byte the kernel and the device copies read, and a fill queued here, on the
+            #  current stream behind a running step, could land after the copy stream's upload and leave a batch of zeros)
+            st["sdev"] = torch.empty(st["slay"].nbytes(st["cap"]), dtype=torch.uint8, device=self.device)
         st["mode"], st["Lp"] = "sessions", Lp
         return self.pack_sessions(recs, idx0, st["slay"].views_np(st["spin"].numpy(), Lp))
 
@@ -676,14 +666,10 @@ class SessionCollator(DeviceCollator):
         ones is the batch's."""
         if "counts" in h:
             return super().limit_violation(h, L)
+        bad = self._id_violation(h["seq"][:, :, 0], h, L)
+        if bad:
+            return bad
         recs = h["recs"]
-        xmax = int(h["seq"][:, :, 0].max())
-        if "x" in L and xmax > L["x"]:
-            return "x", xmax, L["x"] + 1
-        if "user" in L and int(h["user"].max()) > L["user"]:
-            return "user", int(h["user"].max()), L["user"] + 1
-        if "y" in L and int(h["y"].max()) > L["y"]:
-            return "y", int(h["y"].max()), L["y"] + 1
         if "edge" in L:
             big = [r for r in recs if r.mult + 3 >= L["edge"]]
             if big:

@@ -16,6 +16,7 @@
   so a replay sees new values without re-capture.
 """
 import contextlib
+import itertools
 import os
 
 import torch
@@ -1092,8 +1093,21 @@ class TrainStep:
 
 class _StagedBatches:
     """Fresh batches on the device data path, shared by EpochLoop and EvalLoop: shape buckets, pinned staging, the device collate
-    on the copy stream and the host-side index checks.  The owner sets model, collator, dataset, buckets, device, copy_stream,
-    slots = {}, limits = None and side_collate."""
+    on the copy stream, the host-side index checks, the hand-over of a staged batch to its bucket's static buffer and the
+    one-batch-ahead pipeline."""
+
+    def __init__(self, model, collator, dataset, batch_size, buckets, rank, world, side_collate):
+        from .data import BUCKETS
+        self.model, self.collator, self.dataset = model, collator, dataset
+        self.batch_size = int(batch_size)
+        self.buckets = tuple(buckets or BUCKETS)
+        ddp = dist.is_available() and dist.is_initialized()
+        self.rank = rank if rank is not None else (dist.get_rank() if ddp else 0)
+        self.world = world if world is not None else (dist.get_world_size() if ddp else 1)
+        self.device = next(model.parameters()).device
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.slots, self.limits = {}, None
+        self.side_collate = bool(side_collate)
 
     # ---- buckets --------------------------------------------------------------------------------------------------------
     def _slot(self, G, N):
@@ -1131,16 +1145,12 @@ class _StagedBatches:
         if bad:
             raise IndexError(f"batch.{bad[0]} has index {bad[1]}, out of range for a table of {bad[2]} rows")
 
-    def _kept(self, traj):
-        """Whether a sample enters a batch: longer ones than collator.max_node are dropped (as the reference's collator does)."""
-        return self.collator.keeps(traj)
-
     def _stage(self, ids):
         """Host half of a step's input: raw samples (trajectory dicts, or sessions with a SessionCollator) -> the bucket's
         pinned buffer -> async copy to a device staging buffer on the copy stream.  Returns (slot, stage)."""
         from .data import bucket_nodes
         trajs = [self.dataset[i] for i in ids]
-        trajs = [t for t in trajs if self._kept(t)]
+        trajs = [t for t in trajs if self.collator.keeps(t)]
         G = len(trajs)
         if G == 0:
             return None                                # (every trajectory filtered out: the reference's collator skips such a batch too, collator.py:313)
@@ -1158,6 +1168,36 @@ class _StagedBatches:
                 st["work"] = self.collator.finish_into(st["dev_views"], st["work"])
             st["ready"].record(self.copy_stream)
         return slot, st
+
+    def _hand_over(self, slot, st):
+        """On the current stream (where the graphs replay): behind the staged batch's copy-stream work, ONE device-to-device copy
+        of its [raw | derived] bytes into the bucket's static buffer; then the stage may be filled again.  -> that stream."""
+        cur = torch.cuda.current_stream()
+        cur.wait_event(st["ready"])
+        n = slot["copy_bytes"]
+        slot["buf"][:n].copy_(st["dev"][:n], non_blocking=True)
+        if st["free"] is None:
+            st["free"] = torch.cuda.Event()
+        st["free"].record(cur)
+        return cur
+
+    def _collated(self, b):
+        """Inside a step or a forward: raw views -> the collate (in-graph form); a collated static batch passes through."""
+        return self.collator.finish(b) if isinstance(b, dict) else b
+
+    def _pipeline(self, batches, launch=None):
+        """One batch ahead, in this host order for every j: launch(j, slot, stage) of batch j (asynchronous: the GPU works on
+        it ...), unless staging returned None for it (an empty batch: skipped, as the reference's collator does); stage batch
+        j + 1 (... while the host packs the next one); only then yield (j, ids, staged, launch's result) to the caller, whose
+        code may synchronise.  `launch` defaults to the loop's own _launch(slot, stage)."""
+        if launch is None:
+            launch = lambda j, slot, st: self._launch(slot, st)
+        nxt = self._stage(batches[0]) if batches else None
+        for j, ids in enumerate(batches):
+            cur = nxt
+            res = launch(j, *cur) if cur is not None else None
+            nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None
+            yield j, ids, cur, res
 
 
 class EpochLoop(_StagedBatches):
@@ -1189,27 +1229,17 @@ class EpochLoop(_StagedBatches):
         mega-batch of 32 x world x batch_size i.i.d. samples -- batches stay mixed over the epoch and its long graphs are spread
         over the windows; DEVIATION from the reference's i.i.d. batches, bounded by the window; None = sort the whole epoch, the
         tightest balance; balance=False = the reference's sampler order exactly)."""
-        from .data import BUCKETS
-        self.model, self.collator, self.dataset = model, collator, dataset
-        self.batch_size, self.seed, self.shuffle = int(batch_size), int(seed), shuffle
-        self.buckets = tuple(buckets or BUCKETS)
-        ddp = dist.is_available() and dist.is_initialized()
-        self.rank = rank if rank is not None else (dist.get_rank() if ddp else 0)
-        self.world = world if world is not None else (dist.get_world_size() if ddp else 1)
+        super().__init__(model, collator, dataset, batch_size, buckets, rank, world, side_collate)
+        self.seed, self.shuffle = int(seed), shuffle
         self.balance = (self.world > 1) if balance is None else bool(balance)
         self.balance_window = balance_window
         self._lengths = None
-        self.device = next(model.parameters()).device
-        self.copy_stream = torch.cuda.Stream(device=self.device)
-        self.slots = {}
         self.ts = None
         self._ts_args = dict(autocast_dtype=autocast_dtype, use_graph=use_graph, seed=seed, overlap=overlap)
         check_accum_args(accumulate, clip_norm)          # (fail at construction, not at the first batch)
         if accumulate != 1 or clip_norm is not None:
             self._ts_args.update(accumulate=accumulate, clip_norm=clip_norm)
         self.steps_done = 0
-        self.limits = None
-        self.side_collate = bool(side_collate)
         # (round 4 measured and round 5 removed: one step graph per STAGING buffer, i.e. no device-to-device copy between two
         #  replays -- 0.734 against 0.700 ms per step on the S-FSQ pool: two graphs per bucket alternate between two sets of
         #  activation buffers, and the copy was not what the loop waited for)
@@ -1231,24 +1261,14 @@ class EpochLoop(_StagedBatches):
     def _ensure_trainer(self, slot):
         """The first batch builds the TrainStep (dry run for the trained-parameter set, flat buffers, optimizer graph)."""
         if self.ts is None:
-            self.ts = TrainStep(self.model, [slot["batch"]], batch_fn=self._batch_fn, **self._ts_args)
+            self.ts = TrainStep(self.model, [slot["batch"]], batch_fn=self._collated, **self._ts_args)
             self.ts.prepare()
             slot["index"] = 0
         elif slot["index"] is None:
             slot["index"] = self.ts.add_batch(slot["batch"])
 
-    def _batch_fn(self, b):
-        """inside the step: raw views -> collate (in-graph form); an already collated static batch passes through"""
-        return self.collator.finish(b) if isinstance(b, dict) else b
-
     def _launch(self, slot, st):
-        cur = torch.cuda.current_stream()                # (graphs replay on the current stream)
-        cur.wait_event(st["ready"])
-        n = slot["copy_bytes"]
-        slot["buf"][:n].copy_(st["dev"][:n], non_blocking=True)
-        if st["free"] is None:
-            st["free"] = torch.cuda.Event()
-        st["free"].record(cur)
+        self._hand_over(slot, st)
         if slot["index"] is None or self.ts is None:
             self._ensure_trainer(slot)                   # (dry run / capture on the data that is now in the static buffer)
         return self.ts.step(slot["index"])
@@ -1262,16 +1282,11 @@ class EpochLoop(_StagedBatches):
         seen = []
         if not batches:
             return dict(steps=0, graphs=len(self.slots), sample_ids=seen)
-        nxt = self._stage(batches[0])
         steps = 0
-        for j, ids in enumerate(batches):
-            cur = nxt
-            if cur is not None:
-                loss = self._launch(*cur)                # asynchronous: the GPU works on step j ...
-            nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None          # ... while the host packs j + 1
+        for _, ids, staged, loss in self._pipeline(batches):
             seen.extend(ids)
-            if cur is None:
-                continue                                 # (an empty batch: skipped, as the reference's collator does)
+            if staged is None:
+                continue
             steps += 1
             self.steps_done += 1
             if on_step is not None:
@@ -1355,7 +1370,8 @@ class EvalLoop(_StagedBatches):
 
     dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator -- the
     loops reach the input form through the collator only (nodes_of, keeps, lengths_of, new_stage, stage_host, limit_violation,
-    upload)."""
+    upload), and the collate through can_finish_into, finish_into and batch_from_views on the copy stream, or finish inside
+    the step."""
 
     def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
                  side_collate=True, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
@@ -1381,20 +1397,10 @@ class EvalLoop(_StagedBatches):
         self.work = torch.empty(ops.rank_metrics_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
 
     def _setup(self, model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate):
-        from .data import BUCKETS
-        self.model, self.collator, self.dataset = model, collator, dataset
-        self.batch_size = int(batch_size)
-        self.buckets = tuple(buckets or BUCKETS)
-        ddp = dist.is_available() and dist.is_initialized()
-        self.rank = rank if rank is not None else (dist.get_rank() if ddp else 0)
-        self.world = world if world is not None else (dist.get_world_size() if ddp else 1)
-        self.device = next(model.parameters()).device
-        self.copy_stream = torch.cuda.Stream(device=self.device)
+        super().__init__(model, collator, dataset, batch_size, buckets, rank, world, side_collate)
         self.stream = torch.cuda.Stream(device=self.device) if use_graph else None     # warm-ups and captures
         self.use_graph = bool(use_graph)
-        self.side_collate = bool(side_collate)
-        self.slots, self.limits, self.graphs = {}, None, {}
-        self._graph_ptrs = None
+        self.graphs, self._graph_ptrs = {}, None
 
     def batches(self):
         from .data import shard_indices
@@ -1403,7 +1409,7 @@ class EvalLoop(_StagedBatches):
         return [idx[i:i + B] for i in range(0, len(idx), B)]
 
     def _forward(self, batch, acc):
-        b = self.collator.finish(batch) if isinstance(batch, dict) else batch      # (raw views: the in-graph collate)
+        b = self._collated(batch)
         if self.restricted:
             self.model.metric_step(b, acc, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow,
                                    split_revisits=self.split_revisits, near=self.near)
@@ -1422,13 +1428,7 @@ class EvalLoop(_StagedBatches):
         return tuple(ptrs)
 
     def _launch(self, slot, st):
-        cur = torch.cuda.current_stream()
-        cur.wait_event(st["ready"])
-        n = slot["copy_bytes"]
-        slot["buf"][:n].copy_(st["dev"][:n], non_blocking=True)
-        if st["free"] is None:
-            st["free"] = torch.cuda.Event()
-        st["free"].record(cur)
+        cur = self._hand_over(slot, st)
         if not self.use_graph or not slot["side"]:
             # Buckets whose collate needs torch ops (coords= + bin_edges=: S-BIG's default collator) run eagerly.  Captured with the collate inside, the
             # replay took 130 ms per 16 x 784 batch against 13 ms eager: inside the replayed graph the SPD kernel's split form
@@ -1502,12 +1502,8 @@ class EvalLoop(_StagedBatches):
             batches = batches[:max_batches]
         with self._evaluating():
             self.acc.zero_()
-            nxt = self._stage(batches[0]) if batches else None
-            for j in range(len(batches)):
-                cur = nxt
-                if cur is not None:
-                    self._launch(*cur)                   # asynchronous: the GPU evaluates batch j ...
-                nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None     # ... while the host packs j + 1
+            for _ in self._pipeline(batches):
+                pass
             if self.world > 1 and dist.is_available() and dist.is_initialized():
                 if dist.get_backend() == "gloo":
                     host = self.acc.cpu()
@@ -1557,7 +1553,7 @@ class PredictLoop(EvalLoop):
         self.work = torch.empty(ops.topk_work_bytes(self.batch_size, V, self.k), dtype=torch.uint8, device=self.device)
 
     def _forward(self, batch, _acc):
-        b = self.collator.finish(batch) if isinstance(batch, dict) else batch
+        b = self._collated(batch)
         self.model.recommend_step(b, *self._out, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow,
                                   near=self.near)
 
@@ -1581,22 +1577,22 @@ class PredictLoop(EvalLoop):
         sample_index = torch.tensor(flat, dtype=torch.int64).to(self.device)
         ids = torch.full((len(flat), self.k), -1, dtype=torch.int64, device=self.device)
         vals = torch.full((len(flat), self.k), float("-inf"), dtype=torch.float32, device=self.device)
+        starts = [0, *itertools.accumulate(len(b) for b in batches)]
+
+        def launch(j, slot, st):
+            """Rank batch j, then -- enqueued before the next batch is staged -- its lists into the result's rows."""
+            bi, bv = self._launch(slot, st)
+            rows = [starts[j] + i for i, t in enumerate(batches[j]) if self.collator.keeps(self.dataset[t])]
+            r = 0
+            while r < len(rows):                         # runs of kept rows (one run unless a trajectory was dropped)
+                e = r + 1
+                while e < len(rows) and rows[e] == rows[e - 1] + 1:
+                    e += 1
+                ids[rows[r]:rows[e - 1] + 1].copy_(bi[r:e], non_blocking=True)
+                vals[rows[r]:rows[e - 1] + 1].copy_(bv[r:e], non_blocking=True)
+                r = e
+
         with self._evaluating():
-            nxt = self._stage(batches[0]) if batches else None
-            off = 0
-            for j, b in enumerate(batches):
-                cur = nxt
-                if cur is not None:
-                    bi, bv = self._launch(*cur)          # asynchronous: the GPU ranks batch j ...
-                    rows = [off + i for i, t in enumerate(b) if self._kept(self.dataset[t])]
-                    r = 0
-                    while r < len(rows):                 # runs of kept rows (one run unless a trajectory was dropped)
-                        e = r + 1
-                        while e < len(rows) and rows[e] == rows[e - 1] + 1:
-                            e += 1
-                        ids[rows[r]:rows[e - 1] + 1].copy_(bi[r:e], non_blocking=True)
-                        vals[rows[r]:rows[e - 1] + 1].copy_(bv[r:e], non_blocking=True)
-                        r = e
-                nxt = self._stage(batches[j + 1]) if j + 1 < len(batches) else None     # ... while the host packs j + 1
-                off += len(b)
+            for _ in self._pipeline(batches, launch):
+                pass
         return sample_index, ids, vals

@@ -185,9 +185,25 @@ def test_collator_against_the_haversine_collator():
     pair_bins_cases.assert_agrees_with_haversine(a.poi_pos.cpu().numpy(), uni.coords, x, uni.bin_edges, "against np.digitize")
 
 
-def test_finish_into_equals_finish():
+@functools.lru_cache(maxsize=None)
+def small_table():
+    """The int16 bin table of the small universe, as geo.distance_bins leaves it on the device."""
+    uni, _ = small_universe()
+    table = geo.distance_bins(uni.coords, device=DEV, pad_row=True).table
+    assert table.dtype == torch.int16 and table.is_contiguous() and table.shape == (401, 401)
+    return table
+
+
+def collator_with(source, **kw):
+    """A collator per source of poi_pos the kernels serve: the chord search, the int16 table, none (all zeros)."""
+    source_kw = dict(pair_bins=dict(pair_bins=small_universe()[1]), table=dict(bin_table=small_table()), none={})[source]
+    return DeviceCollator(DEV, **source_kw, **kw)
+
+
+@pytest.mark.parametrize("source", ["pair_bins", "table", "none"])
+def test_finish_into_equals_finish(source):
     uni, pb = small_universe()
-    coll = DeviceCollator(DEV, pair_bins=pb)
+    coll = collator_with(source)
     trajs = synth.make_batch_of_trajectories(seed=6, G=5, P=400, n_user=8, cat_of_poi=uni.cat_of_poi, n_nodes=[61, 2, 33, 1, 20])
     G, N = 5, 65                                                       # (odd N: rows of poi_pos start on odd int16 offsets)
     h = coll.pack_host(trajs, idx0=3, n_pad=N)
@@ -200,7 +216,94 @@ def test_finish_into_equals_finish():
     coll.finish_into(v)
     want = coll.finish({k: torch.from_numpy(arr).to(DEV) for k, arr in h.items()})
     same_fields(coll.batch_from_views(v), want)
-    assert int(want.poi_pos.max()) > 1
+    assert int(want.poi_pos.max()) > 1 if source != "none" else not bool(want.poi_pos.any())
+
+
+# finish has two forms: finish_into's launches into fresh tensors (the kernel form) and torch ops behind mobgt_spd_batched (the
+# torch form: haversine bins, a table that is not contiguous int16, ids that are not int32).  G = 4 graphs of 1, 5, 33 and 64
+# nodes at the odd pitch N = 65, D = 20.
+FORMS_N, FORMS_NODES = 65, (1, 5, 33, 64)
+
+
+@functools.lru_cache(maxsize=None)
+def forms_batch():
+    """The raw arrays of that batch on the device (read only: finish writes none of them)."""
+    uni, _ = small_universe()
+    trajs = synth.make_batch_of_trajectories(seed=7, G=len(FORMS_NODES), P=400, n_user=8, cat_of_poi=uni.cat_of_poi, n_nodes=list(FORMS_NODES))
+    h = DeviceCollator(DEV).pack_host(trajs, idx0=11, n_pad=FORMS_N)
+    return {k: torch.from_numpy(arr).to(DEV) for k, arr in h.items()}
+
+
+@pytest.mark.parametrize("rel_pos_max", [1024, 3])
+def test_torch_form_of_finish_equals_the_kernel_form(rel_pos_max):
+    """attn_bias holds 0 and -inf only and every other field is an integer or a copy: equality is exact.  The int64 table gives
+    an int64 poi_pos, compared by value."""
+    d = forms_batch()
+    kernel = DeviceCollator(DEV, bin_table=small_table(), multi_hop_max_dist=20, rel_pos_max=rel_pos_max)
+    by_torch = DeviceCollator(DEV, bin_table=small_table().long(), multi_hop_max_dist=20, rel_pos_max=rel_pos_max)
+    assert kernel.can_finish_into() and not by_torch.can_finish_into()
+    a, b = kernel.finish(dict(d)), by_torch.finish(dict(d))
+    same_fields(a, b, skip=("poi_pos",))
+    assert a.poi_pos.dtype == torch.int16 and a.poi_pos.shape == b.poi_pos.shape == (4, FORMS_N, FORMS_N)
+    assert torch.equal(a.poi_pos.long(), b.poi_pos.long()) and int(a.poi_pos.max()) > 1
+    assert a.edge_input.shape == (4, FORMS_N, FORMS_N, 20, 1)
+    far = torch.isinf(a.attn_bias[3, 1:65, 1:65]).any()               # (among the 64 real nodes of the longest graph)
+    assert bool(far) == (rel_pos_max == 3) and bool(torch.isinf(a.attn_bias[0, :, 2:]).all())
+    # no table: all-zero int16 poi_pos by either form; ids given as int64 select the torch form
+    none = DeviceCollator(DEV, multi_hop_max_dist=20, rel_pos_max=rel_pos_max)
+    k, t = none.finish(dict(d)), none.finish(dict(d, x=d["x"].long()))
+    same_fields(k, t, skip=("x",))
+    assert torch.equal(k.x.long(), t.x) and k.poi_pos.dtype == torch.int16 and not bool(k.poi_pos.any())
+    same_fields(k, a, skip=("poi_pos",))
+
+
+def test_which_entry_points_a_finish_calls(monkeypatch):
+    """The library calls of every form, in order, as the code before finish had one kernel path made them: the workspace query,
+    mobgt_spd_batched, mobgt_collate_finish [, one mobgt_bins_batch]; the torch form stops behind mobgt_spd_batched."""
+    from mobgt_amd import _lib
+    uni, pb = small_universe()
+    d, table = forms_batch(), small_table()
+    real, real_launch = _lib.lib(), _pairbins.launch
+    work = torch.empty(int(real.mobgt_spd_workspace_bytes(4, FORMS_N)), dtype=torch.uint8, device=DEV)
+    seen = []
+
+    class _Spy:
+        def __getattr__(self, name):
+            seen.append(name)
+            return getattr(real, name)
+
+    def launch(name, *args):
+        seen.append(name)
+        return real_launch(name, *args)
+
+    monkeypatch.setattr(_lib, "lib", lambda: _Spy())
+    monkeypatch.setattr(_pairbins, "launch", launch)
+
+    def calls(fn):
+        del seen[:]
+        fn()
+        return list(seen)
+
+    def views(coll):
+        lay = data.BatchLayout(4, FORMS_N, coll.D)
+        v = lay.views_torch(torch.zeros(lay.nbytes, dtype=torch.uint8, device=DEV))
+        for k, t in d.items():
+            v[k].copy_(t)
+        return v
+
+    kernel = ["mobgt_spd_workspace_bytes", "mobgt_spd_batched", "mobgt_collate_finish"]
+    for source, more in (("table", []), ("none", []), ("pair_bins", ["mobgt_bins_batch"])):
+        coll = collator_with(source)
+        assert calls(lambda: coll.finish(dict(d))) == kernel + more, source
+        v = views(coll)
+        assert calls(lambda: coll.finish_into(v)) == kernel + more, source
+        assert calls(lambda: coll.finish_into(v, work)) == kernel[1:] + more, source
+    by_torch = ["mobgt_spd_workspace_bytes", "mobgt_spd_batched"]
+    haversine = DeviceCollator(DEV, coords=uni.coords, bin_edges=uni.bin_edges)
+    assert calls(lambda: haversine.finish(dict(d))) == by_torch
+    assert calls(lambda: DeviceCollator(DEV, bin_table=table.long()).finish(dict(d))) == by_torch
+    assert calls(lambda: collator_with("none").finish(dict(d, x=d["x"].long()))) == by_torch
+    torch.cuda.synchronize()
 
 
 def test_session_collator_equals_the_dict_collator():

@@ -309,6 +309,33 @@ def test_epoch_loop_stages_the_same_bytes_from_sessions_and_from_dicts(side):
         assert torch.equal(c.slots[key]["buf"][:want.numel()], want), key
 
 
+def test_first_use_of_a_session_stage_behind_a_busy_compute_stream(fsq):
+    """A stage allocates its device session buffer on its first use, when the compute stream may still run a step.  Nothing
+    queued on that stream for the new buffer may land after the copy stream has filled it (a fill that lands between the
+    upload and the kernel that reads it leaves a batch of zeros): staged while the compute stream is kept busy for some tens
+    of milliseconds, the buffer still holds the uploaded bytes once both streams are idle, and the stage the dict path's."""
+    uni, model, coll, scoll, sessions = fsq
+    ds, dicts = SessionDataset(sessions[:16]), sessions_to_trajectories(sessions[:16])
+    a, b = EvalLoop(model, scoll, ds, batch_size=16), EvalLoop(model, coll, dicts, batch_size=16)
+    ids = list(range(16))
+    key, want = _staged_bytes(b, ids)
+    slot, first = a._stage(ids)                                        # (the bucket and its first stage exist now)
+    torch.cuda.synchronize()
+    busy = torch.randn(4096, 4096, device=DEV)
+    busy = (busy @ busy).clamp_(-1.0, 1.0)                             # (the GEMM library is loaded before the clock matters)
+    torch.cuda.synchronize()
+    for _ in range(40):
+        busy = (busy @ busy).clamp_(-1.0, 1.0)                         # queued on the compute stream, not waited for
+    slot, st = a._stage(ids)                                           # the second stage's first use
+    assert st is not first and st["mode"] == "sessions"
+    a.copy_stream.synchronize()
+    got = st["dev"][:slot["copy_bytes"]].clone()
+    torch.cuda.synchronize()
+    assert (slot["layout"].G, slot["layout"].N) == key and torch.equal(got, want)
+    nb = st["slay"].nbytes(st["Lp"])
+    assert torch.equal(st["sdev"][:nb].cpu(), st["spin"][:nb]) and int(st["spin"][:nb].max()) > 0
+
+
 def test_out_of_range_indices_raise_on_the_host_before_any_launch(fsq):
     uni, model, coll, scoll, sessions = fsq
     model.eval()
