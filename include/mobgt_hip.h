@@ -539,15 +539,17 @@ int mobgt_colsum(const void* g, float* out, int64_t R, int C, int act_dtype, voi
  * F.linear backward computes as dy^T x and dy.sum(0)):  dw [M,N] (f32, row pitch ldw) += g^T x and, when db is
  * not null, db [M] += column sums of g, for g [R,M] (row pitch ldg) and x [R,N] (row pitch ldx), both bf16
  * (act_dtype MOBGT_BF16) or both f32 (MOBGT_F32: rounded to bf16 while loading -- bf16 MFMA operands, f32
- * accumulate -- exactly what a cast kernel in front would produce).  M, N, ldg, ldx even; g, x 4-byte (8-byte for
+ * accumulate -- exactly what a cast kernel in front would produce; db then sums g AFTER its rounding to bf16, the values the
+ * matrix cores see, not the f32 ones in memory).  M, N, ldg, ldx even; g, x 4-byte (8-byte for
  * f32) aligned.  Split over R across the grid with
  * f32 atomics into dw/db, which the caller zero-initialises (or pre-loads with a gradient to accumulate into). */
 int mobgt_linear_wgrad(const void* g, int64_t ldg, const void* x, int64_t ldx, float* dw, int64_t ldw, float* db,
                        int64_t R, int M, int N, int act_dtype, void* stream);
 /* ... with f32 operands and the activation derivative m(.) of mobgt_small_gemm_f32_act applied to g and / or x while they
  * are loaded (g_mask / x_mask: the activation's output, the operand's layout; either may be null).  db_of_x: db is [N] and
- * receives the column sums of the (masked) x instead of g.  g_masked_out (optional, g's layout, f32): the masked g itself,
- * for a data-gradient GEMM that follows. */
+ * receives the column sums of the (masked) x instead of g.  An operand is multiplied by m(.) in f32 and THEN rounded to nearest
+ * even to bf16; db sums the operand after that rounding.  g_masked_out (optional, g's layout, f32): the masked g itself before
+ * the rounding, for a data-gradient GEMM that follows (written only with a g_mask). */
 int mobgt_linear_wgrad_masked(const float* g, int64_t ldg, const float* x, int64_t ldx, const float* g_mask, const float* x_mask,
                               float m_pos, float m_neg, float m_zero, float* g_masked_out, float* dw, int64_t ldw, float* db,
                               int db_of_x, int64_t R, int M, int N, void* stream);
@@ -556,7 +558,8 @@ int mobgt_linear_wgrad_masked(const float* g, int64_t ldg, const float* x, int64
 int mobgt_linear_wgrad_bias(const void* g, int64_t ldg, const void* x, int64_t ldx, const float* out_bias, float* dw,
                             int64_t ldw, int64_t R, int M, int N, int act_dtype, void* stream);
 /* g bf16 [R,M], x f32 [R,N] (rounded to bf16 while loading): dw (ZERO on entry) = g^T x and db_x [N] (zero on entry, or null)
- * += column sums of x: d(support) = adj[rows]^T dout and b.grad = dout.sum(0) of the rows-only GraphConvolution's backward. */
+ * += column sums of x AFTER its rounding to bf16: d(support) = adj[rows]^T dout and b.grad = dout.sum(0) of the rows-only
+ * GraphConvolution's backward. */
 int mobgt_linear_wgrad_mixed(const void* g_bf16, int64_t ldg, const float* x_f32, int64_t ldx, float* dw, int64_t ldw,
                              float* db_x, int64_t R, int M, int N, void* stream);
 /* The same for n <= 32 independent Linear layers over the same R rows in ONE launch (host arrays of n entries each;
@@ -569,7 +572,8 @@ int mobgt_linear_wgrad_group(int n, const void* const* g, const int64_t* ldg, co
  * (bf16 when in_f32[q] == 0, f32 rounded to bf16 while loading when 1); f32 operands may carry activation masks g_mask[q] /
  * x_mask[q] (operand's layout; m(y) = y > 0 ? mask_vals[3q] : (y < 0 ? mask_vals[3q+1] : mask_vals[3q+2]) multiplies the
  * operand: the derivative of dropout(leaky_relu(.)) taken from the activation's output, model_fqandtoyo.py:452-455,
- * modelGNN.py:66-72); db[q] (or NULL) accumulates the column sums of the masked g, or of x when db_of_x[q].  dw[q] and db[q]
+ * modelGNN.py:66-72); db[q] (or NULL) accumulates the column sums of the masked g, or of x when db_of_x[q] (of an f32 operand:
+ * after its rounding to bf16).  dw[q] and db[q]
  * accumulate (zero them first).  One launch: the leaf weight gradients of a training step issued together. */
 int mobgt_linear_wgrad_multi(int n, const void* const* g, const int64_t* ldg, const void* const* x, const int64_t* ldx,
                              const float* const* g_mask, const float* const* x_mask, const float* mask_vals,

@@ -2508,11 +2508,12 @@ def linear_wgrad_masked(g, x, g_mask=None, x_mask=None, mask_vals=(1.0, 1.0, 1.0
         assert m is None or (m.dtype == torch.float32 and m.shape == t.shape and m.stride() == t.stride())
     if dw is None:
         dw = zeros_f32((M, N), g.device)
+    assert dw.dim() == 2 and dw.stride(1) == 1          # (its row pitch may exceed N: a column view of a wider buffer)
     assert g_out is None or (g_mask is not None and g_out.shape == g.shape and g_out.stride() == g.stride())
     if leaf and STEP.wgrad_on and g_out is None and M % 2 == 0 and N % 2 == 0:
         return _wgrad_defer(g, x, g_mask, x_mask, mask_vals, dw, db, db_of_x)
     _lib.call("mobgt_linear_wgrad_masked", _p(g), g.stride(0), _p(x), x.stride(0), _p(g_mask), _p(x_mask), float(mask_vals[0]),
-              float(mask_vals[1]), float(mask_vals[2]), _p(g_out), _p(dw), N, _p(db), int(db_of_x),
+              float(mask_vals[1]), float(mask_vals[2]), _p(g_out), _p(dw), dw.stride(0), _p(db), int(db_of_x),
               R, M, N, _stream())
     return dw
 
@@ -2610,16 +2611,17 @@ def linear_wgrad(g, x, with_bias=False, db=None, out_bias=None, leaf=False, dw=N
     assert g.dtype == x.dtype and g.dtype in (torch.bfloat16, torch.float32) and g.stride(1) == 1 and x.stride(1) == 1
     if dw is None:                    # (`dw` / `db`: zeroed f32 destinations the products are ADDED to -- e.g. gradient sinks)
         dw = zeros_f32((M, N), g.device)
+    assert dw.dim() == 2 and dw.stride(1) == 1          # (its row pitch may exceed N: a column view of a wider buffer)
     if out_bias is not None:
         assert db is None and not with_bias and out_bias.dtype == torch.float32 and out_bias.numel() == N
-        _lib.call("mobgt_linear_wgrad_bias", _p(g), g.stride(0), _p(x), x.stride(0), _p(out_bias.contiguous()), _p(dw), N, R, M, N,
+        _lib.call("mobgt_linear_wgrad_bias", _p(g), g.stride(0), _p(x), x.stride(0), _p(out_bias.contiguous()), _p(dw), dw.stride(0), R, M, N,
                   _DT[g.dtype], _stream())
         return dw, None
     if db is None and with_bias:
         db = zeros_f32((M,), g.device)
     if leaf and STEP.wgrad_on and M % 2 == 0 and N % 2 == 0:
         return _wgrad_defer(g, x, None, None, (1.0, 1.0, 1.0), dw, db, False), (db[:] if db is not None else None)
-    _lib.call("mobgt_linear_wgrad", _p(g), g.stride(0), _p(x), x.stride(0), _p(dw), N, _p(db), R, M, N, _DT[g.dtype],
+    _lib.call("mobgt_linear_wgrad", _p(g), g.stride(0), _p(x), x.stride(0), _p(dw), dw.stride(0), _p(db), R, M, N, _DT[g.dtype],
               _stream())
     return dw, db
 
