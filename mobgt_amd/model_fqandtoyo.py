@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import forms, ops
+from .restriction import Restriction
 from .step_state import STEP
 from .lr import PolynomialDecayLR
 from .model import (FeedForwardNetwork, MultiHeadAttention, hop_table_from, no_grad_row0, fused_layer_forward,
@@ -483,7 +484,9 @@ class Graphormer(nn.Module):
         return dict(x=self.X.shape[0], user=self.num_users, y=self.out_proj.out_features, edge=self.edge_encoder.num_embeddings,
                     deg=self.in_degree_encoder.num_embeddings, slots=self.time_embed_model_48.num_embeddings)
 
-    def forward(self, batched_data, perturb=None):
+    def encode(self, batched_data):
+        """The batch -> tok [G, C + U], the classifier heads' input (:1143-1364): everything but the two output Linears.  Leaves
+        `_bias_pack`, `_cuts` and `_enc_out` on the module for train.TrainStep, which cuts the backward pass there."""
         self.validate_batch(batched_data)
         # The category GCN (weights only: no batch input; one launch that keeps 19 compute units busy) goes FIRST and carries the
         # step's other front-of-step launches as passenger workgroups: the hop table's forward, the gather indices, the MFMA-order
@@ -548,106 +551,59 @@ class Graphormer(nn.Module):
             tok = fuse3(output[:, 0, :].float(), user_embedding)                               # :1353-1358, q = 0 only
             tok = ops.dropout(self.ELU(self.final_ln(tok)), self.output_dropout.p, self.training, 0x1004)   # :1360-1364
         ops.trace_nan("tok", tok)
-        y_head = getattr(self, "_loss_in_head", None)
-        toyota = self.dataset_name == "toyotagraph"
-        m_head = getattr(self, "_metrics_in_head", None)
-        if m_head is not None:
-            # metric_step: the classifier ends in the ranking metrics of test_epoch_end (:1546-1597) added to a device
-            # accumulator; cat_decoder's output (read by nobody there) is not produced
-            y_m, acc, work, restrict = m_head
-            W, b = self.out_proj.weight, self.out_proj.bias
-            # (the logits are stored and ranked by mobgt_rank_metrics: measured faster than the fused classifier-ranking form,
-            #  ops.skinny_linear_rank_metrics, at every width from 3 680 to 100 001 classes -- 15.1 against 23.4 us at S-FSQ's
-            #  7 857, 49 against 75 us at S-BIG's 100 001 (tools/eval_bench.py); both give the same bits)
-            logits = ops.skinny_linear(tok, W, b) if ops.skinny_linear_ok(tok, W) else self.out_proj(tok)
-            if restrict is not None:
-                # restricted / split: recommend_step's scores, candidates and label space (x holds the trajectory's POI ids as
-                # y does, 0 = padding; column = y - 1 = x - 1, or y = x for toyotagraph)
-                exclude_visited, allow, split, near = restrict
-                scores = torch.log_softmax(logits.float(), dim=1) if toyota else logits
-                hist = batched_data.x.reshape(batched_data.x.shape[0], -1)
-                if near is not None:
-                    allow = self._near_allow(hist, near, allow, toyota)
-                ops.rank_metrics_masked(scores, y_m, acc, target_offset=0 if toyota else -1, allow=allow, hist=hist,
-                                        hist_offset=0 if toyota else 1, exclude_hist=exclude_visited, split=split, work=work)
-                return [None, None]
-            if toyota:
-                # :1484-1495: toyotagraph is not in the y - 1 list -- unshifted y, and the POI head's log-probabilities (:1417-1428)
-                ops.rank_metrics(torch.log_softmax(logits.float(), dim=1), y_m, acc, target_offset=0, work=work)
-            else:
-                ops.rank_metrics(logits, y_m, acc, target_offset=-1, work=work)
-            return [None, None]
-        r_head = getattr(self, "_recommend_in_head", None)
-        if r_head is not None:
-            # recommend_step: the classifier's scores ranked into the caller's [G, k] buffers, ids in y's label space (the scores
-            # and shift metric_step ranks: log_softmax and unshifted for toyotagraph, logits and column + 1 otherwise)
-            ids, vals, work, exclude_visited, allow, near = r_head
-            W, b = self.out_proj.weight, self.out_proj.bias
-            logits = ops.skinny_linear(tok, W, b) if ops.skinny_linear_ok(tok, W) else self.out_proj(tok)
-            scores = torch.log_softmax(logits.float(), dim=1) if toyota else logits
-            # (exclude_visited: x holds the trajectory's POI ids in y's label space, 0 = padding)
-            hist = batched_data.x.reshape(batched_data.x.shape[0], -1)
-            excl = hist if exclude_visited else None
-            if near is not None:
-                allow = self._near_allow(hist, near, allow, toyota)
-            ops.topk_rows(scores, ids.shape[1], col_offset=0 if toyota else 1, work=work, out=(ids, vals), allow=allow, exclude=excl)
-            return [None, None]
-        if y_head is not None and not toyota and ops.skinny_linear_gtl_ok(tok, self.out_proj.weight):
-            # training_step: the classifier and GradientTailLoss(alpha = 0.2) on y - 1 (:1394, :1446-1460) in ONE launch; the
-            # logits are never stored
-            self._head_loss = ops.skinny_linear_gtl(tok, self.out_proj.weight, self.out_proj.bias, y_head, 0.2, target_offset=-1)
-            return [None, None]
+        return tok
+
+    @property
+    def label_offset(self):
+        """y - label_offset is y's column of the POI head: 1 for foursquaregraph / gowalla, whose steps rank against y - 1
+        (:1446-1460, :1483-1495), 0 for toyotagraph, whose steps take y as it is (:1462-1471).  x holds POI ids as y does."""
+        return 0 if self.dataset_name == "toyotagraph" else 1
+
+    def poi_logits(self, tok):
+        """:1394 with M = G rows: the skinny classifier where the shape allows it, else out_proj"""
         if ops.skinny_linear_ok(tok, self.out_proj.weight):
-            logits = ops.skinny_linear(tok, self.out_proj.weight, self.out_proj.bias)      # :1394, M = G rows
+            logits = ops.skinny_linear(tok, self.out_proj.weight, self.out_proj.bias)
         else:
             logits = self.out_proj(tok)
-        ops.trace_nan("logits", logits)
-        if toyota:
-            # :1417-1428: the POI head returns log-probabilities.  training_step (below) takes the raw logits instead -- its
-            # fused log-softmax + NLL kernel (mobgt_cross_entropy) is NLLLoss(log_softmax(logits)) -- through `_toyota_logits`
-            self._toyota_logits = logits
-            return [torch.log_softmax(logits.float(), dim=1), self.cat_decoder(tok)]
-        if getattr(self, "_poi_logits_only", False):     # training_step reads logits[0] only (:1446-1460)
-            return [logits, None]
-        return [logits, self.cat_decoder(tok)]                                                 # :1394-1396
+        return ops.trace_nan("logits", logits)
 
-    @staticmethod
-    def _near_allow(hist, near, allow, toyota):
-        """metric_step's / recommend_step's near=: the rows' candidate words (ops.near_words on the trajectory's POI ids, the hist
-        and offset exclude_visited uses; a shared allow ANDed in) written into the caller's buffer -> the 2-D allow"""
-        pos, chord2_max, mode, words = near
-        return ops.near_words(pos, hist, 0 if toyota else 1, chord2_max, mode, allow=allow, out=words[:hist.shape[0]])
+    def poi_scores(self, tok):
+        """What the reference's steps rank: the POI logits; for toyotagraph the head's log-probabilities (:1417-1428).
+        (The logits are stored and ranked by mobgt_rank_metrics: measured faster than the fused classifier-ranking form,
+        ops.skinny_linear_rank_metrics, at every width from 3 680 to 100 001 classes -- 15.1 against 23.4 us at S-FSQ's 7 857,
+        49 against 75 us at S-BIG's 100 001 (tools/eval_bench.py); both give the same bits.)"""
+        logits = self.poi_logits(tok)
+        return torch.log_softmax(logits.float(), dim=1) if self.label_offset == 0 else logits
+
+    def forward(self, batched_data, perturb=None):
+        tok = self.encode(batched_data)
+        return [self.poi_scores(tok), self.cat_decoder(tok)]                                              # :1394-1396 / :1417-1428
 
     # modules whose parameters only receive gradient from the part of the graph ABOVE the encoder output: their
     # gradients are complete after the first ~20 kernels of the backward pass (61 % of all gradient bytes: out_proj)
     head_modules = ("out_proj", "final_ln", "embed_fuse_model3", "user_embed_model", "cat_decoder")
 
     def training_step(self, batched_data, batch_idx=0):
-        """model_fqandtoyo.py:1446-1460: y-1 targets, GradientTailLoss(alpha=0.2) on the POI logits only.
+        """model_fqandtoyo.py:1446-1460: y-1 targets, GradientTailLoss(alpha=0.2) on the POI logits only (the category decoder,
+        whose output the loss does not read, is not run).
         toyotagraph (:1462-1471): GradientTailLoss(category logits, category of the target POI - 1, alpha = 0.1) +
         NLLLoss(ignore_index=0)(log_softmax(POI logits), y) -- y unshifted, the category target as :1262 derives it."""
+        tok = self.encode(batched_data)
         if self.dataset_name == "toyotagraph":
-            out = self(batched_data)
-            logits = self.__dict__.pop("_toyota_logits")
+            logits, cat_logits = self.poi_logits(tok), self.cat_decoder(tok)
             y = batched_data.y.long().view(-1)
             cat_target = self.poi2cat[y] - 1                                                   # :1262 (poi_idx2cat_idx_dict[y] - 1)
-            loss_cat = ops.gradient_tail_loss(out[1], cat_target, 0.1, target_offset=0)
+            loss_cat = ops.gradient_tail_loss(cat_logits, cat_target, 0.1, target_offset=0)
             if ops.cross_entropy_ok(logits, y):
+                # (mobgt_cross_entropy is NLLLoss(log_softmax(logits)) in one kernel: the log-probabilities are never stored)
                 loss_poi = ops.cross_entropy(logits, y, ignore_index=0)
             else:
-                loss_poi = torch.nn.functional.nll_loss(out[0], y, ignore_index=0)
+                loss_poi = F.nll_loss(torch.log_softmax(logits.float(), dim=1), y, ignore_index=0)
             return loss_cat + loss_poi
-        self._poi_logits_only = True
-        self._loss_in_head = batched_data.y              # (forward() may fold the loss into the classifier's launch)
-        try:
-            y_hat = self(batched_data)[0]
-        finally:
-            self._poi_logits_only = False
-            self._loss_in_head = None
-        loss = self.__dict__.pop("_head_loss", None)
-        if loss is not None:
-            return loss
-        return ops.gradient_tail_loss(y_hat, batched_data.y, 0.2, target_offset=-1)
+        if ops.skinny_linear_gtl_ok(tok, self.out_proj.weight):
+            # the classifier and the loss in ONE launch; the logits are never stored
+            return ops.skinny_linear_gtl(tok, self.out_proj.weight, self.out_proj.bias, batched_data.y, 0.2, target_offset=-1)
+        return ops.gradient_tail_loss(self.poi_logits(tok), batched_data.y, 0.2, target_offset=-1)
 
     def validation_step(self, batched_data, batch_idx=0):
         """model_fqandtoyo.py:1483-1495"""
@@ -657,7 +613,8 @@ class Graphormer(nn.Module):
         """model_fqandtoyo.py:1530-1544"""
         return {"y_pred": self(batched_data), "y_true": batched_data.y.long() - 1, "idx": batched_data.idx}
 
-    def metric_step(self, batched_data, acc, work=None, exclude_visited=False, allow=None, split_revisits=False, near=None):
+    def metric_step(self, batched_data, acc, work=None, exclude_visited=False, allow=None, split_revisits=False, near=None,
+                    restriction=None):
         """validation_step / test_step + test_epoch_end's per-batch bookkeeping in one pass: the batch's ACC / NDCG @1/5/10/20
         and MRR sums (metrics.evaluate_outputs, quirks included) are ADDED to `acc` (metrics.new_accumulator) on the device --
         no category head, no host read.  Eval mode, under no_grad.  toyotagraph ranks log_softmax(logits) against
@@ -667,21 +624,23 @@ class Graphormer(nn.Module):
         ops.rank_metrics_masked_work_bytes): the ranking of the lists recommend_step returns with the same exclude_visited /
         allow, so a hit at k <=> y is in that list's first k; a row whose y cannot be listed counts in n only.  split_revisits
         adds the rows whose y is not among the trajectory's POIs (batched_data.x) to slot 1, the others to slot 2.
-        near: recommend_step's radius restriction (see there); a y outside its row's radius counts in n only."""
+        near: recommend_step's radius restriction (see there); a y outside its row's radius counts in n only.
+        restriction: a prebuilt restriction.Restriction in place of those four keywords (the loops build theirs once)."""
         if self.training:
             raise RuntimeError("metric_step: the model is in training mode (call .eval() first)")
-        restrict = None
-        if exclude_visited or allow is not None or split_revisits or near is not None:
-            restrict = (bool(exclude_visited), allow, bool(split_revisits), near)
+        r = restriction or Restriction(self.label_offset, exclude_visited, allow, split_revisits, near)
         with torch.no_grad():
-            self._metrics_in_head = (batched_data.y, acc, work, restrict)
-            try:
-                self(batched_data)
-            finally:
-                self._metrics_in_head = None
+            scores = self.poi_scores(self.encode(batched_data))
+            if r.active:
+                hist = r.hist(batched_data)
+                ops.rank_metrics_masked(scores, batched_data.y, acc, target_offset=-r.label_offset, allow=r.allow_for(hist),
+                                        hist=hist, hist_offset=r.label_offset, exclude_hist=r.exclude_visited,
+                                        split=r.split_revisits, work=work)
+            else:
+                ops.rank_metrics(scores, batched_data.y, acc, target_offset=-r.label_offset, work=work)
         return acc
 
-    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None, near=None):
+    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None, near=None, restriction=None):
         """The batch's top-k next POIs, best first, into ids [G, k] int64 / vals [G, k] f32 (k = ids.shape[1] <= ops.TOPK_MAX) on
         the device: the scores metric_step ranks (logits; log_softmax for toyotagraph) in ops.topk_rows' order, so equal scores
         list the lower POI first and `y in ids[:, :k]` is exactly the hit ACC@k counts.  ids are in batched_data.y's label space:
@@ -699,15 +658,17 @@ class Graphormer(nn.Module):
         trajectory's last node (node_name[-1]): for graphs made from sessions (data.SessionCollator, sessions_to_trajectories,
         gen_pickles.py) nodes are ordered by their last visit, so it is the last history check-in; a hand-made dict stores
         distinct POIs in the order given, where it need not be.  "any" -- within r of anywhere the user has been -- does not
-        depend on order."""
+        depend on order.
+
+        restriction: a prebuilt restriction.Restriction in place of those three keywords (the loops build theirs once)."""
         if self.training:
             raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
+        r = restriction or Restriction(self.label_offset, exclude_visited, allow, near=near)
         with torch.no_grad():
-            self._recommend_in_head = (ids, vals, work, bool(exclude_visited), allow, near)
-            try:
-                self(batched_data)
-            finally:
-                self._recommend_in_head = None
+            scores = self.poi_scores(self.encode(batched_data))
+            hist = r.hist(batched_data)
+            ops.topk_rows(scores, ids.shape[1], col_offset=r.label_offset, work=work, out=(ids, vals), allow=r.allow_for(hist),
+                          exclude=r.exclude(hist))
         return ids, vals
 
     def recommend(self, dataset, collator, k=20, exclude_visited=False, candidates=None, within_km=None, coords=None, near="last",

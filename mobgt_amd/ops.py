@@ -905,8 +905,8 @@ def target_rank(scores, target):
     return rank
 
 
-# (device, stream) -> work buffer of the ranking launches.  A buffer that is outgrown stays alive (_RANK_WORK_OLD): a captured
-# graph may still name it.
+# (family, device, stream) -> work buffer of the ranking / the top-k launches.  A buffer that is outgrown stays alive
+# (_RANK_WORK_OLD): a captured graph may still name it.
 _RANK_WORK, _RANK_WORK_OLD = {}, []
 
 
@@ -918,21 +918,34 @@ def rank_metrics_masked_work_bytes(G, V):
     return int(_lib.lib().mobgt_rank_metrics_masked_work_bytes(G, V))
 
 
-def _rank_work(device, G, V, work=None, nbytes=None):
-    n = rank_metrics_work_bytes(G, V) if nbytes is None else nbytes
+def _rank_work(device, n, work, who):
+    """The caller's `work` if it holds n bytes, else the grow-only buffer family `who` keeps for this (device, stream)"""
     if work is not None:
-        assert work.is_cuda and work.numel() * work.element_size() >= n, f"rank metrics: work buffer of {n} bytes needed"
+        assert work.is_cuda and work.numel() * work.element_size() >= n, f"{who}: work buffer of {n} bytes needed"
         return work
-    key = (device, torch.cuda.current_stream(device).stream_id)
+    key = (who, device, torch.cuda.current_stream(device).stream_id)
     buf = _RANK_WORK.get(key)
     if buf is None or buf.numel() < n:
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("mobgt rank metrics: no work buffer of this size on this stream yet -- pass `work` or run the call "
-                               "once eagerly before capturing it")
+            raise RuntimeError(f"{who}: no work buffer of this size on this stream yet -- pass `work` or run the call once eagerly "
+                               "before capturing it")
         if buf is not None:
             _RANK_WORK_OLD.append(buf)
         buf = _RANK_WORK[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
     return buf
+
+
+def _id_table(ids, G, who, name):
+    """A per-row id table (hist / exclude: [G, n] int32 / int64, 0 = padding) as the kernels take it: (tensor, dtype code, row
+    pitch, n); None: (None, I64, 0, 0).  `G`: the rows it must have (None: any); host tables are checked and passed through."""
+    if ids is None:
+        return None, I64, 0, 0
+    assert ids.dim() == 2 and G in (None, ids.shape[0]) and ids.dtype in (torch.int32, torch.int64), \
+        f"{who}: {name} = [{'G' if G is None else G}, n] int32 / int64 ids"
+    n = ids.shape[1]
+    if ids.is_cuda and n and (ids.stride(1) != 1 or ids.stride(0) < n):
+        ids = ids.contiguous()
+    return ids, _IT[ids.dtype], max(ids.stride(0), n), n
 
 
 def _check_acc(acc):
@@ -949,7 +962,7 @@ def rank_metrics(scores, target, acc, target_offset=0, work=None):
     target = target.reshape(-1).long().contiguous()
     G, V = scores.shape
     assert target.numel() >= G
-    work = _rank_work(scores.device, G, V, work)
+    work = _rank_work(scores.device, rank_metrics_work_bytes(G, V), work, "rank metrics")
     _lib.call("mobgt_rank_metrics", _p(scores), _p(target), int(target_offset), G, V, _p(acc), _p(work), _stream())
     return acc
 
@@ -977,9 +990,7 @@ def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=N
         f"rank_metrics_masked: acc = metrics.new_restricted_accumulator(device, split={bool(split)}), f64 [{S}, 11]"
     if allow is not None:
         _check_allow(allow, G, V, "rank_metrics_masked")
-    if hist is not None:
-        assert hist.dim() == 2 and hist.shape[0] == G and hist.dtype in (torch.int32, torch.int64), \
-            f"rank_metrics_masked: hist = [{G}, n] int32 / int64 ids"
+    hist, hist_dt, ld_h, n_h = _id_table(hist, G, "rank_metrics_masked", "hist")
     target = target.reshape(-1)
     assert target.numel() >= G
     if not (scores.is_cuda and scores.dtype == torch.float32):
@@ -992,22 +1003,15 @@ def rank_metrics_masked(scores, target, acc, target_offset=0, allow=None, hist=N
     ld_allow = 0
     if allow is not None:
         allow, ld_allow = _allow_on_device(allow, V, "rank_metrics_masked")
-    n_h, ld_h = 0, 0
-    if hist is not None:
-        assert hist.is_cuda, "rank_metrics_masked: hist on the device"
-        if hist.shape[1] and (hist.stride(1) != 1 or hist.stride(0) < hist.shape[1]):
-            hist = hist.contiguous()
-        n_h, ld_h = hist.shape[1], max(hist.stride(0), hist.shape[1])
-    work = _rank_work(scores.device, G, V, work, rank_metrics_masked_work_bytes(G, V))
+    assert hist is None or hist.is_cuda, "rank_metrics_masked: hist on the device"
+    work = _rank_work(scores.device, rank_metrics_masked_work_bytes(G, V), work, "rank metrics")
     flags = (RM_EXCLUDE_HIST if exclude_hist else 0) | (RM_SPLIT if split else 0)
     if ld_allow:
         _lib.call("mobgt_rank_metrics_masked_rows", _p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), ld_allow,
-                  _p(hist), _IT[hist.dtype] if hist is not None else I64, ld_h, n_h,
-                  hist_offset, flags, _p(acc), _p(work), _stream())
+                  _p(hist), hist_dt, ld_h, n_h, hist_offset, flags, _p(acc), _p(work), _stream())
         return acc
     _lib.call("mobgt_rank_metrics_masked", _p(scores.detach()), _p(target), int(target_offset), G, V, _p(allow), _p(hist),
-              _IT[hist.dtype] if hist is not None else I64, ld_h, n_h, hist_offset, flags,
-              _p(acc), _p(work), _stream())
+              hist_dt, ld_h, n_h, hist_offset, flags, _p(acc), _p(work), _stream())
     return acc
 
 
@@ -1030,14 +1034,13 @@ def skinny_linear_rank_metrics(x, weight, bias, target, acc, target_offset=0, wo
     target = target.reshape(-1)[:G].long().contiguous()
     assert target.numel() == G
     b = bias.detach().contiguous() if bias is not None else None
-    work = _rank_work(x.device, G, V, work)
+    work = _rank_work(x.device, rank_metrics_work_bytes(G, V), work, "rank metrics")
     _lib.call("mobgt_skinny_linear_rank_metrics", _p(x.detach()), _p(weight.detach()), _p(b), _p(target), int(target_offset),
               G, K, V, _p(acc), _p(work), _stream())
     return acc
 
 
 TOPK_MAX = 64                # the largest k mobgt_topk_rows takes
-_TOPK_WORK, _TOPK_WORK_OLD = {}, []
 
 
 def topk_work_bytes(G, V, k):
@@ -1154,8 +1157,9 @@ def near_words(pos, hist, hist_offset, chord2_max, mode="last", allow=None, out=
     the torch statement of this contract, which is the kernel's specification."""
     m = near_mode(mode)
     assert pos.dim() == 2 and pos.shape[1] == 4 and pos.dtype == torch.float32, "near_words: pos = pack_positions(...), f32 [V, 4]"
-    assert hist.dim() == 2 and hist.dtype in (torch.int32, torch.int64), "near_words: hist = [G, n] int32 / int64 ids"
-    V, (G, n) = pos.shape[0], hist.shape
+    assert hist is not None, "near_words: hist = [G, n] int32 / int64 ids"
+    hist, hist_dt, ld_h, n = _id_table(hist, None, "near_words", "hist")
+    V, G = pos.shape[0], hist.shape[0]
     W = (V + 31) // 32
     if allow is not None:
         assert allow.dtype == torch.int32 and allow.dim() == 1 and allow.numel() >= W, \
@@ -1172,15 +1176,13 @@ def near_words(pos, hist, hist_offset, chord2_max, mode="last", allow=None, out=
         return out
     _require_cuda(pos, hist)
     pos = pos.contiguous()
-    if n and (hist.stride(1) != 1 or hist.stride(0) < n):
-        hist = hist.contiguous()
     if allow is not None:
         assert allow.is_cuda and allow.is_contiguous(), "near_words: allow words on the device, contiguous"
     if out is None:
         out = torch.empty(G, W, dtype=torch.int32, device=pos.device)
     if G == 0:
         return out
-    _lib.call("mobgt_near_words", _p(pos), V, _p(hist), _IT[hist.dtype], max(hist.stride(0), n), n, int(hist_offset), m,
+    _lib.call("mobgt_near_words", _p(pos), V, _p(hist), hist_dt, ld_h, n, int(hist_offset), m,
               chord2_max, _p(allow), _p(out), out.stride(0), G, _stream())
     return out
 
@@ -1256,7 +1258,7 @@ def topk_rows(scores, k, col_offset=0, work=None, out=None, allow=None, exclude=
     ids, vals = out = _topk_out(scores, G, k, out)
     if G == 0:
         return out
-    work = _topk_work(scores, G, V, k, work)
+    work = _rank_work(scores.device, topk_work_bytes(G, V, k), work, "topk_rows")
     _lib.call("mobgt_topk_rows", _p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(ids), _p(vals), _p(work),
               _stream())
     return out
@@ -1266,9 +1268,7 @@ def _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude, exclude_
     G, V = scores.shape
     if allow is not None:
         _check_allow(allow, G, V, "topk_rows")
-    if exclude is not None:
-        assert exclude.dim() == 2 and exclude.shape[0] == G and exclude.dtype in (torch.int32, torch.int64), \
-            f"topk_rows: exclude = [{G}, n] int32 / int64 ids"
+    exclude, ex_dt, ld_ex, n_ex = _id_table(exclude, G, "topk_rows", "exclude")
     if not (scores.is_cuda and scores.dtype == torch.float32):
         # the contract in torch: the stable descending sort, then its candidates moved to the front in that order
         sv, si = torch.sort(scores, dim=1, descending=True, stable=True)
@@ -1287,24 +1287,17 @@ def _topk_rows_masked(scores, k, col_offset, work, out, allow, exclude, exclude_
     ld_allow = 0
     if allow is not None:
         allow, ld_allow = _allow_on_device(allow, V, "topk_rows")
-    n_ex, ld_ex = 0, 0
-    if exclude is not None:
-        assert exclude.is_cuda, "topk_rows: exclude on the device"
-        if exclude.shape[1] and (exclude.stride(1) != 1 or exclude.stride(0) < exclude.shape[1]):
-            exclude = exclude.contiguous()
-        n_ex, ld_ex = exclude.shape[1], max(exclude.stride(0), exclude.shape[1])
+    assert exclude is None or exclude.is_cuda, "topk_rows: exclude on the device"
     ids, vals = out = _topk_out(scores, G, k, out)
     if G == 0:
         return out
-    work = _topk_work(scores, G, V, k, work)
+    work = _rank_work(scores.device, topk_work_bytes(G, V, k), work, "topk_rows")
     if ld_allow:
         _lib.call("mobgt_topk_rows_masked_rows", _p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
-                  ld_allow, _p(exclude), _IT[exclude.dtype] if exclude is not None else I64,
-                  ld_ex, n_ex, int(exclude_offset), _p(ids), _p(vals), _p(work), _stream())
+                  ld_allow, _p(exclude), ex_dt, ld_ex, n_ex, int(exclude_offset), _p(ids), _p(vals), _p(work), _stream())
         return out
     _lib.call("mobgt_topk_rows_masked", _p(scores.detach()), scores.stride(0), G, V, k, int(col_offset), _p(allow),
-              _p(exclude), _IT[exclude.dtype] if exclude is not None else I64, ld_ex, n_ex,
-              int(exclude_offset), _p(ids), _p(vals), _p(work), _stream())
+              _p(exclude), ex_dt, ld_ex, n_ex, int(exclude_offset), _p(ids), _p(vals), _p(work), _stream())
     return out
 
 
@@ -1315,23 +1308,6 @@ def _topk_out(scores, G, k, out):
     assert ids.is_cuda and vals.is_cuda and ids.dtype == torch.int64 and vals.dtype == torch.float32 and ids.is_contiguous() \
         and vals.is_contiguous() and ids.shape == (G, k) and vals.shape == (G, k), "topk_rows: out = ([G, k] int64, [G, k] f32)"
     return out
-
-
-def _topk_work(scores, G, V, k, work):
-    n = topk_work_bytes(G, V, k)
-    if work is not None:
-        assert work.is_cuda and work.numel() * work.element_size() >= n, f"topk_rows: work buffer of {n} bytes needed"
-        return work
-    key = (scores.device, torch.cuda.current_stream(scores.device).stream_id)
-    work = _TOPK_WORK.get(key)
-    if work is None or work.numel() < n:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("topk_rows: no work buffer of this size on this stream yet -- pass `work` or run the call "
-                               "once eagerly before capturing it")
-        if work is not None:
-            _TOPK_WORK_OLD.append(work)           # (a captured graph may still name it)
-        work = _TOPK_WORK[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=scores.device)
-    return work
 
 
 def node_index(x, time_normal, poi2cat, rows_only, in_degree=None, out_degree=None):

@@ -23,6 +23,7 @@ import torch
 import torch.distributed as dist
 
 from . import forms, ops
+from .restriction import Restriction
 from .step_state import STEP
 from .step_graphs import Entry, StepGraphs, group_key
 from .model import sync_external_shadows
@@ -1299,122 +1300,54 @@ class EpochLoop(_StagedBatches):
         return dict(steps=steps, graphs=len(self.slots), sample_ids=seen)
 
 
-def _pack_candidates(model, candidates, V, device):
-    """EvalLoop's / PredictLoop's candidate set: POI ids in y's label space -> ops.pack_allow words on the device, packed once
-    so that a loop's graphs read them at one fixed address (None: no candidate set)."""
-    if candidates is None:
-        return None
-    offset = 0 if getattr(model, "dataset_name", None) == "toyotagraph" else 1          # (recommend_step's label space)
-    return ops.pack_allow(torch.as_tensor(candidates).to(device), V, offset)
+class _FrozenModelLoop(_StagedBatches):
+    """What EvalLoop and PredictLoop share on top of the staged batches: the eval loader's order, the model held in eval mode
+    with its weights refreshed once and frozen while a run lasts, and per (G, bucket, forms.on("safe_forms")) ONE captured graph
+    of the loop's step -- `_step(slot, warm)`, which each loop supplies -- warmed once on the capture stream and then replayed.
+    `use_graph=False` runs the step eagerly, and so do buckets whose collate needs torch ops."""
 
-
-def _near_args(collator, within_km, coords, near):
-    """The radius restriction of EvalLoop / PredictLoop, checked on the host before anything is allocated:
-    None, or (coordinate table, whether it is in radians, chord2_max, mode)."""
-    ops.near_mode(near)                                               # (a bad mode string is refused here, on the host)
-    mode = near
-    if within_km is None:
-        return None
-    chord2_max = ops.chord2_of_km(within_km)
-    if coords is not None:
-        return torch.as_tensor(coords), False, chord2_max, mode
-    if getattr(collator, "coords", None) is None:
-        raise ValueError("within_km: no POI coordinates -- pass coords=[P + 1, 2] lat / lon in degrees (row 0 the pad POI), or "
-                         "use a collator built with coords=")
-    return collator.coords, True, chord2_max, mode                    # (DeviceCollator keeps radians)
-
-
-def _near_state(model, args, V, batch_size, device):
-    """-> Graphormer.metric_step's / recommend_step's near=(pos, chord2_max, mode, words): the positions packed once and one
-    [batch_size, W] words buffer, so that a loop's graphs build and read the rows' candidate words at fixed addresses."""
-    if args is None:
-        return None
-    table, radians, chord2_max, mode = args
-    offset = 0 if getattr(model, "dataset_name", None) == "toyotagraph" else 1          # (recommend_step's label space)
-    pos = ops.pack_positions(table.to(device), V, offset, radians=radians)
-    words = torch.zeros(batch_size, (V + 31) // 32, dtype=torch.int32, device=device)
-    return pos, chord2_max, mode, words
-
-
-class EvalLoop(_StagedBatches):
-    """The validation / test loop (Lightning's `trainer.validate` / `trainer.test` over the reference's eval DataLoader,
-    entry.py:120-161, with test_epoch_end's bookkeeping, model_fqandtoyo.py:1484-1597) on the device data path of EpochLoop.
-
-    * order: the reference's eval loader -- no shuffle, consecutive runs of `batch_size`, drop_last=False; with `world` > 1 the
-      non-shuffling DistributedSampler (data.shard_indices, wrap-around duplicates included).  Batches are never regrouped by
-      length: which rows share a batch decides where get_acc's stop at the first target 0 applies;
-    * shapes and staging: EpochLoop's buckets (one static batch per (G, bucket)), pinned buffers, device collate on the copy
-      stream, host index checks; trajectories over `collator.max_node` are dropped;
-    * per (G, bucket, forms.on("safe_forms")) ONE captured graph = eval forward + the fused classifier-ranking launches
-      (Graphormer.metric_step) adding into ONE f64 accumulator; `use_graph=False` runs the same launches eagerly, and so do
-      collators whose finish needs torch ops (coordinate bins by coords= + bin_edges=, S-BIG's default: see _launch; a
-      collator built with pair_bins= is captured like a bin-table one);
-    * `run()` reads the accumulator once (after one all-reduce of all its doubles when world > 1: every rank's samples pooled).
-    The weights are read as they are when `run()` starts (bf16 shadows and MFMA packs re-derived there, outside any graph), so an
-    evaluation between training epochs sees the current model; it leaves no state behind that the trainer's next step reads.
-
-    Restricted and split evaluation (Graphormer.metric_step's restricted form, ops.rank_metrics_masked) measures the lists
-    PredictLoop returns with the same restriction, kept for the loop's lifetime: exclude_visited ranks each target among the
-    POIs its trajectory has not visited, candidates (POI ids in y's label space, packed once here) among those only.
-    split_revisits also reports the rows whose target is a new POI and those whose target is a revisit.  run() then returns
-    metrics.finalize_restricted's dict: today's keys, "n", "reachable" (targets that can be listed at all) and, with the split,
-    "new" / "revisit" dicts of the same keys.  The defaults run today's launches and return today's dict.
-
-    within_km=r ranks each target among the POIs within r km of the row's anchor (ops.near_words inside the captured graph, then
-    the per-row form of ops.rank_metrics_masked); it combines with the other restrictions.  coords: [P + 1, 2] lat / lon in
-    degrees, row 0 the pad POI (default: the collator's coords; neither: ValueError).  near="last": the anchor is the
-    trajectory's last node, node_name[-1] -- the last history check-in for a SessionDataset and for dicts made from sessions
-    (nodes ordered by last visit); a hand-made dict stores distinct POIs in the order given, where the last node need not be the
-    last check-in; near="any": within r of any POI of the trajectory, which does not depend on order.  A target outside its
-    row's radius is unreachable and counts in n only.
-
-    dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator -- the
-    loops reach the input form through the collator only (nodes_of, keeps, lengths_of, new_stage, stage_host, limit_violation,
-    upload), and the collate through can_finish_into, finish_into and batch_from_views on the copy stream, or finish inside
-    the step."""
-
-    def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
-                 side_collate=True, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
-                 near="last"):
-        from . import metrics
-        if not hasattr(model, "metric_step"):
-            raise TypeError("EvalLoop: the model has no metric_step (the fq model, model_fqandtoyo.Graphormer)")
-        near_args = _near_args(collator, within_km, coords, near)
-        self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
-        self.captures = 0                                   # graphs captured so far (a replayed run captures none)
-        V = model.out_proj.out_features
-        self.exclude_visited, self.split_revisits = bool(exclude_visited), bool(split_revisits)
-        self.allow = _pack_candidates(model, candidates, V, self.device)
-        self.near = _near_state(model, near_args, V, self.batch_size, self.device)
-        self.restricted = self.exclude_visited or self.allow is not None or self.split_revisits or self.near is not None
-        if self.restricted:
-            self.acc = metrics.new_restricted_accumulator(self.device, self.split_revisits)
-            self._scratch = metrics.new_restricted_accumulator(self.device, self.split_revisits)     # warm-ups count nowhere
-            self.work = torch.empty(ops.rank_metrics_masked_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
-            return
-        self.acc = metrics.new_accumulator(self.device)
-        self._scratch = metrics.new_accumulator(self.device)                          # warm-up passes count nowhere
-        self.work = torch.empty(ops.rank_metrics_work_bytes(self.batch_size, V), dtype=torch.uint8, device=self.device)
-
-    def _setup(self, model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate):
+    def __init__(self, model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate):
         super().__init__(model, collator, dataset, batch_size, buckets, rank, world, side_collate)
         self.stream = torch.cuda.Stream(device=self.device) if use_graph else None     # warm-ups and captures
         self.use_graph = bool(use_graph)
         self.graphs, self._graph_ptrs = {}, None
+        self.captures = 0                                   # graphs captured so far (a replayed run captures none)
 
-    def batches(self):
+    near = property(lambda self: self.restriction.near)             # (the loop's restriction is one object; these two parts of it
+    allow = property(lambda self: self.restriction.allow)           #  stay readable on the loop)
+
+    def batches(self, max_batches=None):
         from .data import shard_indices
         idx = shard_indices(len(self.dataset), self.rank, self.world, shuffle=False)
         B = self.batch_size
-        return [idx[i:i + B] for i in range(0, len(idx), B)]
+        return [idx[i:i + B] for i in range(0, len(idx), B)][:max_batches]
 
-    def _forward(self, batch, acc):
-        b = self._collated(batch)
-        if self.restricted:
-            self.model.metric_step(b, acc, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow,
-                                   split_revisits=self.split_revisits, near=self.near)
+    def _step(self, slot, warm):
+        """The loop's launches on the bucket's static batch; warm: the pass before a capture, whose results count nowhere."""
+        raise NotImplementedError
+
+    def _launch(self, slot, st):
+        cur = self._hand_over(slot, st)
+        if not self.use_graph or not slot["side"]:
+            # Buckets whose collate needs torch ops (coords= + bin_edges=: S-BIG's default collator) run eagerly.  Captured with the collate inside, the
+            # replay took 130 ms per 16 x 784 batch against 13 ms eager: inside the replayed graph the SPD kernel's split form
+            # (workgroups that wait for each other, csrc/spd.hip) gave up on every call and its one-workgroup-per-graph redo
+            # pass ran (fw_kernel: 75 ms per call, rocprofv3).  Why it gives up only there is not known.
+            self._step(slot, warm=False)
             return
-        self.model.metric_step(b, acc, work=self.work)
+        key = (slot["layout"].G, slot["layout"].N, forms.on("safe_forms"))
+        g = self.graphs.get(key)
+        if g is None:
+            self.stream.wait_stream(cur)
+            with torch.cuda.stream(self.stream):
+                self._step(slot, warm=True)                                          # allocator, lazy initialisations
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self.stream):
+                self._step(slot, warm=False)
+            cur.wait_stream(self.stream)
+            self.graphs[key] = g
+            self.captures += 1
+        g.replay()
 
     def _weights_ptrs(self):
         """Addresses a captured eval forward reads besides its batch: parameters, bf16 shadows, MFMA packs, the dropout seed.  A
@@ -1426,29 +1359,6 @@ class EvalLoop(_StagedBatches):
                 ptrs += [x.data_ptr() for x in t] if t is not None else [0]
         ptrs += [m.seed_dev.data_ptr() for m in self.model.modules() if getattr(m, "seed_dev", None) is not None]
         return tuple(ptrs)
-
-    def _launch(self, slot, st):
-        cur = self._hand_over(slot, st)
-        if not self.use_graph or not slot["side"]:
-            # Buckets whose collate needs torch ops (coords= + bin_edges=: S-BIG's default collator) run eagerly.  Captured with the collate inside, the
-            # replay took 130 ms per 16 x 784 batch against 13 ms eager: inside the replayed graph the SPD kernel's split form
-            # (workgroups that wait for each other, csrc/spd.hip) gave up on every call and its one-workgroup-per-graph redo
-            # pass ran (fw_kernel: 75 ms per call, rocprofv3).  Why it gives up only there is not known.
-            self._forward(slot["batch"], self.acc)
-            return
-        key = (slot["layout"].G, slot["layout"].N, forms.on("safe_forms"))
-        g = self.graphs.get(key)
-        if g is None:
-            self.stream.wait_stream(cur)
-            with torch.cuda.stream(self.stream):
-                self._forward(slot["batch"], self._scratch)                          # allocator, lazy initialisations
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self.stream):
-                self._forward(slot["batch"], self.acc)
-            cur.wait_stream(self.stream)
-            self.graphs[key] = g
-            self.captures += 1
-        g.replay()
 
     def _refresh_weights(self):
         """bf16 shadows and MFMA packs from the current fp32 weights, once, outside any graph (the captured forwards then skip
@@ -1494,15 +1404,76 @@ class EvalLoop(_StagedBatches):
         if left:
             raise RuntimeError(f"{type(self).__name__}: the evaluation left parked work behind {left}")
 
+
+class EvalLoop(_FrozenModelLoop):
+    """The validation / test loop (Lightning's `trainer.validate` / `trainer.test` over the reference's eval DataLoader,
+    entry.py:120-161, with test_epoch_end's bookkeeping, model_fqandtoyo.py:1484-1597) on the device data path of EpochLoop.
+
+    * order: the reference's eval loader -- no shuffle, consecutive runs of `batch_size`, drop_last=False; with `world` > 1 the
+      non-shuffling DistributedSampler (data.shard_indices, wrap-around duplicates included).  Batches are never regrouped by
+      length: which rows share a batch decides where get_acc's stop at the first target 0 applies;
+    * shapes and staging: EpochLoop's buckets (one static batch per (G, bucket)), pinned buffers, device collate on the copy
+      stream, host index checks; trajectories over `collator.max_node` are dropped;
+    * per (G, bucket, forms.on("safe_forms")) ONE captured graph = eval forward + the fused classifier-ranking launches
+      (Graphormer.metric_step) adding into ONE f64 accumulator; `use_graph=False` runs the same launches eagerly, and so do
+      collators whose finish needs torch ops (coordinate bins by coords= + bin_edges=, S-BIG's default: see _launch; a
+      collator built with pair_bins= is captured like a bin-table one);
+    * `run()` reads the accumulator once (after one all-reduce of all its doubles when world > 1: every rank's samples pooled).
+    The weights are read as they are when `run()` starts (bf16 shadows and MFMA packs re-derived there, outside any graph), so an
+    evaluation between training epochs sees the current model; it leaves no state behind that the trainer's next step reads.
+
+    Restricted and split evaluation (Graphormer.metric_step's restricted form, ops.rank_metrics_masked) measures the lists
+    PredictLoop returns with the same restriction, kept for the loop's lifetime: exclude_visited ranks each target among the
+    POIs its trajectory has not visited, candidates (POI ids in y's label space, packed once here) among those only.
+    split_revisits also reports the rows whose target is a new POI and those whose target is a revisit.  run() then returns
+    metrics.finalize_restricted's dict: today's keys, "n", "reachable" (targets that can be listed at all) and, with the split,
+    "new" / "revisit" dicts of the same keys.  The defaults run today's launches and return today's dict.
+
+    within_km=r ranks each target among the POIs within r km of the row's anchor (ops.near_words inside the captured graph, then
+    the per-row form of ops.rank_metrics_masked); it combines with the other restrictions.  coords: [P + 1, 2] lat / lon in
+    degrees, row 0 the pad POI (default: the collator's coords; neither: ValueError).  near="last": the anchor is the
+    trajectory's last node, node_name[-1] -- the last history check-in for a SessionDataset and for dicts made from sessions
+    (nodes ordered by last visit); a hand-made dict stores distinct POIs in the order given, where the last node need not be the
+    last check-in; near="any": within r of any POI of the trajectory, which does not depend on order.  A target outside its
+    row's radius is unreachable and counts in n only.
+
+    dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator -- the
+    loops reach the input form through the collator only (nodes_of, keeps, lengths_of, new_stage, stage_host, limit_violation,
+    upload), and the collate through can_finish_into, finish_into and batch_from_views on the copy stream, or finish inside
+    the step."""
+
+    def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
+                 side_collate=True, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
+                 near="last"):
+        from . import metrics
+        if not hasattr(model, "metric_step"):
+            raise TypeError("EvalLoop: the model has no metric_step (the fq model, model_fqandtoyo.Graphormer)")
+        radius = Restriction.radius(collator, within_km, coords, near)
+        super().__init__(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
+        V = model.out_proj.out_features
+        r = self.restriction = Restriction.on_device(model.label_offset, V, self.batch_size, self.device, exclude_visited,
+                                                     candidates, split_revisits, radius)
+        if r.active:
+            new_acc = lambda: metrics.new_restricted_accumulator(self.device, r.split_revisits)
+            nbytes = ops.rank_metrics_masked_work_bytes(self.batch_size, V)
+        else:
+            new_acc = lambda: metrics.new_accumulator(self.device)
+            nbytes = ops.rank_metrics_work_bytes(self.batch_size, V)
+        self.acc, self._scratch = new_acc(), new_acc()      # (warm-up passes count in the scratch one, that is nowhere)
+        self.work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    restricted = property(lambda self: self.restriction.active)
+
+    def _step(self, slot, warm):
+        self.model.metric_step(self._collated(slot["batch"]), self._scratch if warm else self.acc, work=self.work,
+                               restriction=self.restriction)
+
     def run(self, max_batches=None):
         """One pass over this rank's part of the split -> dict of metrics.evaluate_outputs' keys + "n" (samples counted)."""
         from . import metrics
-        batches = self.batches()
-        if max_batches is not None:
-            batches = batches[:max_batches]
         with self._evaluating():
             self.acc.zero_()
-            for _ in self._pipeline(batches):
+            for _ in self._pipeline(self.batches(max_batches)):
                 pass
             if self.world > 1 and dist.is_available() and dist.is_initialized():
                 if dist.get_backend() == "gloo":
@@ -1511,11 +1482,10 @@ class EvalLoop(_StagedBatches):
                     self.acc.copy_(host)
                 else:
                     dist.all_reduce(self.acc)
-            out = metrics.finalize_restricted(self.acc) if self.restricted else metrics.finalize(self.acc)    # the one host read
-        return out
+            return (metrics.finalize_restricted if self.restriction.active else metrics.finalize)(self.acc)    # the one host read
 
 
-class PredictLoop(EvalLoop):
+class PredictLoop(_FrozenModelLoop):
     """Top-k next-POI recommendations over a whole split (Graphormer.recommend_step) on EvalLoop's device data path: the eval
     loader's order and sharding, EpochLoop's buckets and staging, one captured graph per (G, bucket, forms.on("safe_forms")) -- eager
     for collators whose finish needs torch ops (coords= + bin_edges=, S-BIG's default) -- and the weights as they are when run() starts.
@@ -1537,42 +1507,32 @@ class PredictLoop(EvalLoop):
                  side_collate=True, exclude_visited=False, candidates=None, within_km=None, coords=None, near="last"):
         if not hasattr(model, "recommend_step"):
             raise TypeError("PredictLoop: the model has no recommend_step (the fq model, model_fqandtoyo.Graphormer)")
-        near_args = _near_args(collator, within_km, coords, near)
+        radius = Restriction.radius(collator, within_km, coords, near)
         V = model.out_proj.out_features
         self.k = int(k)
         if not 1 <= self.k <= min(ops.TOPK_MAX, V):
             raise ValueError(f"PredictLoop: k = {k} outside [1, {min(ops.TOPK_MAX, V)}]")
-        self._setup(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
-        self.exclude_visited = bool(exclude_visited)
-        self.allow = _pack_candidates(model, candidates, V, self.device)
-        self.near = _near_state(model, near_args, V, self.batch_size, self.device)
-        self.captures = 0
-        self.acc = self._scratch = None                     # (EvalLoop._launch passes them to _forward, which ignores them)
+        super().__init__(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
+        self.restriction = Restriction.on_device(model.label_offset, V, self.batch_size, self.device, exclude_visited, candidates,
+                                                 radius=radius)
         self.outs = {}                                      # (G, N) -> the [G, k] buffers its graphs write
-        self._out = None
         self.work = torch.empty(ops.topk_work_bytes(self.batch_size, V, self.k), dtype=torch.uint8, device=self.device)
 
-    def _forward(self, batch, _acc):
-        b = self._collated(batch)
-        self.model.recommend_step(b, *self._out, work=self.work, exclude_visited=self.exclude_visited, allow=self.allow,
-                                  near=self.near)
-
-    def _launch(self, slot, st):
+    def _out(self, slot):
         key = (slot["layout"].G, slot["layout"].N)
         if key not in self.outs:
             G = key[0]
             self.outs[key] = (torch.empty(G, self.k, dtype=torch.int64, device=self.device),
                               torch.empty(G, self.k, dtype=torch.float32, device=self.device))
-        self._out = self.outs[key]
-        super()._launch(slot, st)
-        return self._out
+        return self.outs[key]
+
+    def _step(self, slot, warm):
+        self.model.recommend_step(self._collated(slot["batch"]), *self._out(slot), work=self.work, restriction=self.restriction)
 
     def run(self, max_batches=None):
         """One pass over this rank's part of the split -> (sample_index [n] int64, ids [n, k] int64, vals [n, k] f32), device
         tensors in batch order, no host read."""
-        batches = self.batches()
-        if max_batches is not None:
-            batches = batches[:max_batches]
+        batches = self.batches(max_batches)
         flat = [i for b in batches for i in b]
         sample_index = torch.tensor(flat, dtype=torch.int64).to(self.device)
         ids = torch.full((len(flat), self.k), -1, dtype=torch.int64, device=self.device)
@@ -1581,7 +1541,8 @@ class PredictLoop(EvalLoop):
 
         def launch(j, slot, st):
             """Rank batch j, then -- enqueued before the next batch is staged -- its lists into the result's rows."""
-            bi, bv = self._launch(slot, st)
+            self._launch(slot, st)
+            bi, bv = self._out(slot)
             rows = [starts[j] + i for i, t in enumerate(batches[j]) if self.collator.keeps(self.dataset[t])]
             r = 0
             while r < len(rows):                         # runs of kept rows (one run unless a trajectory was dropped)

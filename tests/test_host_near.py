@@ -246,20 +246,22 @@ def test_two_dimensional_allow_in_restricted_sums():
 def test_loop_state_from_the_collators_radians_table(city):
     """coords=None takes the collator's table, which DeviceCollator keeps in radians: the packed positions are those of the
     degrees table, bit for bit, in both label spaces"""
-    from mobgt_amd.train import _near_args, _near_state
+    from mobgt_amd.restriction import Restriction
     uni, c, _ = city
     coll = SimpleNamespace(coords=torch.from_numpy(np.radians(c)))          # (what DeviceCollator(coords=c) stores)
     for name, offset in (("toyotagraph", 0), ("foursquaregraph", 1)):
-        model = SimpleNamespace(dataset_name=name)
         V = uni.P + 1 - offset
-        a = _near_state(model, _near_args(coll, 2.0, None, "any"), V, 16, "cpu")
-        b = _near_state(model, _near_args(SimpleNamespace(coords=None), 2.0, c, "any"), V, 16, "cpu")
+        a = Restriction.on_device(offset, V, 16, "cpu", radius=Restriction.radius(coll, 2.0, None, "any"))
+        b = Restriction.on_device(offset, V, 16, "cpu", radius=Restriction.radius(SimpleNamespace(coords=None), 2.0, c, "any"))
         want = ops.pack_positions(torch.from_numpy(c), V, offset)
-        for pos, chord2_max, mode, words in (a, b):
+        for r in (a, b):
+            pos, chord2_max, mode, words = r.near
             assert torch.equal(pos.view(torch.int32), want.view(torch.int32)), name
             assert chord2_max == ops.chord2_of_km(2.0) and mode == "any"
             assert words.shape == (16, (V + 31) // 32) and words.dtype == torch.int32
-    assert _near_args(coll, None, None, "last") is None
+            assert r.label_offset == offset and r.active and r.allow is None
+    assert Restriction.radius(coll, None, None, "last") is None
+    assert Restriction.on_device(1, 40, 16, "cpu", radius=None).near is None
 
 
 def test_argument_errors():
