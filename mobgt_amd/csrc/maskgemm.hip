@@ -542,6 +542,8 @@ extern "C" int mobgt_mask_gemm(const uint32_t* mask, int64_t ld_mask_words, cons
     // (N = 16, measured at M = K = 7856: 64 rows x 16 waves 14.5 us, 32 rows x 16 waves 11.9, 32 x 8 waves 12.1, 16 x 16 19.4)
     if (N == 16) hipLaunchKernelGGL((mask_gemm_kernel<1, 16, 2>), dim3((M + 31) / 32), dim3(1024), 0, st, p);
     else if (N == 32) hipLaunchKernelGGL((mask_gemm_kernel<2, 16, 2>), dim3((M + 31) / 32), dim3(1024), 0, st, p);
+    // (N = 48 has its own three-block form: the operand buffer holds N rows, and the four-block kernel would load rows 48..63)
+    else if (N == 48) hipLaunchKernelGGL((mask_gemm_kernel<3, 8, 2>), dim3((M + 31) / 32), dim3(512), 0, st, p);
     else hipLaunchKernelGGL((mask_gemm_kernel<4, 8, 2>), dim3((M + 31) / 32), dim3(512), 0, st, p);
     return (int)hipGetLastError();
 }

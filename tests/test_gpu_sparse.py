@@ -160,13 +160,14 @@ def test_mask_gemm_matches_the_dense_normalised_adjacency():
         dense = torch.from_numpy(calculate_laplacian_matrix(uni.graph_dist)).float().to(DEV)
         adj = MaskAdj(*[t.to(DEV) for t in MaskAdj.from_dense01(uni.graph_dist)])
         g = torch.Generator().manual_seed(P)
-        for N in (16, 64):
+        dense01 = torch.from_numpy(np.asarray(uni.graph_dist) + np.eye(P)).float().to(DEV)
+        for N in (16, 32, 48, 64):
             x = torch.randn(P, N, generator=g).to(DEV)
             xr = x.bfloat16().float()
             np.testing.assert_allclose(mask_gemm(adj, x).cpu().numpy(), (dense @ xr).cpu().numpy(), rtol=1e-4, atol=1e-5)
-            want_t = dense.t() @ (x * 1.0)                      # (the kernel scales the operand's rows BEFORE rounding)
+            want_t = dense01.t() @ (x * adj.scale[:, None]).bfloat16().float()     # (the operand's rows are scaled BEFORE rounding)
             got_t = mask_gemm(adj, x, transposed=True)
-            np.testing.assert_allclose(got_t.cpu().numpy(), want_t.cpu().numpy(), rtol=2e-2, atol=2e-2 * float(want_t.abs().max()))
+            np.testing.assert_allclose(got_t.cpu().numpy(), want_t.cpu().numpy(), rtol=1e-4, atol=1e-5)
         x = torch.randn(P, 16, generator=g).to(DEV)
         w = (torch.randn(16, 64, generator=g) * 0.2).to(DEV)
         b = torch.randn(64, generator=g).to(DEV)
