@@ -512,6 +512,41 @@ class SessionDataset:
         self.n = np.asarray(n, dtype=np.int32)
         self.mult = np.asarray(mult, dtype=np.int32)
 
+    @classmethod
+    def from_packed(cls, seq, offsets, users, n, mult):
+        """The dataset of arrays that are packed already (checkins.sessionize builds them on the device; the constructor's loop
+        over sessions would not do for 10^5 of them): validated vectorised, stored as they come.  seq [M, 3] int32, offsets
+        [S + 1] ascending from 0 to M with at least two rows per session, users [S], n / mult [S] as the constructor computes
+        them (1 <= n, mult <= history rows; taken on trust beyond that)."""
+        seq, offsets, users, n, mult = (np.asarray(a) for a in (seq, offsets, users, n, mult))
+        for name, a in (("seq", seq), ("offsets", offsets), ("users", users), ("n", n), ("mult", mult)):
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"SessionDataset.from_packed: {name} must be integers, got {a.dtype}")
+        if seq.ndim != 2 or seq.shape[1] != 3:
+            raise ValueError(f"SessionDataset.from_packed: seq must be [M, 3] rows of (poi, time slot, category), got shape {seq.shape}")
+        if seq.size and (seq.min() < np.iinfo(np.int32).min or seq.max() > np.iinfo(np.int32).max):
+            raise ValueError("SessionDataset.from_packed: a value of seq does not fit int32")
+        S = len(users)
+        if offsets.shape != (S + 1,) or users.ndim != 1 or n.shape != (S,) or mult.shape != (S,):
+            raise ValueError(f"SessionDataset.from_packed: {S} users need offsets [{S + 1}], n [{S}] and mult [{S}], got "
+                             f"{offsets.shape}, {n.shape}, {mult.shape}")
+        lengths = np.diff(offsets)
+        if int(offsets[0]) != 0 or int(offsets[-1]) != seq.shape[0]:
+            raise ValueError(f"SessionDataset.from_packed: offsets run from {int(offsets[0])} to {int(offsets[-1])}, seq has {seq.shape[0]} rows")
+        if S and lengths.min() < 2:
+            s = int(np.argmax(lengths < 2))
+            raise ValueError(f"session {s} has {int(lengths[s])} check-in(s): a history of at least one and a target are needed")
+        if S and ((n < 1) | (n > lengths - 1) | (mult < 1) | (mult > lengths - 1)).any():
+            s = int(np.argmax((n < 1) | (n > lengths - 1) | (mult < 1) | (mult > lengths - 1)))
+            raise ValueError(f"session {s}: n = {int(n[s])} / mult = {int(mult[s])} for a history of {int(lengths[s]) - 1} check-in(s)")
+        self = cls.__new__(cls)
+        self.seq = np.ascontiguousarray(seq, dtype=np.int32)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        self.users = np.ascontiguousarray(users, dtype=np.int64)
+        self.n = np.ascontiguousarray(n, dtype=np.int32)
+        self.mult = np.ascontiguousarray(mult, dtype=np.int32)
+        return self
+
     def __len__(self):
         return len(self.users)
 
@@ -709,3 +744,7 @@ def _slot_of(t):
 # ---- the POI table and the transition graphs from sessions (universe.py) ------------------------------------------------------------
 from .universe import (BuiltUniverse, TransitionGraph, UniverseCounts, build_universe, first_seen_ids, universe_counts,  # noqa: E402,F401
                        universe_counts_host)
+
+
+# ---- sessions from a raw check-in log (checkins.py) ---------------------------------------------------------------------------------
+from .checkins import Sessionized, sessionize, sessionize_host  # noqa: E402,F401
