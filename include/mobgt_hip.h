@@ -301,14 +301,17 @@ int mobgt_node_index(const void* x, int x_dtype, int64_t xs_g, int64_t xs_n, con
 
 /* nn.Linear on a handful of rows (G <= 16, K <= 512, K % 4 == 0; f32): y [G,V] = x [G,K] w[V,K]^T + b[V] -- the
  * classifier head out_proj on the graph tokens (model_fqandtoyo.py:1394) -- and its backward: dx [G,K] (or NULL),
- * dw [V,K] and db [V] (or NULL), all OVERWRITTEN.  Each product streams w / writes dw exactly once. */
+ * dw [V,K] and db [V] (or NULL), all OVERWRITTEN.  Each product streams w / writes dw exactly once.  db is a by-product of the
+ * dw launch: db without dw is refused (MOBGT_EBADDIM).  fwd: x, w 16-byte aligned (MOBGT_EALIGN). */
 int mobgt_skinny_linear_fwd(const float* x, const float* w, const float* b, float* y, int G, int K, int V, void* stream);
 int mobgt_skinny_linear_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, int G, int K,
                             int V, void* stream);
-/* dx = dy @ w alone, on the matrix cores (csrc/skinny.hip): dx [G,K] f32 must be ZERO on entry (f32 atomics); K % 16 == 0. */
+/* dx = dy @ w alone, on the matrix cores (csrc/skinny.hip): dx [G,K] f32 (not NULL) must be ZERO on entry (f32 atomics);
+ * K % 16 == 0; w 16-byte aligned (MOBGT_EALIGN). */
 int mobgt_skinny_linear_dx(const float* dy, const float* w, float* dx, int G, int K, int V, void* stream);
 /* Both gradients of the skinny Linear in one launch (csrc/skinny.hip): dx = dy @ w [G,K] (ZERO on entry: f32 atomics;
- * K % 16 == 0), dw = dy^T x [V,K] (overwritten), db = column sums of dy [V] or NULL. */
+ * K % 16 == 0), dw = dy^T x [V,K] (overwritten), db = column sums of dy [V] or NULL.  dx, dw not NULL; w 16-byte aligned
+ * (MOBGT_EALIGN). */
 int mobgt_skinny_linear_bwd_both(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db,
                                  int G, int K, int V, void* stream);
 /* logits = x w^T + b [G,V] alone on the matrix cores, one pass over w (csrc/skinny.hip; the kernel of mobgt_skinny_linear_gtl
@@ -317,7 +320,18 @@ int mobgt_skinny_linear_fwd_mfma(const float* x, const float* w, const float* b,
 /* The classifier and its loss in one launch (training; model_fqandtoyo.py:1394 + GradientTailLoss :545-550 as called at
  * :1446-1460): logits = x w^T + b [G,V] (stored only when `logits` != NULL), *loss = mean GradientTailLoss(logits, class of row g
  * = targets[g] + target_offset, alpha), dlogits [G,V] = d loss / d logits.  G <= 16, K % 64 == 0, K <= 448; x, w 16-byte
- * aligned.  Same formulas as mobgt_gradient_tail_loss; the loss's partial sums are added in a fixed order. */
+ * aligned.  Same formulas as mobgt_gradient_tail_loss; the loss's partial sums are added in a fixed order.
+ * A row whose class matches no column (targets[g] + target_offset < 0 or >= V: a padding y = 0 with target_offset = -1) is a
+ * row of negatives only -- every one of its V columns takes the (1 - one_hot) branch; nothing is refused or skipped.
+ * The loss's sum: nb = min(1024, ceil(V / 32)) workgroups each add their partial sum (>= 0) as an integer count of 2^-24, through
+ * nine device-global cells, so the sum is the same bits whatever the arrival order, and
+ *     0 <= (sum of the workgroups' f32 partial sums) / (G V) - *loss < (nb + 9) 2^-24 / (G V)   (before the final rounding to f32)
+ * -- one truncation to 2^-24 per workgroup; the nine cells are counted too, although integer addition loses nothing in them.
+ * A workgroup whose partial sum is not finite, or is >= 2^18 (a diverged run: a nan or inf anywhere in x, w, b, or a logit
+ * past the range of 1 - sigmoid), makes *loss read +inf -- never nan, whatever the others add; dlogits then holds what the
+ * formulas give (nan / inf where they do).  The call that writes *loss re-arms all nine cells and the flag before it ends, after
+ * a +inf as after a finite loss: the next call on the stream starts from zero and returns the bits it would have returned
+ * without the diverged call before it.  One launch at a time (the cells are device-global). */
 int mobgt_skinny_linear_gtl(const float* x, const float* w, const float* b, const int64_t* targets, int64_t target_offset,
                             float* logits, float* dlogits, float* loss, int G, int K, int V, float alpha, void* stream);
 
@@ -459,7 +473,9 @@ int mobgt_gelu_bwd_colsum(const void* dh, const void* u, void* du, float* dbias,
 /* GradientTailLoss(inputs, targets, alpha) of graphormer/model_fqandtoyo.py:545-550 (beta = k = 1) and its
  * gradient in one pass: logits [G,V] f32, targets [G] int64 -> *loss (f32 scalar, overwritten) and
  * dlogits [G,V] = d(loss)/d(logits).  The class id of row g is targets[g] + target_offset (training_step's
- * `batched_data.y - 1`, model_fqandtoyo.py:1446-1460, without a launch for the subtraction). */
+ * `batched_data.y - 1`, model_fqandtoyo.py:1446-1460, without a launch for the subtraction).  A row whose class matches no
+ * column (< 0 or >= V: a padding y = 0 with target_offset = -1) is a row of negatives only; nothing is refused or skipped.
+ * The sum is f32 (per-workgroup partials added in index order): a nan or inf term makes *loss nan or inf as f32 addition does. */
 int mobgt_gradient_tail_loss(const float* logits, const int64_t* targets, int64_t target_offset, float* dlogits,
                              float* loss, int64_t G, int64_t V, float alpha, void* stream);
 /* The stock variant's encoder input in one launch each way (model.py:193-205; csrc/layer.hip): y [G, N+1, C] with row (g, 0) =
@@ -525,7 +541,12 @@ int mobgt_token_ln_bwd(const float* dy, const float* enc, const float* mean, con
 /* F.cross_entropy(logits, targets, ignore_index = ignore_index) with mean reduction -- the stock variant's training loss
  * (model.py:218-285; data.py:76 / :98: NLLLoss(ignore_index = 0) on log-softmax outputs) -- and its gradient in one launch
  * (csrc/layer.hip): *loss, dlogits [G,V] (may be NULL).  G <= 4095, V <= 10 240; a target outside [0, V) counts as ignored for
- * the gradient (torch raises).  One launch at a time (a device-global cell carries the mean's sum). */
+ * the gradient (torch raises): its dlogits row is zero and it adds nothing to the sum, but it counts in the mean's divisor
+ * (the number of rows with targets[g] != ignore_index).  No such row at all: *loss = nan, dlogits = 0 (as torch).
+ * A row's -log softmax is summed in fixed point (2^-24 units, truncated: *loss is short by < 2^-24 per counted row / divisor);
+ * a counted row whose term is nan makes *loss nan, one whose term is >= 2^16 or +inf makes it +inf (nan wins over inf).
+ * The call re-arms the cell and the flag whatever it returned: the next call is not affected.
+ * One launch at a time (a device-global cell carries the mean's sum). */
 int mobgt_cross_entropy(const float* logits, const int64_t* targets, int64_t ignore_index, float* dlogits, float* loss, int G,
                         int V, void* stream);
 /* nn.Dropout at the model's input/output/positional/GCN sites (model.py:206, model_fqandtoyo.py:358,1347,1364;

@@ -456,6 +456,7 @@ extern "C" int mobgt_skinny_linear_bwd(const float* dy, const float* x, const fl
                                        int G, int K, int V, void* stream) {
     const int rc = check_dims(G, K, V);
     if (rc) return rc;
+    if (db && !dw) return MOBGT_EBADDIM;                                 // (db is the dW kernel's by-product: it would stay unwritten)
     hipStream_t st = (hipStream_t)stream;
     if (dx) {
         // dx is accumulated across the DX_SPLIT workgroups of a column block: zero it first (a kernel, not a memset node)
@@ -470,7 +471,8 @@ extern "C" int mobgt_skinny_linear_bwd(const float* dy, const float* x, const fl
 extern "C" int mobgt_skinny_linear_dx(const float* dy, const float* w, float* dx, int G, int K, int V, void* stream) {
     const int rc = check_dims(G, K, V);
     if (rc) return rc;
-    if ((K & 15) || ((uintptr_t)w & 15)) return MOBGT_EBADDIM;
+    if ((K & 15) || !dx) return MOBGT_EBADDIM;
+    if ((uintptr_t)w & 15) return MOBGT_EALIGN;
     hipLaunchKernelGGL(skinny_dx_mfma_kernel, dim3(K / 16, dxm_vsplit(V)), dim3(256), 0, (hipStream_t)stream, dy, w, dx, G, K, V);
     return (int)hipGetLastError();
 }
@@ -480,7 +482,8 @@ extern "C" int mobgt_skinny_linear_bwd_both(const float* dy, const float* x, con
                                             int G, int K, int V, void* stream) {
     const int rc = check_dims(G, K, V);
     if (rc) return rc;
-    if ((K & 15) || ((uintptr_t)w & 15) || !dx || !dw) return MOBGT_EBADDIM;
+    if ((K & 15) || !dx || !dw) return MOBGT_EBADDIM;
+    if ((uintptr_t)w & 15) return MOBGT_EALIGN;
     const int vsplit = dxm_vsplit(V);
     const int blocks = (K / 16) * vsplit + (V + DW_ROWS - 1) / DW_ROWS;
     hipLaunchKernelGGL(skinny_bwd_both_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, x, w, dx, dw, db, G, K, V, vsplit);

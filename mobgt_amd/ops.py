@@ -804,7 +804,9 @@ def _skinny_backward(ctx, dy):
     dy = dy.contiguous()
     dx = None
     dx_mfma = ctx.needs_input_grad[0] and not ctx.all_hip and K % 16 == 0 and K <= 512
-    both = dx_mfma and ctx.needs_input_grad[1]
+    want_db = ctx.has_bias and ctx.needs_input_grad[2]
+    want_dw = ctx.needs_input_grad[1] or want_db      # (db is the dW kernel's by-product: a frozen weight still gets the launch)
+    both = dx_mfma and want_dw
     if dx_mfma:     # one pass over W at the full L1 rate (the library's 16x16 tiles: 26 us at V = 7857, K = 448)
         dx = zeros_f32((G, K), x.device)
         if not both:
@@ -814,15 +816,17 @@ def _skinny_backward(ctx, dy):
     dw = None
     if ctx.needs_input_grad[1]:
         dw = ctx.sink[:] if ctx.sink is not None else torch.empty_like(w)      # (a fresh view object of the sink)
+    elif want_db:
+        dw = torch.empty_like(w)                      # (scratch: never returned)
     db = None
-    if ctx.has_bias and ctx.needs_input_grad[2]:      # (written in full by the kernel: the sink needs no zeroing for it)
+    if want_db:                                       # (written in full by the kernel: the sink needs no zeroing for it)
         db = ctx.sink_b[:] if ctx.sink_b is not None else torch.empty(V, dtype=torch.float32, device=x.device)
     if both:        # dx and dW (+ db) share nothing but dy: one launch, the first workgroups run the dx body
         _lib.call("mobgt_skinny_linear_bwd_both", _p(dy), _p(x), _p(w), _p(dx), _p(dw), _p(db), G, K, V, _stream())
-        return dx, dw, db
-    _lib.call("mobgt_skinny_linear_bwd", _p(dy), _p(x), _p(w), _p(dx if ctx.all_hip else None), _p(dw), _p(db),
-              G, K, V, _stream())
-    return dx, dw, db
+    else:
+        _lib.call("mobgt_skinny_linear_bwd", _p(dy), _p(x), _p(w), _p(dx if ctx.all_hip else None), _p(dw), _p(db),
+                  G, K, V, _stream())
+    return dx, (dw if ctx.needs_input_grad[1] else None), db
 
 
 class _SkinnyLinearGtlFn(torch.autograd.Function):
