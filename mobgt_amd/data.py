@@ -661,8 +661,9 @@ class SessionCollator(DeviceCollator):
 
     @staticmethod
     def lengths_of(dataset):
-        """A SessionDataset recorded every session's n when it validated them; any other sequence of sessions is measured."""
-        return [int(v) for v in dataset.n] if isinstance(dataset, SessionDataset) else [_as_record(s).n for s in dataset]
+        """A SessionDataset recorded every session's n when it validated them, a PrefixDataset every sample's; any other sequence
+        of sessions is measured."""
+        return [int(v) for v in dataset.n] if isinstance(dataset, (SessionDataset, PrefixDataset)) else [_as_record(s).n for s in dataset]
 
     def new_stage(self, lay, side, host=True):
         """DeviceCollator's stage, with the session bytes in place of its pinned raw arrays: a pinned SessionLayout buffer and
@@ -748,3 +749,7 @@ from .universe import (BuiltUniverse, TransitionGraph, UniverseCounts, build_uni
 
 # ---- sessions from a raw check-in log (checkins.py) ---------------------------------------------------------------------------------
 from .checkins import Sessionized, sessionize, sessionize_host  # noqa: E402,F401
+
+
+# ---- every prefix of a session as a sample (prefixes.py) ----------------------------------------------------------------------------
+from .prefixes import PrefixDataset, PrefixStats, prefix_stats, prefix_stats_host  # noqa: E402,F401

@@ -115,6 +115,10 @@ class UniverseCounts:
 
 # ---- what both forms check on the host, before anything is launched ---------------------------------------------------------------
 def _dataset(ds):
+    from .prefixes import PrefixDataset
+    if isinstance(ds, PrefixDataset):
+        raise TypeError("the universe is counted over sessions, and a PrefixDataset holds every transition of a session once per "
+                        "prefix that contains it: give its base, pds.base")
     if all(hasattr(ds, a) for a in ("seq", "offsets", "users")):
         return ds
     from .data import SessionDataset
