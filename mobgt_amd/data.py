@@ -753,3 +753,7 @@ from .checkins import Sessionized, sessionize, sessionize_host  # noqa: E402,F40
 
 # ---- every prefix of a session as a sample (prefixes.py) ----------------------------------------------------------------------------
 from .prefixes import PrefixDataset, PrefixStats, prefix_stats, prefix_stats_host  # noqa: E402,F401
+
+
+# ---- the Markov baseline on the same samples (baseline.py) --------------------------------------------------------------------------
+from .baseline import MarkovBaseline  # noqa: E402,F401
