@@ -9,17 +9,33 @@ i.e. 4 library GEMMs (bias in the epilogue), the HIP attention kernel and 3-4 fu
 produce every bias / LayerNorm gradient (column sums accumulated in registers), so no separate reduce,
 dropout-mask, cast or accumulate kernels remain.  The residual stream and all statistics are fp32; the
 GEMM-facing activations are fp32 or bf16 (`act_dtype`).
+
+WHICH form of each stage runs is decided in layer_plan.py (plan_forward at the top of the forward, plan_backward at the top of
+the backward); the functions here allocate what the plan names and launch it.
 """
 import ctypes
+from collections import namedtuple
 
 import torch
 
 from . import _lib, forms, ops
+from .layer_plan import (BACKWARD_FORMS, BIG_R, FORWARD_FORMS, TAIL_MAX_R, Given, Operands, Tail, plan_backward, plan_forward)
 from .ops import _p, _stream, _DT
 from .step_state import STEP
 
+_M32 = 0xFFFFFFFF
+_TAKES_OUT_DTYPE = {}
 
-_MM_OUT_DTYPE = [None]
+
+def _takes_out_dtype(gemm, *operands):
+    """Does this torch GEMM (mm / bmm / addmm) take `out_dtype`?  Tried once per function, on the first caller's operands."""
+    if gemm not in _TAKES_OUT_DTYPE:
+        try:
+            gemm(*operands, out_dtype=torch.float32)
+            _TAKES_OUT_DTYPE[gemm] = True
+        except Exception:
+            _TAKES_OUT_DTYPE[gemm] = False
+    return _TAKES_OUT_DTYPE[gemm]
 
 
 def _split_factor(R, tiles):
@@ -40,10 +56,21 @@ def _wgrad_hip(dtype, M, N, R):
     and 256x1024 at R = 12 560: 48 / 50 us vs 29 us) the library's split-K GEMM with its 64x64+ tiles is the
     faster one; at R <= 4096 the kernel is on par or ahead for the 1024x192 FFN shapes as well (9 vs 10.6 us at
     R = 800, 16.6 vs 17.9 at R = 2432) and saves the reduce launch."""
-    return dtype == torch.bfloat16 and M % 2 == 0 and N % 2 == 0 and (M * N <= _WGRAD_HIP_MN[0] or R <= 4096)
+    return dtype == torch.bfloat16 and M % 2 == 0 and N % 2 == 0 and (M * N <= _WGRAD_HIP_MN or R <= BIG_R)
 
 
-_WGRAD_HIP_MN = [131072]      # outputs up to which long batches stay on csrc/wgrad.hip
+_WGRAD_HIP_MN = 131072      # outputs up to which long batches stay on csrc/wgrad.hip
+
+
+def _wgrad_arrays(items):
+    """[(g, x, dw, db or None)] -> (n, g, ldg, x, ldx, dw, ldw, db, M, N) as the grouped weight-gradient launches take them."""
+    n = len(items)
+    vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+    return (n, (vp * n)(*[t[0].data_ptr() for t in items]), (i64 * n)(*[t[0].stride(0) for t in items]),
+            (vp * n)(*[t[1].data_ptr() for t in items]), (i64 * n)(*[t[1].stride(0) for t in items]),
+            (vp * n)(*[t[2].data_ptr() for t in items]), (i64 * n)(*[t[2].shape[1] for t in items]),
+            (vp * n)(*[(t[3].data_ptr() if t[3] is not None else None) for t in items]),
+            (ci * n)(*[t[0].shape[1] for t in items]), (ci * n)(*[t[1].shape[1] for t in items]))
 
 
 class _WgradBatch:
@@ -71,30 +98,28 @@ class _WgradBatch:
         it = self.items
         if not it:
             return False
-        n = len(it)
         R = it[0][0].shape[0]
-        vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-        garr = (vp * n)(*[t[0].data_ptr() for t in it])
-        xarr = (vp * n)(*[t[1].data_ptr() for t in it])
-        warr = (vp * n)(*[t[2].data_ptr() for t in it])
-        barr = (vp * n)(*[(t[3].data_ptr() if t[3] is not None else None) for t in it])
-        ldg = (i64 * n)(*[t[0].stride(0) for t in it])
-        ldx = (i64 * n)(*[t[1].stride(0) for t in it])
-        ldw = (i64 * n)(*[t[2].shape[1] for t in it])
-        M = (ci * n)(*[t[0].shape[1] for t in it])
-        N = (ci * n)(*[t[1].shape[1] for t in it])
+        arr = _wgrad_arrays(it)
+        group = arr[:8] + (R,) + arr[8:] + (_DT[it[0][0].dtype],)
         self.items = []
-        if tail is not None and R <= 1024:           # (the tail GEMM of mobgt_layer_backward_tail is sized for <= 1024 rows)
+        if tail is not None and R <= TAIL_MAX_R:     # (the tail GEMM of mobgt_layer_backward_tail is sized for <= 1024 rows)
             a, w, c = tail
             if (a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and c.dtype == torch.float32 and a.shape[1] % 32 == 0
                     and w.shape[1] % 8 == 0 and a.is_contiguous() and w.is_contiguous() and c.is_contiguous()):
-                _lib.call("mobgt_layer_backward_tail", n, garr, ldg, xarr, ldx, warr, ldw, barr, R, M, N, _DT[it[0][0].dtype],
-                          _p(a), a.stride(0), _p(w), w.stride(0), _p(c), c.stride(0),
+                _lib.call("mobgt_layer_backward_tail", *group, _p(a), a.stride(0), _p(w), w.stride(0), _p(c), c.stride(0),
                           a.shape[0], w.shape[1], a.shape[1], _stream())
                 return True
-        _lib.call("mobgt_linear_wgrad_group", n, garr, ldg, xarr, ldx, warr, ldw, barr, R, M, N, _DT[it[0][0].dtype],
-                  _stream())
+        _lib.call("mobgt_linear_wgrad_group", *group, _stream())
         return False
+
+
+def _join_step_wgrads(wb):
+    """The queued problems join the train step's ONE grouped launch (ops.flush_deferred_wgrads) -- parked as FRESH views of the
+    gradient buffers: autograd's AccumulateGrad clones a returned gradient that anything else still references, and the clone --
+    taken before the buffers are filled -- would later be copied over them."""
+    for g, x, dw, db in wb.items:
+        STEP.wgrad_items.append((g, x, None, None, (1.0, 1.0, 1.0), dw[:], db[:] if db is not None else None, False))
+    wb.items = []
 
 
 def _wgrad(g, x, db=None, sink=None):
@@ -108,9 +133,6 @@ def _wgrad(g, x, db=None, sink=None):
     return _mm_tn_f32(g, x, sink=sink)
 
 
-_BMM_OUT_DTYPE = [None]
-
-
 def _mm_tn_f32(g, x, sink=None):
     """g^T @ x for row-major g [R,M], x [R,N] with an fp32 result (library path: fp32 operands).
     The output is small and K = R is long, so K is split over a batch axis (strided views, no copies):
@@ -122,13 +144,7 @@ def _mm_tn_f32(g, x, sink=None):
     s = _split_factor(R, tiles) if (tiles <= 12 or (R >= 4096 and tiles < 256)) else 1
     if s > 1:
         ga, xa = g.view(s, R // s, M).transpose(1, 2), x.view(s, R // s, N)
-        if g.dtype != torch.float32 and _BMM_OUT_DTYPE[0] is None:
-            try:
-                torch.bmm(ga[:1], xa[:1], out_dtype=torch.float32)
-                _BMM_OUT_DTYPE[0] = True
-            except Exception:
-                _BMM_OUT_DTYPE[0] = False
-        if g.dtype != torch.float32 and _BMM_OUT_DTYPE[0]:
+        if g.dtype != torch.float32 and _takes_out_dtype(torch.bmm, ga[:1], xa[:1]):
             part = torch.bmm(ga, xa, out_dtype=torch.float32)           # f32 partial sums: no cast launch, no bf16 rounding
             # round 4: inside a train step the sum waits for the end of the backward pass, where all of the step's run as ONE
             # launch into the gradients' sinks (36 `.sum(0)` launches of 5.5 us per S-BIG step)
@@ -138,18 +154,11 @@ def _mm_tn_f32(g, x, sink=None):
         return part.float().sum(0) if part.dtype != torch.float32 else part.sum(0)
     if g.dtype == torch.float32:
         return g.t() @ x
-    if _MM_OUT_DTYPE[0] is None:
-        try:
-            torch.mm(g.t(), x, out_dtype=torch.float32)
-            _MM_OUT_DTYPE[0] = True
-        except Exception:
-            _MM_OUT_DTYPE[0] = False
-    if _MM_OUT_DTYPE[0]:
+    if _takes_out_dtype(torch.mm, g.t(), x):
         return torch.mm(g.t(), x, out_dtype=torch.float32)      # bf16 operands, fp32 accumulate AND fp32 result
     return (g.t() @ x).float()
 
 
-_ADDMM_OUT_DTYPE = [None]
 # (forms "chain_big"; round 4 measured and round 5 removed: the 16-row chain kernels also past 4 096 rows -- S-BIG 9.53 -> 10.93 ms: a 16-row
 #  workgroup re-streams the layer's weights from L2 785 times and loses against the library's tiles there)
 
@@ -157,13 +166,7 @@ _ADDMM_OUT_DTYPE = [None]
 def _addmm_f32(c, a, b, inplace=False):
     """c (fp32) + a @ b (bf16 operands) with an fp32 result.  `inplace`: c is a scratch buffer of the caller and
     receives the result (beta = 1 GEMM straight onto it; out-of-place, addmm first copies c into a new tensor)."""
-    if _ADDMM_OUT_DTYPE[0] is None:
-        try:
-            torch.addmm(c, a, b, out_dtype=torch.float32)
-            _ADDMM_OUT_DTYPE[0] = True
-        except Exception:
-            _ADDMM_OUT_DTYPE[0] = False
-    if _ADDMM_OUT_DTYPE[0]:
+    if _takes_out_dtype(torch.addmm, c, a, b):
         if inplace:
             return torch.ops.aten.addmm.dtype_out(c, a, b, torch.float32, out=c)
         return torch.addmm(c, a, b, out_dtype=torch.float32)
@@ -191,8 +194,8 @@ def _k1_fwd(x, y, x1, w, b, z, z32, mean, rstd, R, C, p, seed, seed_dev, salt, a
 # chain_bwd (its forward produced this layer's qkv), this layer returns dx1 as its input gradient, parks (dqkv, Wqkv^T, the
 # four problems) under that tensor's address, and the lower layer's chain launch finishes dx per row block in front of its
 # first norm and runs the weight gradients as extra workgroups (csrc/chain.hip).  A parked entry that no layer picks up is
-# an error, raised when the backward pass ends -- never a silently incomplete gradient.  (forms "defer_tail")
-_DEFER_MAX_R = [4096]      # S-GOW: 1024 / 2048 / 4096 / 16384 -> 18.96 / 19.33 / 19.65 / 19.5 k check-ins/s
+# an error, raised when the backward pass ends -- never a silently incomplete gradient.  (forms "defer_tail"; up to
+# layer_plan.DEFER_MAX_R rows)
 # (STEP.layer_tails, keyed by _pending_key; STEP.tail_check_task; tails of a backward pass that died: STEP.drop_stale_tails)
 
 
@@ -201,19 +204,27 @@ def _pending_key(t):
 
 
 def _park_tail(dx1, **work):
+    """`kind`: "layer" (dx and the four weight gradients), "big" (past 4 096 rows: dx only) or "preln" (dx through the host's norm)."""
     STEP.layer_tails[_pending_key(dx1)] = dict(dx1=dx1[:], **work)
     if STEP.tail_check_task != ops.graph_task_id():
         STEP.tail_check_task = ops.graph_task_id()
         torch.autograd.Variable._execution_engine.queue_callback(_pending_check)
 
 
+def _take_tail(dout):
+    """What the layer above parked under this layer's incoming gradient, or None."""
+    if STEP.layer_tails or STEP.tail_check_task is not None:
+        STEP.drop_stale_tails(ops.graph_task_id())
+    return STEP.layer_tails.pop(_pending_key(dout), None) if STEP.layer_tails else None
+
+
 def _complete_pending(pend):
     """The parked work as its own launch (what the layer would have issued itself): dx1 += dqkv Wqkv and the four dW."""
-    if pend.get("preln"):
+    if pend["kind"] == "preln":
         # (a pre-LN layer's tail goes back through a norm whose parameters and statistics only its host holds)
         raise RuntimeError("mobgt fused layer (pre-LN): the parked input gradient of a chained layer found no host "
                            "(was the layer's input used by something else as well?); set MOBGT_NO_DEFER_TAIL=1")
-    if pend.get("big"):                                   # (past 4 096 rows: the library's GEMM, onto dx1 in place)
+    if pend["kind"] == "big":                             # (past 4 096 rows: the library's GEMM, onto dx1 in place)
         _addmm_f32(pend["dx1"], pend["dqkv"], pend["wqkv"], inplace=True)
         return
     wb = _WgradBatch()
@@ -266,17 +277,6 @@ def chain_workspace(dev, C=192, R=None):
     return ws
 
 
-def _chain_ok(C, F, *ts):
-    return (forms.on("chain") and (C, F) in ((128, 1024), (192, 1024), (256, 1024))
-            and all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in ts))
-
-
-def _ln_gemm_ok(C, *ts):
-    """csrc/lngemm.hip: bf16 activations, model width a multiple of 32 up to 256, contiguous operands."""
-    return (forms.on("ln_gemm") and C % 32 == 0 and C <= 256
-            and all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in ts))
-
-
 def _ln_gemm_fwd(x, y, x1, w, b, z, mean, rstd, R, C, p, seed, seed_dev, salt, weight, bias, epilogue):
     """x1 = x + dropout(y); z = LayerNorm(x1); out = z @ weight.T + bias [-> GELU] in ONE launch (mobgt_ln_gemm_fwd)."""
     N = weight.shape[0]
@@ -305,6 +305,44 @@ def _k1_bwd(dz, dz32, dres, x1, mean, rstd, w, dx1, dy, dgamma, dbeta, dbias, R,
               _stream())
 
 
+def _chain_fwd(a, x, packed, sh, n1, norm, nq, outs, stats, plan, cfg):
+    """mobgt_layer_chain_fwd, both variants: `norm` = (weight, bias) behind the second residual add (fq: ffn_norm2; pre-LN: the NEXT
+    layer's self_attention_norm, or nulls), `nq` = the next layer's (packed Wqkv, bqkv) or nulls, `outs` = (x1, z, u, h, x2, out,
+    out_a, qkv_next) with None for what the variant does not produce."""
+    p_wo, p_w1, p_w2 = packed
+    _lib.call("mobgt_layer_chain_fwd", _p(a), _p(x), _p(p_wo), _p(sh.bo), _p(n1[0]), _p(n1[1]), _p(p_w1), _p(sh.b1), _p(p_w2),
+              _p(sh.b2), _p(norm[0]), _p(norm[1]), _p(nq[0]), _p(nq[1]), *[_p(t) for t in outs], _p(stats[2]), _p(stats[3]),
+              _p(stats[4]), _p(stats[5]), plan.R, plan.C, plan.F, cfg.p, cfg.seed, _p(cfg.seed_dev), (cfg.salt + 1) & _M32,
+              (cfg.salt + 2) & _M32, _p(chain_workspace(x.device, plan.C, plan.R)), _stream())
+
+
+def _chain_bwd(entry, plan, cfg, sv, dout, norm, sm, pend):
+    """One backward chain launch: d(out) -> [norm'] -> dropout' -> (W2, gelu') -> W1 -> ffn_norm' + residual -> dropout' -> Wo.
+    `entry`: "chain16" (mobgt_layer_chain_bwd), "chain64" (..._big, past 4 096 rows) or "preln" (..._preln); the three share their
+    first 32 arguments.  `norm` = (weight, dweight, dbias) of the norm in front (fq: ffn_norm2; pre-LN: the hosted layer's
+    self_attention_norm, or nulls).  `pend`: the tail hosted for the layer above (`dout` holds its dx1): dx1 + dqkv Wqkv is
+    finished in front of the first norm and -- 16-row entry -- its weight gradients run as extra workgroups.
+    -> (df, du, dy, da, dx1)"""
+    R, C, F = plan.R, plan.C, plan.F
+    bf = dict(dtype=cfg.act_dtype, device=dout.device)
+    df, dy, da = torch.empty(R, C, **bf), torch.empty(R, C, **bf), torch.empty(R, C, **bf)
+    du = torch.empty(R, F, **bf)
+    dx1 = torch.empty(R, C, dtype=torch.float32, device=dout.device)
+    w2t, w1t, wot = cfg.packed_t[:3]
+    st = sv.stats
+    ptrs = [_p(t) for t in (dout, sv.x2, sv.x1, sv.u, st[2], st[3], st[4], st[5], sv.n1w, norm[0], w2t, w1t, wot, df, du, dy, da, dx1,
+                            norm[1], norm[2], sm.db2, sm.dn1w, sm.dn1b, sm.dbo)]
+    dims = (R, C, F, cfg.p, cfg.seed, _p(cfg.seed_dev), (cfg.salt + 1) & _M32, (cfg.salt + 2) & _M32)
+    tail = (_p(pend["dqkv"]), _p(pend["wqt"])) if pend is not None else (None, None)
+    if entry == "chain64":      # b1's gradient is summed inside (db1 is zero-filled); the hosted tail comes without weight gradients
+        _lib.call("mobgt_layer_chain_bwd_big", *ptrs, _p(None if plan.db1_in_wgrad else sm.db1), *dims, *tail, _stream())
+    else:
+        extra = _wgrad_arrays(pend["items"]) if pend is not None and pend["items"] else (0,) + (None,) * 9
+        _lib.call("mobgt_layer_chain_bwd_preln" if entry == "preln" else "mobgt_layer_chain_bwd", *ptrs, *dims, *tail, *extra,
+                  _p(chain_workspace(dout.device, C, R)), _stream())
+    return df, du, dy, da, dx1
+
+
 class LayerConfig:
     """Per-call constants of one fused layer (not tensors that need gradients)."""
 
@@ -323,476 +361,342 @@ class LayerConfig:
         self.out_preln = False    # ... and this layer's output then carries that layer's normed input + qkv
 
 
+# the node's parameters (fp32 masters, reference names; nn = the next layer's self_attention_norm, pre-LN only), the layer's shadows,
+# what the forward saves (in ctx.save_for_backward's order), the gradient destinations the trainer registered (or None) and the
+# block of small gradients
+_Params = namedtuple("_Params", "wq bq wk bk wv bv wo bo n1w n1b nxw nxb w1 b1 w2 b2 nnw nnb", defaults=(None, None))
+_Shadows = namedtuple("_Shadows", "wqkv bqkv wo bo w1 b1 w2 b2")
+_Saved = namedtuple("_Saved", "x xa qkv a lse x1 z u h x2 stats s_wqkv s_wo s_w1 s_w2 n1w nxw nnw")
+_Sinks = namedtuple("_Sinks", "qkv wo w1 w2 small nx nn")
+_SmallGrads = namedtuple("_SmallGrads", "dbqkv dbo db1 db2 dn1w dn1b dnxw dnxb")
+
+
+def _aligned(*ts):
+    return all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in ts)
+
+
+def _forms_on(names):
+    return {name: forms.on(name) for name in names}
+
+
+def _given(cfg, xa_pre, qkv_pre, p, R, C):
+    A, nq = cfg.act_dtype, cfg.next_qkv
+    return Given(xa_pre=xa_pre is not None and xa_pre.dtype == A and xa_pre.numel() == R * C,
+                 qkv_pre=qkv_pre is not None and qkv_pre.dtype == A and qkv_pre.numel() == 3 * R * C,
+                 nx=p.nxw is not None, packed=cfg.packed is not None, n_packed_t=len(cfg.packed_t) if cfg.packed_t is not None else 0,
+                 next_qkv=nq is not None and nq[0].dtype == A and tuple(nq[0].shape) == (3 * C, C) and _aligned(nq[0]),
+                 next_norm=p.nnw is not None and p.nnw.is_contiguous() and p.nnb is not None, from_layer=bool(cfg.from_layer))
+
+
+def _operands(cfg, x, xa, sh, p):
+    """The one place that looks at the forward's tensors for plan_forward.  Not asked about: tensors the forward allocates itself
+    (the attention output going into the chain launch, the out-projection going into the norm + FFN-1 launch) -- fresh, so
+    contiguous and aligned.  Every form these predicates guard needs bf16 activations; a group is looked at only where the variant
+    and what the caller supplied leave it a reader."""
+    if cfg.act_dtype != torch.bfloat16 or xa is None:
+        return Operands(False, False, False, False, False, False, False)
+    R, C, F = x.shape[0] * x.shape[1], x.shape[2], sh.w1.shape[0]
+    stock = cfg.variant == "stock"
+    own_norm = () if stock else (p.nxw, p.nxb)                           # (the pre-LN chain applies the NEXT layer's norm, not nx)
+    return Operands(gemm_qkv=ops.layer_gemm_ok(xa, sh.wqkv), gemm_w1=ops.layer_gemm_ok(xa, sh.w1),
+                    chain=cfg.packed is not None and _aligned(x, sh.bo, sh.b1, sh.b2, p.n1w, p.n1b, *own_norm, *cfg.packed),
+                    ln_qkv=stock and _aligned(x, sh.wqkv, sh.bqkv, p.nxw, p.nxb), ln_ffn=_aligned(x, sh.w1, sh.b1, sh.w2, sh.wo),
+                    packed_t=cfg.packed_t is not None and _aligned(*cfg.packed_t), wgrad_hip=_wgrad_hip(cfg.act_dtype, F, C, R))
+
+
+def _input_act(cfg, x, xa_pre, given, R, C):
+    """The layer's GEMM-facing input [R, C]: stock -- a buffer its norm fills, or the normed copy the layer below made (None when
+    that is missing: plan_forward raises); fq -- x itself (f32), the copy the previous layer's LayerNorm kernel wrote, or a cast."""
+    A = cfg.act_dtype
+    if cfg.variant == "stock":
+        if given.nx:
+            return torch.empty(R, C, dtype=A, device=x.device)
+        return xa_pre.view(R, C) if given.xa_pre else None
+    if A == torch.float32:
+        return x.view(R, C)
+    return xa_pre.view(R, C) if given.xa_pre else x.view(R, C).to(A)
+
+
+def _find_sinks(plan, p, C):
+    """Destinations in the trainer's flat buffer, if it registered any."""
+    # the four weight gradients (q/k/v are adjacent there exactly when they are adjacent in the fused [3C, C] parameter storage)
+    sq, sk, sv = ops.grad_sink(p.wq), ops.grad_sink(p.wk), ops.grad_sink(p.wv)
+    s_qkv = None
+    if sq is not None and sk is not None and sv is not None and sq.is_contiguous() \
+            and sk.data_ptr() == sq.data_ptr() + 4 * sq.numel() and sv.data_ptr() == sk.data_ptr() + 4 * sk.numel():
+        s_qkv = torch.as_strided(sq, (3 * C, C), (C, 1))
+    weights = (s_qkv, ops.grad_sink(p.wo), ops.grad_sink(p.w1), ops.grad_sink(p.w2))
+    # the block of small gradients [dbq dbk dbv | dbo | db1 | db2 | dn1w | dn1b | dnxw | dnxb]: one slice of the flat
+    # buffer when the trainer laid these parameters out in that order (train.flat_order)
+    # (pre-LN chain: the two norm gradients at the end of the block belong to ANOTHER layer when this layer's chain applies its
+    #  successor's norm, and do not exist when the layer below applied this layer's: the block is the first eight, the norms'
+    #  gradients have destinations of their own)
+    preln = plan.body == "preln_chain"
+    chain = [ops.grad_sink(t) for t in (p.bq, p.bk, p.bv, p.bo, p.b1, p.b2, p.n1w, p.n1b) + (() if preln else (p.nxw, p.nxb))]
+    small = None
+    if all(t is not None and t.is_contiguous() for t in chain) and \
+            all(chain[j + 1].data_ptr() == chain[j].data_ptr() + 4 * chain[j].numel() for j in range(len(chain) - 1)):
+        small = torch.as_strided(chain[0], (sum(t.numel() for t in chain),), (1,))
+    nx = (ops.grad_sink(p.nxw), ops.grad_sink(p.nxb)) if preln and p.nxw is not None else (None, None)
+    nn = (ops.grad_sink(p.nnw), ops.grad_sink(p.nnb)) if preln and plan.chain_next else (None, None)
+    return _Sinks(*weights, small, nx, nn)
+
+
+def _small_grads(sinks, C, F, n, dev):
+    """The first `n` of the layer's small gradients [dbqkv 3C | dbo C | db1 F | db2 C | dn1w C | dn1b C | dnxw C | dnxb C] as
+    consecutive views of ONE block: the trainer's slice (train.flat_order lays it out in this order) or a zero-filled buffer."""
+    sizes = [3 * C, C, F, C, C, C, C, C][:n]
+    block = sinks.small if sinks.small is not None else ops.zeros_f32((sum(sizes),), dev)
+    views, o = [], 0
+    for size in sizes:
+        views.append(block[o:o + size])
+        o += size
+    return views
+
+
+def _norm_grads(pair, have, C, dev):
+    """(dweight, dbias) of a norm whose gradients have destinations of their own (pre-LN chain), (None, None) without the norm."""
+    if not have:
+        return None, None
+    return tuple(s[:] if s is not None else ops.zeros_f32((C,), dev) for s in pair)
+
+
+def _forward_chain(plan, cfg, x, a, stats, sh, p):
+    """Body "chain" / "preln_chain": everything row-local of the layer -- out-projection ... second residual add [fq: + ffn_norm2] --
+    in one launch, + the NEXT layer's QKV projection (pre-LN: its self_attention_norm and projection) when the model named that layer
+    (cfg.next_qkv / next_norm)."""
+    R, C, F = plan.R, plan.C, plan.F
+    stock, nxt = plan.body == "preln_chain", plan.chain_next
+    f32, bf = dict(dtype=torch.float32, device=x.device), dict(dtype=cfg.act_dtype, device=x.device)
+    x1, x2 = torch.empty(R, C, **f32), torch.empty(R, C, **f32)
+    z, u, h = torch.empty(R, C, **bf), torch.empty(R, F, **bf), torch.empty(R, F, **bf)
+    out = None if stock else torch.empty(R, C, **f32)              # (pre-LN: the residual stream passes the next layer's norm by)
+    out_a = torch.empty(R, C, **bf) if nxt or not stock else None
+    qkv_next = torch.empty(R, 3 * C, **bf) if nxt else None
+    norm = (p.nxw, p.nxb) if not stock else (p.nnw, p.nnb) if nxt else (None, None)
+    _chain_fwd(a, x, cfg.packed, sh, (p.n1w, p.n1b), norm, cfg.next_qkv if nxt else (None, None),
+               (x1, z, u, h, x2, out, out_a, qkv_next), stats, plan, cfg)
+    if not stock:
+        cfg.out_act, cfg.out_qkv = out_a, qkv_next
+    elif nxt:
+        cfg.out_act, cfg.out_qkv, cfg.out_preln = out_a, qkv_next, True
+    return (x2 if stock else out), x1, z, u, h, x2
+
+
+def _forward_launches(plan, cfg, x, a, stats, sh, p):
+    """Body "launches": out-proj ... second LayerNorm as separate launches (every configuration the chain kernel does not cover)."""
+    R, C, A, own = plan.R, plan.C, cfg.act_dtype, plan.own
+    act = _DT[A]
+    seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
+    f32 = dict(dtype=torch.float32, device=x.device)
+    y = ops.layer_gemm(a.view(R, C), sh.wo, sh.bo) if own else torch.addmm(sh.bo, a.view(R, C), sh.wo.t())
+    x1 = torch.empty(R, C, **f32)
+    z = torch.empty(R, C, dtype=A, device=x.device)
+    if plan.ln_gemm:        # x1 = x + dropout(y), z = LN(x1), u = z W1^T + b1, h = gelu(u): one launch
+        u, h = _ln_gemm_fwd(x, y, x1, p.n1w, p.n1b, z, stats[2], stats[3], R, C, cfg.p, seed, sd, salt + 1, sh.w1, sh.b1,
+                            ops.GEMM_GELU)
+        f = ops.layer_gemm(h, sh.w2, sh.b2)
+    elif own:
+        _k1_fwd(x, y, x1, p.n1w, p.n1b, z, None, stats[2], stats[3], R, C, cfg.p, seed, sd, salt + 1, act)
+        u, h = ops.layer_gemm(z, sh.w1, sh.b1, epilogue=ops.GEMM_GELU)
+        f = ops.layer_gemm(h, sh.w2, sh.b2)
+    else:
+        _k1_fwd(x, y, x1, p.n1w, p.n1b, z, None, stats[2], stats[3], R, C, cfg.p, seed, sd, salt + 1, act)
+        u = torch.addmm(sh.b1, z, sh.w1.t())
+        h = torch.empty_like(u)
+        _lib.call("mobgt_gelu_fwd", _p(u), _p(h), u.numel(), act, _stream())
+        f = torch.addmm(sh.b2, h, sh.w2.t())
+    x2 = torch.empty(R, C, **f32)
+    if plan.variant == "stock":                                   # x = x + dropout(ffn(...))  (model.py:485-488)
+        _k1_fwd(x1, f, x2, None, None, None, None, None, None, R, C, cfg.p, seed, sd, salt + 2, act)
+        out = x2
+    else:                                                         # ... then ffn_norm2 (model_fqandtoyo.py:1742)
+        out = torch.empty(R, C, **f32)
+        out_a = torch.empty(R, C, dtype=A, device=x.device) if A != torch.float32 else None
+        _k1_fwd(x1, f, x2, p.nxw, p.nxb, out_a, out, stats[4], stats[5], R, C, cfg.p, seed, sd, salt + 2, act)
+        cfg.out_act = out_a                                       # bf16 copy for the next layer's QKV GEMM
+    return out, x1, z, u, h, x2
+
+
+def _backward_launches(plan, bp, cfg, wb, dout, sv, sm, sinks):
+    """d(out) ... d(attention out) as separate launches (every configuration the backward chain does not cover).
+    -> (da, dx1, dw2, dw1, dwo)"""
+    R, C, F, A, own = plan.R, plan.C, plan.F, cfg.act_dtype, plan.own
+    act, dev, st = _DT[A], dout.device, sv.stats
+    seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
+    db1_in_wgrad = plan.db1_in_wgrad                              # then b1's gradient rides on the dW1 kernel
+    df = torch.empty(R, C, dtype=A, device=dev)
+    du = None
+    if plan.variant == "stock":
+        dx2 = dout                                                # grad at x2 = x1 + dropout(f)
+        _k1_bwd(None, None, dout, sv.x2, None, None, None, None, df, None, None, sm.db2, R, C, cfg.p, seed, sd, salt + 2, act)
+    else:
+        dx2 = torch.empty(R, C, dtype=torch.float32, device=dev)  # through ffn_norm2
+        if bp.ln_gemm_bwd and db1_in_wgrad:    # ffn_norm2' + dropout' -> df, du = (df W2) * gelu'(u): one launch
+            du = _ln_gemm_bwd(None, dout, None, sv.x2, st[4], st[5], sv.nxw, dx2, df, sm.dnxw, sm.dnxb, sm.db2, R, C, cfg.p,
+                              seed, sd, salt + 2, sv.s_w2, ops.GEMM_GELU_BWD, sv.u)
+        else:
+            _k1_bwd(None, dout, None, sv.x2, st[4], st[5], sv.nxw, dx2, df, sm.dnxw, sm.dnxb, sm.db2, R, C, cfg.p, seed, sd,
+                    salt + 2, act)
+    dw2 = wb.add(df, sv.h, sink=sinks.w2)
+    if du is not None:
+        pass
+    elif own and db1_in_wgrad:
+        du = ops.layer_gemm(df, sv.s_w2, None, True, ops.GEMM_GELU_BWD, aux_in=sv.u)      # (df W2) * gelu'(u), one launch
+    else:
+        dh = df @ sv.s_w2
+        du = torch.empty_like(sv.u)
+        _lib.call("mobgt_gelu_bwd_colsum", _p(dh), _p(sv.u), _p(du), _p(None if db1_in_wgrad else sm.db1), R, F, act,
+                  _stream())
+    dz = ops.layer_gemm(du, sv.s_w1, None, True) if own else du @ sv.s_w1
+    dw1 = wb.add(du, sv.z, db=sm.db1 if db1_in_wgrad else None, sink=sinks.w1)
+    dx1 = torch.empty(R, C, dtype=torch.float32, device=dev)
+    dy = torch.empty(R, C, dtype=A, device=dev)
+    if bp.ln_gemm_bwd:      # ffn_norm1' + residual + dropout' -> dy, da = dy Wo: one launch
+        da = _ln_gemm_bwd(dz, None, dx2, sv.x1, st[2], st[3], sv.n1w, dx1, dy, sm.dn1w, sm.dn1b, sm.dbo, R, C, cfg.p, seed, sd,
+                          salt + 1, sv.s_wo, ops.GEMM_BIAS, None)
+    else:
+        _k1_bwd(dz, None, dx2, sv.x1, st[2], st[3], sv.n1w, dx1, dy, sm.dn1w, sm.dn1b, sm.dbo, R, C, cfg.p, seed, sd, salt + 1, act)
+        da = ops.layer_gemm(dy, sv.s_wo, None, True) if own else dy @ sv.s_wo
+    dwo = wb.add(dy, sv.a.view(R, C), sink=sinks.wo)
+    return da, dx1, dw2, dw1, dwo
+
+
+def _finish_dx(plan, bp, cfg, sv, sm, dqkv2, dx1, items):
+    """The layer's input gradient from dx1 (the gradient at the first residual add) and dqkv, the way the plan names."""
+    R, C = plan.R, plan.C
+    if bp.dx == "below":
+        # nothing more is launched for this layer: the chain launch of the layer below finishes dx = dx1 + dqkv Wqkv in front of its
+        # first norm (pre-LN: dx2 = dx1 + norm'(dqkv Wqkv)) and runs the parked weight gradients, if any.  Past 4 096 rows it is the
+        # 64-row chain and a 20 us library GEMM otherwise; the weight gradients are the library's there and were issued here.
+        kind = "preln" if bp.entry == "preln" else "layer" if bp.wgrads == "below" else "big"
+        _park_tail(dx1, dqkv=dqkv2, wqkv=sv.s_wqkv, wqt=cfg.packed_t[3], items=items, R=R, kind=kind)
+    elif bp.dx == "norm":                                         # stock: back through self_attention_norm
+        dz0 = ops.layer_gemm(dqkv2, sv.s_wqkv, None, True) if plan.own else dqkv2 @ sv.s_wqkv
+        dx = torch.empty(R, C, dtype=torch.float32, device=dx1.device)
+        _k1_bwd(dz0, None, dx1, sv.x.view(R, C), sv.stats[0], sv.stats[1], sv.nxw, dx, None, sm.dnxw, sm.dnxb, None, R, C, 0.0,
+                cfg.seed, cfg.seed_dev, cfg.salt, _DT[cfg.act_dtype])
+        return dx
+    elif bp.dx == "addmm_out":                                    # dx1 is this function's own buffer: accumulate onto it
+        torch.addmm(dx1, dqkv2, sv.s_wqkv, out=dx1)
+    elif bp.dx == "own_gemm":
+        ops.layer_gemm(dqkv2, sv.s_wqkv, None, True, ops.GEMM_ADD, aux_in=dx1)     # dx1 + dqkv Wqkv, f32, in place
+    elif bp.dx == "addmm_f32":
+        _addmm_f32(dx1, dqkv2, sv.s_wqkv, inplace=True)
+    return dx1                                                    # ("tail": the weight-gradient launch added dqkv Wqkv onto it)
+
+
 class _FusedLayerFn(torch.autograd.Function):
-    """params (fp32 masters, reference names):
+    """params (fp32 masters, reference names; _Params):
        fq   : wq, bq, wk, bk, wv, bv, wo, bo, n1 = ffn_norm1, nx = ffn_norm2, w1, b1, w2, b2
-       stock: wq, bq, wk, bk, wv, bv, wo, bo, n1 = ffn_norm,  nx = self_attention_norm, w1, b1, w2, b2
+       stock: wq, bq, wk, bk, wv, bv, wo, bo, n1 = ffn_norm,  nx = self_attention_norm, w1, b1, w2, b2, nn = the next layer's nx
     `shadows`: (wqkv [3C,C], bqkv [3C], wo, bo, w1, b1, w2, b2) in act_dtype (the fused masters when fp32)."""
 
     @staticmethod
-    def forward(ctx, x, token, cfg, shadows, xa_pre, qkv_pre, wq, bq, wk, bk, wv, bv, wo, bo, n1w, n1b, nxw, nxb, w1, b1, w2, b2,
-                nnw=None, nnb=None):
+    def forward(ctx, x, token, cfg, shadows, xa_pre, qkv_pre, *params):
         # wq/wk/wv (+ biases) are views of one fused [3C, C] storage (MultiHeadAttention.fuse_qkv_storage); they
         # are separate arguments only so that autograd has an edge to each reference-named parameter.
+        p, sh = _Params(*params), _Shadows(*shadows)
         G, T, C = x.shape
-        R = G * T
-        A = cfg.act_dtype
-        act = _DT[A]
-        dev = x.device
-        s_wqkv, s_bqkv, s_wo, s_bo, s_w1, s_b1, s_w2, s_b2 = shadows
+        R, F, A = G * T, sh.w1.shape[0], cfg.act_dtype
         x = x.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        stats = torch.empty(6, R, **f32)
+        given = _given(cfg, xa_pre, qkv_pre, p, R, C)
+        xa = _input_act(cfg, x, xa_pre, given, R, C)
+        plan = plan_forward(cfg.variant, A == torch.bfloat16, R, C, F, any(ctx.needs_input_grad), given, _operands(cfg, x, xa, sh, p),
+                            _forms_on(FORWARD_FORMS))
+        stats = torch.empty(6, R, dtype=torch.float32, device=x.device)
         seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
-        stock = cfg.variant == "stock"
-        # pre-LN, input normed and projected by the chain launch of the layer below (model.fused_layer_forward: no own norm)
-        chained_in = stock and nxw is None
-        if chained_in:
-            if not (xa_pre is not None and qkv_pre is not None and xa_pre.dtype == A and xa_pre.numel() == R * C
-                    and qkv_pre.dtype == A and qkv_pre.numel() == 3 * R * C):
-                raise RuntimeError("mobgt fused layer (pre-LN): a chained input without its normed copy / qkv")
-            xa = xa_pre.view(R, C)
-        elif stock:                                                   # y = self_attention_norm(x)  (model.py:480)
-            xa = torch.empty(R, C, dtype=A, device=dev)
-            # (the first layer of a stack: norm + QKV projection as one launch when the own-GEMM path takes the layer -- below)
-            norm_in_gemm = (A == torch.bfloat16 and qkv_pre is None and forms.on("own_gemm") and ops.layer_gemm_ok(xa, s_wqkv)
-                            and _ln_gemm_ok(C, x, s_wqkv, s_bqkv, nxw, nxb) and forms.on("stock_ln_qkv"))
-            if not norm_in_gemm:
-                _k1_fwd(x, None, None, nxw, nxb, xa, None, stats[0], stats[1], R, C, 0.0, seed, sd, salt, act)
-        else:
-            if A == torch.float32:
-                xa = x.view(R, C)
-            elif xa_pre is not None and xa_pre.dtype == A and xa_pre.numel() == R * C:
-                xa = xa_pre.view(R, C)                             # written by the previous layer's LayerNorm kernel
-            else:
-                xa = x.view(R, C).to(A)
-        # bf16 configuration at MobGT's sizes: the split-K MFMA kernel of csrc/gemm.hip (GELU fused after FFN layer 1);
-        # otherwise the library
-        own = forms.on("own_gemm") and ops.layer_gemm_ok(xa, s_wqkv) and ops.layer_gemm_ok(xa, s_w1) and C % 32 == 0 \
-            and s_w1.shape[0] % 32 == 0
-        ctx.own_gemm = own
-        if qkv_pre is not None and qkv_pre.dtype == A and qkv_pre.numel() == 3 * R * C and (not stock or chained_in):
-            qkv = qkv_pre.view(G, T, 3 * C)                            # written by the previous layer's chain kernel
-        elif stock and not chained_in and norm_in_gemm:
+        if plan.norm_launch:                                          # y = self_attention_norm(x)  (model.py:480)
+            _k1_fwd(x, None, None, p.nxw, p.nxb, xa, None, stats[0], stats[1], R, C, 0.0, seed, sd, salt, _DT[A])
+        if plan.qkv == "pre":
+            qkv = qkv_pre.view(G, T, 3 * C)                           # written by the previous layer's chain kernel
+        elif plan.qkv == "ln_gemm":
             # round 4: xa = self_attention_norm(x) and qkv = xa Wqkv^T + b in ONE launch (csrc/lngemm.hip, no residual input)
-            qkv = _ln_gemm_fwd(x, None, None, nxw, nxb, xa, stats[0], stats[1], R, C, 0.0, seed, sd, salt, s_wqkv, s_bqkv,
+            qkv = _ln_gemm_fwd(x, None, None, p.nxw, p.nxb, xa, stats[0], stats[1], R, C, 0.0, seed, sd, salt, sh.wqkv, sh.bqkv,
                                ops.GEMM_BIAS).view(G, T, 3 * C)
-        elif own:
-            qkv = ops.layer_gemm(xa, s_wqkv, s_bqkv).view(G, T, 3 * C)
+        elif plan.qkv == "own":
+            qkv = ops.layer_gemm(xa, sh.wqkv, sh.bqkv).view(G, T, 3 * C)
         else:
-            qkv = torch.addmm(s_bqkv, xa, s_wqkv.t()).view(G, T, 3 * C)
+            qkv = torch.addmm(sh.bqkv, xa, sh.wqkv.t()).view(G, T, 3 * C)
         q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
         a, lse = ops._attn_fwd(q, k, v, cfg.pack, cfg.scale, cfg.p_att, seed ^ (salt * 0x9E3779B1), sd)
-        F = s_w1.shape[0]
         cfg.out_qkv = None
-        # (past 4 096 rows `own` is off -- the library's GEMMs take the layer's products -- but the forward chain has its 64-row
-        #  form there: csrc/chain.hip, layer_chain_fwd_big_kernel; the backward then runs the library's launches)
-        use_chain = (not stock and (own or (R > 4096 and forms.on("chain_big"))) and A == torch.bfloat16 and cfg.packed is not None
-                     and _chain_ok(C, F, x, a, s_bo, s_b1, s_b2, n1w, n1b, nxw, nxb, *cfg.packed))
-        # pre-LN chain (round 4): out-projection ... second residual add in one launch, + the NEXT layer's self_attention_norm
-        # and QKV projection when the model named that layer (cfg.next_norm / next_qkv); the backward is the chain's too
-        need_bwd = any(ctx.needs_input_grad)
-        bwd_ok = bool(forms.on("chain_bwd") and cfg.packed_t is not None and len(cfg.packed_t) > 3
-                      and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in cfg.packed_t))
-        stock_chain = (stock and own and A == torch.bfloat16 and cfg.packed is not None and (bwd_ok or not need_bwd)
-                       and _wgrad_hip(A, F, C, R) and _chain_ok(C, F, x, a, s_bo, s_b1, s_b2, n1w, n1b, *cfg.packed))
-        ctx.stock_chain = stock_chain
-        ctx.chained_in = chained_in
-        if chained_in and not stock_chain:
-            raise RuntimeError("mobgt fused layer (pre-LN): the layer below chained into this one, which cannot run its chain kernels")
-        ctx.fuse_ln = use_chain and own
-        # (past 4 096 rows both chains are the 64-row kernels of csrc/chain.hip; the backward hosts the upper layer's tail only)
-        ctx.chain_bwd = bool(use_chain and forms.on("chain_bwd") and cfg.packed_t is not None and (R <= 4096 or forms.on("chain_big"))
-                             and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in cfg.packed_t))
-        # the layer below produced this layer's qkv in ITS chain launch and will run chain_bwd: it can host what this layer's
-        # backward leaves undone (see STEP.layer_tails)
-        ctx.below_hosts = bool(cfg.from_layer and qkv_pre is not None and ctx.chain_bwd and len(cfg.packed_t) > 3)
-        if use_chain:               # everything row-local of the layer (+ the next layer's QKV projection) in one launch
-            bf = dict(dtype=A, device=dev)
-            x1, x2, out = torch.empty(R, C, **f32), torch.empty(R, C, **f32), torch.empty(R, C, **f32)
-            z, out_a = torch.empty(R, C, **bf), torch.empty(R, C, **bf)
-            u, h = torch.empty(R, F, **bf), torch.empty(R, F, **bf)
-            nq = cfg.next_qkv
-            if nq is not None and not (nq[0].dtype == A and tuple(nq[0].shape) == (3 * C, C) and nq[0].is_contiguous()
-                                       and nq[0].data_ptr() % 16 == 0):
-                nq = None
-            qkv_next = torch.empty(R, 3 * C, **bf) if nq is not None else None
-            p_wo, p_w1, p_w2 = cfg.packed
-            _lib.call("mobgt_layer_chain_fwd", _p(a), _p(x), _p(p_wo), _p(s_bo), _p(n1w), _p(n1b), _p(p_w1), _p(s_b1), _p(p_w2),
-                      _p(s_b2), _p(nxw), _p(nxb), _p(nq[0] if nq else None),
-                      _p(nq[1] if nq else None), _p(x1), _p(z), _p(u), _p(h), _p(x2), _p(out),
-                      _p(out_a), _p(qkv_next), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                      _p(stats[5]), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                      (salt + 2) & 0xFFFFFFFF, _p(chain_workspace(dev, C, R)), _stream())
-            cfg.out_act, cfg.out_qkv = out_a, qkv_next
-        elif stock_chain:
-            bf = dict(dtype=A, device=dev)
-            x1, x2 = torch.empty(R, C, **f32), torch.empty(R, C, **f32)
-            z = torch.empty(R, C, **bf)
-            u, h = torch.empty(R, F, **bf), torch.empty(R, F, **bf)
-            nq = cfg.next_qkv if nnw is not None else None
-            if nq is not None and not (nq[0].dtype == A and tuple(nq[0].shape) == (3 * C, C) and nq[0].is_contiguous()
-                                       and nq[0].data_ptr() % 16 == 0 and nnw.is_contiguous() and nnb is not None):
-                nq = None
-            ctx.chain_next = nq is not None
-            out_a = torch.empty(R, C, **bf) if nq is not None else None
-            qkv_next = torch.empty(R, 3 * C, **bf) if nq is not None else None
-            p_wo, p_w1, p_w2 = cfg.packed
-            _lib.call("mobgt_layer_chain_fwd", _p(a), _p(x), _p(p_wo), _p(s_bo), _p(n1w), _p(n1b), _p(p_w1), _p(s_b1), _p(p_w2),
-                      _p(s_b2), _p(nnw if nq is not None else None), _p(nnb if nq is not None else None),
-                      _p(nq[0] if nq else None), _p(nq[1] if nq else None), _p(x1), _p(z), _p(u), _p(h),
-                      _p(x2), _p(None), _p(out_a), _p(qkv_next), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                      _p(stats[5]), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                      (salt + 2) & 0xFFFFFFFF, _p(chain_workspace(dev, C, R)), _stream())
-            out = x2                                                  # the residual stream passes the next layer's norm by
-            if nq is not None:
-                cfg.out_act, cfg.out_qkv, cfg.out_preln = out_a, qkv_next, True
-        else:
-            out, x1, z, u, h, x2 = _FusedLayerFn._tail_launches(ctx, cfg, x, a, stats, shadows, own, stock, n1w, n1b, nxw, nxb,
-                                                                R, C, A, act, dev)
-        # destinations for the four weight gradients in the trainer's flat buffer, if it registered any (q/k/v are
-        # adjacent there exactly when they are adjacent in the fused [3C, C] parameter storage)
-        sq, sk, sv = ops.grad_sink(wq), ops.grad_sink(wk), ops.grad_sink(wv)
-        s_qkv = None
-        if sq is not None and sk is not None and sv is not None and sq.is_contiguous() \
-                and sk.data_ptr() == sq.data_ptr() + 4 * sq.numel() and sv.data_ptr() == sk.data_ptr() + 4 * sk.numel():
-            s_qkv = torch.as_strided(sq, (3 * C, C), (C, 1))
-        ctx.sinks = (s_qkv, ops.grad_sink(wo), ops.grad_sink(w1), ops.grad_sink(w2))
-        # the block of small gradients [dbq dbk dbv | dbo | db1 | db2 | dn1w | dn1b | dnxw | dnxb]: one slice of the flat
-        # buffer when the trainer laid these parameters out in that order (train.flat_order)
-        ctx.small_sink = None
-        # (pre-LN chain: the two norm gradients at the end of the block belong to ANOTHER layer when this layer's chain applies its
-        #  successor's norm, and do not exist when the layer below applied this layer's: the block is the first eight, the norms'
-        #  gradients have destinations of their own)
-        chain = [ops.grad_sink(t) for t in ((bq, bk, bv, bo, b1, b2, n1w, n1b) if stock_chain else (bq, bk, bv, bo, b1, b2, n1w, n1b, nxw, nxb))]
-        if all(t is not None and t.is_contiguous() for t in chain) and \
-                all(chain[j + 1].data_ptr() == chain[j].data_ptr() + 4 * chain[j].numel() for j in range(len(chain) - 1)):
-            ctx.small_sink = torch.as_strided(chain[0], (sum(t.numel() for t in chain),), (1,))
-        if stock_chain:
-            ctx.nx_sinks = (ops.grad_sink(nxw), ops.grad_sink(nxb)) if nxw is not None else (None, None)
-            ctx.nn_sinks = (ops.grad_sink(nnw), ops.grad_sink(nnb)) if getattr(ctx, "chain_next", False) else (None, None)
-        ctx.cfg = cfg
-        ctx.shapes = (G, T, C)
-        ctx.save_for_backward(x, xa, qkv, a, lse, x1, z, u, h, x2, stats, s_wqkv, s_wo, s_w1, s_w2, n1w, nxw,
-                              nnw if getattr(ctx, "chain_next", False) else None)
+        body = _forward_launches if plan.body == "launches" else _forward_chain
+        out, x1, z, u, h, x2 = body(plan, cfg, x, a, stats, sh, p)
+        ctx.plan, ctx.cfg, ctx.shapes = plan, cfg, (G, T, C)
+        ctx.chain_bwd, ctx.stock_chain = plan.chain_bwd, plan.body == "preln_chain"      # (the parity tests read these two off grad_fn)
+        ctx.sinks = _find_sinks(plan, p, C)
+        ctx.save_for_backward(x, xa, qkv, a, lse, x1, z, u, h, x2, stats, sh.wqkv, sh.wo, sh.w1, sh.w2, p.n1w, p.nxw,
+                              p.nnw if plan.chain_next else None)
         return out.view(G, T, C)
 
     @staticmethod
-    def _tail_launches(ctx, cfg, x, a, stats, shadows, own, stock, n1w, n1b, nxw, nxb, R, C, A, act, dev):
-        """out-proj ... second LayerNorm as separate launches (every configuration the chain kernel does not cover)."""
-        s_wqkv, s_bqkv, s_wo, s_bo, s_w1, s_b1, s_w2, s_b2 = shadows
-        seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
-        f32 = dict(dtype=torch.float32, device=dev)
-        y = ops.layer_gemm(a.view(R, C), s_wo, s_bo) if own else torch.addmm(s_bo, a.view(R, C), s_wo.t())
-        x1 = torch.empty(R, C, **f32)
-        z = torch.empty(R, C, dtype=A, device=dev)
-        fuse_ln = own and A == torch.bfloat16 and _ln_gemm_ok(C, x, y, s_w1, s_b1, s_w2, s_wo)
-        ctx.fuse_ln = fuse_ln
-        if fuse_ln:             # x1 = x + dropout(y), z = LN(x1), u = z W1^T + b1, h = gelu(u): one launch
-            u, h = _ln_gemm_fwd(x, y, x1, n1w, n1b, z, stats[2], stats[3], R, C, cfg.p, seed, sd, salt + 1, s_w1, s_b1,
-                                ops.GEMM_GELU)
-            f = ops.layer_gemm(h, s_w2, s_b2)
-        elif own:
-            _k1_fwd(x, y, x1, n1w, n1b, z, None, stats[2], stats[3], R, C, cfg.p, seed, sd, salt + 1, act)
-            u, h = ops.layer_gemm(z, s_w1, s_b1, epilogue=ops.GEMM_GELU)
-            f = ops.layer_gemm(h, s_w2, s_b2)
-        else:
-            _k1_fwd(x, y, x1, n1w, n1b, z, None, stats[2], stats[3], R, C, cfg.p, seed, sd, salt + 1, act)
-            u = torch.addmm(s_b1, z, s_w1.t())
-            h = torch.empty_like(u)
-            _lib.call("mobgt_gelu_fwd", _p(u), _p(h), u.numel(), act, _stream())
-            f = torch.addmm(s_b2, h, s_w2.t())
-        x2 = torch.empty(R, C, **f32)
-        if stock:                                                     # x = x + dropout(ffn(...))  (model.py:485-488)
-            _k1_fwd(x1, f, x2, None, None, None, None, None, None, R, C, cfg.p, seed, sd, salt + 2, act)
-            out = x2
-        else:                                                         # ... then ffn_norm2 (model_fqandtoyo.py:1742)
-            out = torch.empty(R, C, **f32)
-            out_a = torch.empty(R, C, dtype=A, device=dev) if A != torch.float32 else None
-            _k1_fwd(x1, f, x2, nxw, nxb, out_a, out, stats[4], stats[5], R, C, cfg.p, seed, sd, salt + 2, act)
-            cfg.out_act = out_a                                       # bf16 copy for the next layer's QKV GEMM
-        return out, x1, z, u, h, x2
-
-    @staticmethod
-    def _bwd_launches(ctx, cfg, wb, dout, x1, z, u, h, x2, a, stats, s_wo, s_w1, s_w2, n1w, nxw, dbo, db1, db2, dn1w, dn1b, dnxw,
-                      dnxb, G, T, C, F, A, act, dev, own, stock, db1_in_wgrad):
-        """d(out) ... d(attention out) as separate launches (every configuration the backward chain does not cover)."""
-        R = G * T
-        seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
-        k_qkv, k_wo, k_w1, k_w2 = ctx.sinks
-        df = torch.empty(R, C, dtype=A, device=dev)
-        fuse_ln = ctx.fuse_ln and forms.on("ln_gemm_bwd")
-        du = None
-        if stock:
-            dx2 = dout                                                # grad at x2 = x1 + dropout(f)
-            _k1_bwd(None, None, dout, x2, None, None, None, None, df, None, None, db2, R, C, cfg.p, seed, sd, salt + 2, act)
-        else:
-            dx2 = torch.empty(R, C, dtype=torch.float32, device=dev)  # through ffn_norm2
-            if fuse_ln and db1_in_wgrad:    # ffn_norm2' + dropout' -> df, du = (df W2) * gelu'(u): one launch
-                du = _ln_gemm_bwd(None, dout, None, x2, stats[4], stats[5], nxw, dx2, df, dnxw, dnxb, db2, R, C, cfg.p,
-                                  seed, sd, salt + 2, s_w2, ops.GEMM_GELU_BWD, u)
-            else:
-                _k1_bwd(None, dout, None, x2, stats[4], stats[5], nxw, dx2, df, dnxw, dnxb, db2, R, C, cfg.p, seed, sd,
-                        salt + 2, act)
-        dw2 = wb.add(df, h, sink=k_w2)
-        if du is not None:
-            pass
-        elif own and db1_in_wgrad:
-            du = ops.layer_gemm(df, s_w2, None, True, ops.GEMM_GELU_BWD, aux_in=u)      # (df W2) * gelu'(u), one launch
-        else:
-            dh = df @ s_w2
-            du = torch.empty_like(u)
-            _lib.call("mobgt_gelu_bwd_colsum", _p(dh), _p(u), _p(du), _p(None if db1_in_wgrad else db1), R, F, act,
-                      _stream())
-        dz = ops.layer_gemm(du, s_w1, None, True) if own else du @ s_w1
-        dw1 = wb.add(du, z, db=db1 if db1_in_wgrad else None, sink=k_w1)
-        dx1 = torch.empty(R, C, dtype=torch.float32, device=dev)
-        dy = torch.empty(R, C, dtype=A, device=dev)
-        if fuse_ln:             # ffn_norm1' + residual + dropout' -> dy, da = dy Wo: one launch
-            da = _ln_gemm_bwd(dz, None, dx2, x1, stats[2], stats[3], n1w, dx1, dy, dn1w, dn1b, dbo, R, C, cfg.p, seed, sd,
-                              salt + 1, s_wo, ops.GEMM_BIAS, None).view(G, T, C)
-        else:
-            _k1_bwd(dz, None, dx2, x1, stats[2], stats[3], n1w, dx1, dy, dn1w, dn1b, dbo, R, C, cfg.p, seed, sd, salt + 1, act)
-            da = (ops.layer_gemm(dy, s_wo, None, True) if own else dy @ s_wo).view(G, T, C)
-        dwo = wb.add(dy, a.view(R, C), sink=k_wo)
-        return da, dx1, dw2, dw1, dwo
-
-    @staticmethod
     def backward(ctx, dout):
-        cfg = ctx.cfg
-        G, T, C = ctx.shapes
-        R = G * T
-        x, xa, qkv, a, lse, x1, z, u, h, x2, stats, s_wqkv, s_wo, s_w1, s_w2, n1w, nxw, nnw = ctx.saved_tensors
-        pend = getattr(ctx, "_mobgt_pending", None)     # (model.note_pending_backward: the layer's shadows may be rewritten again)
-        if pend is not None:
-            pend.done()
-        if getattr(ctx, "stock_chain", False):
-            return _FusedLayerFn._backward_preln_chain(ctx, dout, x, xa, qkv, a, lse, x1, z, u, h, x2, stats, s_wqkv, n1w, nxw, nnw)
-        A = cfg.act_dtype
-        act = _DT[A]
-        dev = dout.device
-        seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
-        stock = cfg.variant == "stock"
-        F = s_w1.shape[0]
-        dout = dout.contiguous().view(R, C).float()
-        # every small gradient of the layer in ONE zero-filled buffer:
-        # [dbqkv 3C | dbo C | db1 F | db2 C | dn1w C | dn1b C | dnxw C | dnxb C]
-        small = ctx.small_sink if ctx.small_sink is not None else ops.zeros_f32((3 * C + C + F + C + 4 * C,), dev)
-        o = [0]
-
-        def take(n):
-            t = small[o[0]:o[0] + n]
-            o[0] += n
-            return t
-        dbqkv, dbo, db1, db2, dn1w, dn1b, dnxw, dnxb = take(3 * C), take(C), take(F), take(C), take(C), take(C), take(C), take(C)
-        own = ctx.own_gemm
-        wb = _WgradBatch()
-        k_qkv, k_wo, k_w1, k_w2 = ctx.sinks                          # gradient sinks (or None)
-        db1_in_wgrad = _wgrad_hip(A, F, C, R)                         # then b1's gradient rides on the dW1 kernel
-        if STEP.layer_tails or STEP.tail_check_task is not None:
-            STEP.drop_stale_tails(ops.graph_task_id())
-        pend = STEP.layer_tails.pop(_pending_key(dout), None) if STEP.layer_tails else None
-        # (the 64-row backward chain, R > 4096: b1's gradient is a column sum of du behind it -- the weight gradients are the
-        #  library's there)
-        chain_b = getattr(ctx, "chain_bwd", False) and (db1_in_wgrad or R > 4096) and not stock
-        host = pend is not None and chain_b and pend["R"] == R
-        if pend is not None and not host:
-            _complete_pending(pend)                                   # this layer cannot host it: finish it right here
-            pend = None
-        if chain_b:
-            # d(out) -> ffn_norm2' -> dropout' -> (W2, gelu') -> W1 -> ffn_norm1' + residual -> dropout' -> Wo: one launch
-            bf = dict(dtype=A, device=dev)
-            df, dy, da = torch.empty(R, C, **bf), torch.empty(R, C, **bf), torch.empty(R, C, **bf)
-            du = torch.empty(R, F, **bf)
-            dx1 = torch.empty(R, C, dtype=torch.float32, device=dev)
-            w2t, w1t, wot = cfg.packed_t[:3]
-            vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-            if pend is not None:
-                # ... and, hosted for the layer above: its input gradient is finished in front of the first norm (`dout` holds
-                # its dx1), its four weight gradients run as extra workgroups of this launch
-                it = pend["items"]
-                n = len(it)
-                extra = (_p(pend["dqkv"]), _p(pend["wqt"]), n, (vp * n)(*[t[0].data_ptr() for t in it]),
-                         (i64 * n)(*[t[0].stride(0) for t in it]), (vp * n)(*[t[1].data_ptr() for t in it]),
-                         (i64 * n)(*[t[1].stride(0) for t in it]), (vp * n)(*[t[2].data_ptr() for t in it]),
-                         (i64 * n)(*[t[2].shape[1] for t in it]),
-                         (vp * n)(*[(t[3].data_ptr() if t[3] is not None else None) for t in it]),
-                         (ci * n)(*[t[0].shape[1] for t in it]), (ci * n)(*[t[1].shape[1] for t in it]))
-            else:
-                extra = (None, None, 0, None, None, None, None, None, None, None, None, None)
-            if R > 4096 and (pend is None or not pend["items"]):
-                # the 64-row form: b1's gradient is summed inside (db1 is zero-filled: `small`); it hosts the upper layer's tail
-                # (dout = that layer's dx1; dout + dqkv Wqkv is finished in front of the first norm), not its weight gradients
-                _lib.call("mobgt_layer_chain_bwd_big", _p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                          _p(stats[5]), _p(n1w), _p(nxw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
-                          _p(dy), _p(da), _p(dx1), _p(dnxw), _p(dnxb), _p(db2), _p(dn1w), _p(dn1b),
-                          _p(dbo), _p(None if db1_in_wgrad else db1), R, C, F, cfg.p, seed, _p(sd),
-                          (salt + 1) & 0xFFFFFFFF, (salt + 2) & 0xFFFFFFFF,
-                          _p(pend["dqkv"]) if pend is not None else None,
-                          _p(pend["wqt"]) if pend is not None else None, _stream())
-            else:
-                _lib.call("mobgt_layer_chain_bwd", _p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                          _p(stats[5]), _p(n1w), _p(nxw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
-                          _p(dy), _p(da), _p(dx1), _p(dnxw), _p(dnxb), _p(db2), _p(dn1w), _p(dn1b),
-                          _p(dbo), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                          (salt + 2) & 0xFFFFFFFF, *extra, _p(chain_workspace(dev, C, R)), _stream())
-                if not db1_in_wgrad:
-                    _lib.call("mobgt_colsum", _p(du), _p(db1), R, F, act, _stream())
-            da = da.view(G, T, C)
-            big_items = None
-            if R > 4096 and forms.on("wgrad_big") and A == torch.bfloat16 and not db1_in_wgrad:
-                # past 4 096 rows: all four weight gradients of the layer (and dbqkv) as ONE launch behind the attention backward
-                # (csrc/wgradbig.hip, round 6; before: three library split-K GEMMs, the grouped kernel for dWo, a column-sum launch)
-                big_items = [(df, h, None, k_w2), (du, z, None, k_w1), (dy, a.view(R, C), None, k_wo)]
-                if not ops.layer_wgrad_big_ok(big_items):
-                    big_items = None
-            if big_items is None:
-                dw2 = wb.add(df, h, sink=k_w2)
-                dw1 = wb.add(du, z, db=db1 if db1_in_wgrad else None, sink=k_w1)
-                dwo = wb.add(dy, a.view(R, C), sink=k_wo)
-        else:
-            big_items = None
-            da, dx1, dw2, dw1, dwo = _FusedLayerFn._bwd_launches(ctx, cfg, wb, dout, x1, z, u, h, x2, a, stats, s_wo, s_w1, s_w2,
-                                                                n1w, nxw, dbo, db1, db2, dn1w, dn1b, dnxw, dnxb, G, T, C, F, A,
-                                                                act, dev, own, stock, db1_in_wgrad)
-        dqkv = torch.empty(G, T, 3 * C, dtype=A, device=dev)
-        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-        ops._attn_bwd(q, k, v, a, lse, da, dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:], cfg.pack, cfg.scale,
-                      cfg.p_att, seed ^ (salt * 0x9E3779B1), sd)
-        dqkv2 = dqkv.view(R, 3 * C)
-        if big_items is not None and ops.layer_wgrad_big_ok([(dqkv2, xa.view(R, C), dbqkv, k_qkv)]):
-            dw2, dw1, dwo, dwqkv = ops.layer_wgrad_big(big_items + [(dqkv2, xa.view(R, C), dbqkv, k_qkv)], R)
-        else:
-            if big_items is not None:
-                dw2, dw1, dwo = ops.layer_wgrad_big(big_items, R)
-            dwqkv = wb.add(dqkv2, xa, db=dbqkv, sink=k_qkv)
-        defer = (forms.on("defer_tail") and getattr(ctx, "below_hosts", False) and own and not stock and forms.on("tail") and len(wb.items) == 4
-                 and R <= _DEFER_MAX_R[0] and dx1.data_ptr() % 16 == 0 and dqkv2.is_contiguous() and ctx.small_sink is not None
-                 and all(k is not None for k in ctx.sinks))
-        big_defer = (not defer and forms.on("defer_tail") and getattr(ctx, "below_hosts", False) and not stock and forms.on("tail") and R > 4096
-                     and dx1.data_ptr() % 16 == 0 and dqkv2.is_contiguous() and dqkv2.data_ptr() % 16 == 0)
-        if big_defer:
-            # past 4 096 rows: the 64-row chain of the layer below finishes dx = dx1 + dqkv Wqkv in front of its first norm (a
-            # 20 us library GEMM otherwise); the weight gradients are the library's and are issued here
-            wb.flush(tail=None)
-            _park_tail(dx1, dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=[], R=R, big=True)
-            rode = True
-            dx = dx1
-        elif defer:
-            # nothing more is launched for this layer: the chain launch of the layer below finishes dx and the weight gradients
-            # (parked as FRESH views of the gradient buffers: autograd's AccumulateGrad clones a returned gradient that anything
-            # else still references, and the clone -- taken before the buffers are filled -- would later be copied over them)
-            items = [(g_, x_, dw_[:], db_[:] if db_ is not None else None) for g_, x_, dw_, db_ in wb.items]
-            _park_tail(dx1, dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=items, R=R)
-            wb.items = []
-            rode = True
-            dx = dx1
-        elif (stock and STEP.wgrad_on and wb.items and R <= _DEFER_MAX_R[0] and all(k is not None for k in ctx.sinks)
-              and all(g_.dtype == torch.bfloat16 and x_.dtype == torch.bfloat16 for g_, x_, _, _ in wb.items)):
-            # stock variant inside a train step: nothing downstream reads a weight gradient and all four land in their sinks, so
-            # they join the step's ONE grouped launch (ops.flush_deferred_wgrads) instead of one 7 us launch per layer -- parked
-            # as FRESH views (see above: AccumulateGrad clones a returned gradient that anything else still references)
-            for g_, x_, dw_, db_ in wb.items:
-                STEP.wgrad_items.append((g_, x_, None, None, (1.0, 1.0, 1.0), dw_[:], db_[:] if db_ is not None else None, False))
-            wb.items = []
-            rode = False
-        else:
-            # fq variant, own GEMMs: dx = dx1 + dqkv Wqkv rides in the weight-gradient launch
-            rode = wb.flush(tail=(dqkv2, s_wqkv, dx1) if (own and not stock and forms.on("tail")) else None)
-        if rode:
-            dx = dx1
-        elif stock:                                                     # back through self_attention_norm
-            dz0 = ops.layer_gemm(dqkv2, s_wqkv, None, True) if own else dqkv2 @ s_wqkv
-            dx = torch.empty(R, C, dtype=torch.float32, device=dev)
-            _k1_bwd(dz0, None, dx1, x.view(R, C), stats[0], stats[1], nxw, dx, None, dnxw, dnxb, None, R, C, 0.0, seed, sd,
-                    salt, act)
-        elif A == torch.float32:                                      # dx1 is this function's own buffer: accumulate onto it
-            dx = torch.addmm(dx1, dqkv2, s_wqkv, out=dx1)
-        elif own:
-            dx = ops.layer_gemm(dqkv2, s_wqkv, None, True, ops.GEMM_ADD, aux_in=dx1)     # dx1 + dqkv Wqkv, f32, in place
-        else:
-            dx = _addmm_f32(dx1, dqkv2, s_wqkv, inplace=True)
-        return (dx.view(G, T, C), None, None, None, None, None, dwqkv[:C], dbqkv[:C], dwqkv[C:2 * C], dbqkv[C:2 * C], dwqkv[2 * C:],
-                dbqkv[2 * C:], dwo, dbo, dn1w, dn1b, dnxw, dnxb, dw1, db1, dw2, db2) + ((None, None) if stock else ())
-
-    @staticmethod
-    def _backward_preln_chain(ctx, dout, x, xa, qkv, a, lse, x1, z, u, h, x2, stats, s_wqkv, n1w, nxw, nnw):
-        """model.py:479-489 backwards through the chain kernel (mobgt_layer_chain_bwd_preln):
+        """fq / stock as separate launches or through the fq backward chain; pre-LN chain (model.py:479-489 backwards,
+        mobgt_layer_chain_bwd_preln):
             [hosted for the layer above:  t = dqkv_above Wqkv_above;  dx2 = dout + norm_above'(t)]    else dx2 = dout
             df = dropout'(dx2);  du = (df W2) gelu'(u);  dz = du W1;  dx1 = dx2 + ffn_norm'(dz);  dy = dropout'(dx1);  da = dy Wo
-        then the attention backward; then either this layer's own norm (a layer without a chained input: dx = dx1 +
-        self_attention_norm'(dqkv Wqkv), two launches) or nothing -- the layer below finishes dx in ITS chain launch."""
-        cfg = ctx.cfg
+        then the attention backward, the four weight gradients and the input gradient, each the way plan_backward names."""
+        cfg, plan, sinks = ctx.cfg, ctx.plan, ctx.sinks
         G, T, C = ctx.shapes
-        R = G * T
-        A = cfg.act_dtype
-        act = _DT[A]
-        dev = dout.device
-        seed, sd, salt = cfg.seed, cfg.seed_dev, cfg.salt
-        F = u.shape[1]
+        R, F, A, dev = plan.R, plan.F, cfg.act_dtype, dout.device
+        sv = _Saved(*ctx.saved_tensors)
+        busy = getattr(ctx, "_mobgt_pending", None)     # (model.note_pending_backward: the layer's shadows may be rewritten again)
+        if busy is not None:
+            busy.done()
+        preln = plan.body == "preln_chain"
         dout = dout.contiguous().view(R, C).float()
-        n8 = 3 * C + C + F + C + 2 * C
-        small = ctx.small_sink if ctx.small_sink is not None else ops.zeros_f32((n8,), dev)
-        o = [0]
-
-        def take(n):
-            t = small[o[0]:o[0] + n]
-            o[0] += n
-            return t
-        dbqkv, dbo, db1, db2, dn1w, dn1b = take(3 * C), take(C), take(F), take(C), take(C), take(C)
-
-        def dst(sink):
-            return sink[:] if sink is not None else ops.zeros_f32((C,), dev)
-        dnxw, dnxb = (dst(ctx.nx_sinks[0]), dst(ctx.nx_sinks[1])) if nxw is not None else (None, None)
-        dnnw, dnnb = (dst(ctx.nn_sinks[0]), dst(ctx.nn_sinks[1])) if nnw is not None else (None, None)
-        wb = _WgradBatch()
-        k_qkv, k_wo, k_w1, k_w2 = ctx.sinks
-        if STEP.layer_tails or STEP.tail_check_task is not None:
-            STEP.drop_stale_tails(ops.graph_task_id())
-        pend = STEP.layer_tails.pop(_pending_key(dout), None) if STEP.layer_tails else None
-        if pend is not None and not (pend.get("preln") and nnw is not None and pend["R"] == R):
-            _complete_pending(pend)                    # (not this layer's kind of guest: finish it as its own launches)
-            pend = None
-        bf = dict(dtype=A, device=dev)
-        df, dy, da = torch.empty(R, C, **bf), torch.empty(R, C, **bf), torch.empty(R, C, **bf)
-        du = torch.empty(R, F, **bf)
-        dx1 = torch.empty(R, C, dtype=torch.float32, device=dev)
-        w2t, w1t, wot = cfg.packed_t[:3]
-        tail = (_p(pend["dqkv"]), _p(pend["wqt"])) if pend is not None else (None, None)
-        _lib.call("mobgt_layer_chain_bwd_preln", _p(dout), _p(x2), _p(x1), _p(u), _p(stats[2]), _p(stats[3]), _p(stats[4]),
-                  _p(stats[5]), _p(n1w), _p(nnw), _p(w2t), _p(w1t), _p(wot), _p(df), _p(du),
-                  _p(dy), _p(da), _p(dx1), _p(dnnw), _p(dnnb), _p(db2), _p(dn1w), _p(dn1b),
-                  _p(dbo), R, C, F, cfg.p, seed, _p(sd), (salt + 1) & 0xFFFFFFFF,
-                  (salt + 2) & 0xFFFFFFFF, *tail, 0, None, None, None, None, None, None, None,
-                  None, None, _p(chain_workspace(dev, C, R)), _stream())
-        dw2 = wb.add(df, h, sink=k_w2)
-        dw1 = wb.add(du, z, db=db1, sink=k_w1)
-        dwo = wb.add(dy, a.view(R, C), sink=k_wo)
-        dqkv = torch.empty(G, T, 3 * C, dtype=A, device=dev)
-        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-        ops._attn_bwd(q, k, v, a, lse, da.view(G, T, C), dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:], cfg.pack, cfg.scale,
-                      cfg.p_att, seed ^ (salt * 0x9E3779B1), sd)
-        dqkv2 = dqkv.view(R, 3 * C)
-        dwqkv = wb.add(dqkv2, xa, db=dbqkv, sink=k_qkv)
-        # the four weight gradients: inside a train step they join the step's ONE grouped launch (as the separate-launch stock
-        # layer's do), else their own grouped launch now
-        if (STEP.wgrad_on and wb.items and R <= _DEFER_MAX_R[0] and all(k_ is not None for k_ in ctx.sinks)
-                and all(g_.dtype == torch.bfloat16 and x_.dtype == torch.bfloat16 for g_, x_, _, _ in wb.items)):
-            for g_, x_, dw_, db_ in wb.items:
-                STEP.wgrad_items.append((g_, x_, None, None, (1.0, 1.0, 1.0), dw_[:], db_[:] if db_ is not None else None, False))
-            wb.items = []
+        if preln:
+            sm = _SmallGrads(*_small_grads(sinks, C, F, 6, dev), *_norm_grads(sinks.nx, sv.nxw is not None, C, dev))
+            dnn = _norm_grads(sinks.nn, sv.nnw is not None, C, dev)
         else:
-            wb.flush()
-        if ctx.chained_in:
-            # nothing more for this layer: the layer below opens its chain launch with  dx2 = dx1 + norm'(dqkv Wqkv)
-            _park_tail(dx1, dqkv=dqkv2, wqkv=s_wqkv, wqt=cfg.packed_t[3], items=[], R=R, preln=True)
-            dx = dx1
-        else:                                                           # back through this layer's own self_attention_norm
-            dz0 = ops.layer_gemm(dqkv2, s_wqkv, None, True)
-            dx = torch.empty(R, C, dtype=torch.float32, device=dev)
-            _k1_bwd(dz0, None, dx1, x.view(R, C), stats[0], stats[1], nxw, dx, None, dnxw, dnxb, None, R, C, 0.0, seed, sd, salt, act)
-        return (dx.view(G, T, C), None, None, None, None, None, dwqkv[:C], dbqkv[:C], dwqkv[C:2 * C], dbqkv[C:2 * C], dwqkv[2 * C:],
-                dbqkv[2 * C:], dwo, dbo, dn1w, dn1b, dnxw, dnxb, dw1, db1, dw2, db2, dnnw, dnnb)
+            sm, dnn = _SmallGrads(*_small_grads(sinks, C, F, 8, dev)), (None, None)
+        pend = _take_tail(dout)
+        # (not asked about: dx1, dqkv and the operands of mobgt_layer_wgrad_big beyond their size -- this pass allocates them itself)
+        bp = plan_backward(plan, _forms_on(BACKWARD_FORMS), STEP.wgrad_on,
+                           Tail(pend["kind"], pend["R"], bool(pend["items"])) if pend is not None else None,
+                           sum(_wgrad_hip(A, m, n, R) for m, n in ((C, F), (F, C), (C, C), (3 * C, C))),
+                           all(k is not None for k in sinks[:4]), sinks.small is not None, R * max(3 * C, F) * 2 < (1 << 31))
+        if pend is not None and not bp.host:
+            _complete_pending(pend)                     # this layer cannot host it: finish it right here, as its own launches
+            pend = None
+        wb = _WgradBatch()
+        if bp.entry is None:
+            da, dx1, dw2, dw1, dwo = _backward_launches(plan, bp, cfg, wb, dout, sv, sm, sinks)
+        else:
+            norm = (sv.nnw,) + dnn if preln else (sv.nxw, sm.dnxw, sm.dnxb)
+            df, du, dy, da, dx1 = _chain_bwd(bp.entry, plan, cfg, sv, dout, norm, sm, pend)
+            if bp.db1_colsum:
+                _lib.call("mobgt_colsum", _p(du), _p(sm.db1), R, F, _DT[A], _stream())
+            three = [(df, sv.h, None, sinks.w2), (du, sv.z, sm.db1 if plan.db1_in_wgrad else None, sinks.w1),
+                     (dy, sv.a.view(R, C), None, sinks.wo)]
+            if bp.wgrads != "big":
+                dw2, dw1, dwo = [wb.add(g_, x_, db=db_, sink=k_) for g_, x_, db_, k_ in three]
+        dqkv = torch.empty(G, T, 3 * C, dtype=A, device=dev)
+        q, k, v = sv.qkv[..., :C], sv.qkv[..., C:2 * C], sv.qkv[..., 2 * C:]
+        ops._attn_bwd(q, k, v, sv.a, sv.lse, da.view(G, T, C), dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:], cfg.pack,
+                      cfg.scale, cfg.p_att, cfg.seed ^ (cfg.salt * 0x9E3779B1), cfg.seed_dev)
+        dqkv2 = dqkv.view(R, 3 * C)
+        items = []
+        if bp.wgrads == "big":
+            # (csrc/wgradbig.hip, round 6; before: three library split-K GEMMs, the grouped kernel for dWo, a column-sum launch)
+            four = three + [(dqkv2, sv.xa.view(R, C), sm.dbqkv, sinks.qkv)]
+            assert ops.layer_wgrad_big_ok(four)
+            dw2, dw1, dwo, dwqkv = ops.layer_wgrad_big(four, R)
+        else:
+            dwqkv = wb.add(dqkv2, sv.xa, db=sm.dbqkv, sink=sinks.qkv)
+        if bp.wgrads == "below":                        # (parked as fresh views: _join_step_wgrads says why)
+            items = [(g_, x_, dw_[:], db_[:] if db_ is not None else None) for g_, x_, dw_, db_ in wb.items]
+            wb.items = []
+        elif bp.wgrads == "step":
+            _join_step_wgrads(wb)
+        else:
+            rode = wb.flush(tail=(dqkv2, sv.s_wqkv, dx1) if bp.dx == "tail" else None)
+            assert rode == (bp.dx == "tail")
+        dx = _finish_dx(plan, bp, cfg, sv, sm, dqkv2, dx1, items)
+        return (dx.view(G, T, C), None, None, None, None, None, dwqkv[:C], sm.dbqkv[:C], dwqkv[C:2 * C], sm.dbqkv[C:2 * C],
+                dwqkv[2 * C:], sm.dbqkv[2 * C:], dwo, sm.dbo, sm.dn1w, sm.dn1b, sm.dnxw, sm.dnxb, dw1, sm.db1, dw2, sm.db2) \
+            + (dnn if plan.variant == "stock" else ())
 
 
 def fused_encoder_layer(x, pack, cfg, shadows, params, xa_pre=None, qkv_pre=None):
