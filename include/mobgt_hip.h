@@ -165,6 +165,8 @@ int mobgt_build_bias(const float* attn_bias, const void* rel_pos, const void* po
  *        MOBGT_BF16: n_slices bf16 buffers of that shape, slice_stride ELEMENTS apart (one per layer, as written
  *        by mobgt_attn_bias_bwd), summed here in f32.
  * Entries where attn_bias is -inf carry no gradient and are skipped.
+ * ld_bias as in mobgt_build_bias: a multiple of 32, >= N + 1 (MOBGT_EALIGN otherwise).  A dbias value that is not finite reaches
+ * exactly the table entries its pair names, as in a float sum.
  */
 int mobgt_build_bias_bwd(const void* dbias, int dbias_dtype, int n_slices, int64_t slice_stride,
                          const float* attn_bias, const void* rel_pos, const void* poi_pos,

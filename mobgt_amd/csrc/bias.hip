@@ -738,23 +738,29 @@ __device__ __forceinline__ void build_bias_bwd_body(const BuildParams& p, int ld
                 // the COMPILER has to be kept from moving this round's writes above the previous round's reads
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
+                // a pair whose gradient is not finite stays out of the matrix product -- there its NaN would meet the zeros of
+                // the other 15 one-hot rows (0 x NaN = NaN) and poison rows a float sum leaves alone: it takes the atomic path
+                bool fin = true;
+#pragma unroll
+                for (int h = 0; h < HH; ++h) fin = fin && fabsf(ge[h]) < INFINITY;
 #pragma unroll
                 for (int h = 0; h < HH; ++h) {
-                    const bf16_t hi = (bf16_t)ge[h];
+                    const float gh = fin ? ge[h] : 0.f;
+                    const bf16_t hi = (bf16_t)gh;
                     hop_b[half][h][k] = hi;
-                    hop_b[half][8 + h][k] = (bf16_t)(ge[h] - (float)hi);
+                    hop_b[half][8 + h][k] = (bf16_t)(gh - (float)hi);
                 }
 #pragma unroll
                 for (int d = 0; d < HOP_DMAX; ++d) {
                     if (d < p.D) {
                         const int raw = HOPW ? (int)((hop_w[HOPW ? d / 4 : 0] >> (8 * (d & 3))) & 0xffu) : hop_id[HOPW ? 0 : d];
                         const int idx = pairlive ? raw : 0;
-                        if (idx >= 16 && idx < p.n_edge) {         // rare id: straight to the atomic unit
+                        if ((idx >= 16 || !fin) && idx < p.n_edge) {         // rare id: straight to the atomic unit
 #pragma unroll
                             for (int h = 0; h < HH; ++h) atomicAdd(&p.d_hop[((int64_t)d * p.n_edge + idx) * HH + h], ge[h]);
                         }
                         // staged as a 16-bit one-hot mask (bit e); 0 = "no row here"
-                        hop_e[wave][d][lane] = idx < 16 ? (uint16_t)(1u << idx) : (uint16_t)0;
+                        hop_e[wave][d][lane] = (idx < 16 && fin) ? (uint16_t)(1u << idx) : (uint16_t)0;
                     }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1033,6 +1039,8 @@ int fill_bias_bwd(BuildParams& p, const void* dbias, int dbias_dtype, int n_slic
                   float* d_hop_table, float* d_vdist, int G, int N, int H, int D_in, int D, int F, int n_rel, int n_poi, int n_edge,
                   int64_t ld_bias) {
     if (G <= 0 || N <= 0 || H > BIAS_MAXH || D < 0 || D > D_in || F <= 0 || n_slices < 1) return MOBGT_EBADDIM;
+    // (as the forward: the rows of dBias are read as 16-byte pieces of a [T, ld] layout, and ld < T would index past them)
+    if (ld_bias % 32 != 0 || ld_bias < N + 1) return MOBGT_EALIGN;
     if (dbias_dtype != MOBGT_F32 && dbias_dtype != MOBGT_BF16) return MOBGT_EDTYPE;
     p = BuildParams{};
     p.dbias = dbias; p.dbias_bf16 = dbias_dtype == MOBGT_BF16; p.n_slices = p.dbias_bf16 ? n_slices : 1;
