@@ -42,7 +42,10 @@ extern "C" {
  * version 1 -- ADVICE r5; version 2 = that ABI; version 3 = round 6).  mobgt_amd/_lib.py derives its SIGNATURES table and its
  * constants from this file (mobgt_amd/_cabi.py: one-statement prototypes over int / int64_t / float / double /
  * uint64_t / uint32_t and pointers, integer #defines named MOBGT_*) and refuses a library whose version differs from the number
- * below: a new entry point is its prototype here, its definition in csrc/ and its caller. */
+ * below: a new entry point is its prototype here, its definition in csrc/ and its caller.
+ * Shape limits and dispatch thresholds that a caller has to predict (which form a call takes, which shapes it refuses) are
+ * `#define MOBGT_<NAME> <decimal int>` beside the prototypes they govern: csrc/ names its own constants from them and the Python
+ * layer reads them through the same table, so neither side keeps a copy. */
 #define MOBGT_ABI_VERSION 3
 int mobgt_abi_version(void);
 const char* mobgt_build_info(void);
@@ -152,6 +155,13 @@ int mobgt_bias_pack(const void* src, int src_dtype, int64_t s_g, int64_t s_h, in
  * vdist     : [H] graph_token_virtual_distance.weight (added to column 0 of rows 1..N only, model.py:139-151)
  * bias, bias_t : outputs, [G, H, T, ld_bias] bias_dtype (see mobgt_attn_bias_fwd); columns T..ld_bias-1 = -inf
  */
+/* Pairs G (N+1)^2 from which a batch is LONG: mobgt_build_bias (H = 8) takes its super-tile form and mobgt_build_bias_bwd its
+ * persistent-workgroup form, and mobgt_small_gcn_bwd_bias refuses the passenger.  Callers choose by it where the gradient runs
+ * (ops.take_bias_bwd_job: in the GCN launch only below it; ops._bias_bwd_beside: on a side stream only from it on). */
+#define MOBGT_BIAS_LONG_PAIRS 1048576
+/* Hops D of the matrix-core hop histogram of mobgt_build_bias_bwd (F = 1, H = 8; more hops take the atomic form) and so of the
+ * passenger form of mobgt_small_gcn_bwd_bias, which refuses D above it (ops.take_bias_bwd_job asks first). */
+#define MOBGT_HOP_DMAX 20
 int mobgt_build_bias(const float* attn_bias, const void* rel_pos, const void* poi_pos, const void* edge_input,
                      const float* rel_table, const float* poi_table, const float* hop_table, const float* vdist,
                      void* bias, void* bias_t,
@@ -174,7 +184,7 @@ int mobgt_build_bias_bwd(const void* dbias, int dbias_dtype, int n_slices, int64
                          float* d_rel_table, float* d_poi_table, float* d_hop_table, float* d_vdist,
                          int G, int N, int H, int D_in, int D, int F, int n_rel, int n_poi, int n_edge,
                          int64_t ld_bias, int idx_dtype, int edge_dtype, void* stream);
-/* Round 6: the persistent workgroups of the LONG-batch form of mobgt_build_bias_bwd (G (N+1)^2 >= 2^20 pairs: one 8-wave
+/* Round 6: the persistent workgroups of the LONG-batch form of mobgt_build_bias_bwd (G (N+1)^2 >= MOBGT_BIAS_LONG_PAIRS: one 8-wave
  * workgroup per compute unit walks the pairs) for the launches that follow: 0 = one per compute unit (default), n = at most n.  A
  * caller that issues the launch on a side stream under other work (the tail of the backward pass: autograd of
  * model_fqandtoyo.py:1143-1216 needs nothing but the dBias slices) leaves a quarter of the units to that work; no effect on
@@ -301,6 +311,13 @@ int mobgt_node_index(const void* x, int x_dtype, int64_t xs_g, int64_t xs_n, con
                      int64_t ts_n, const int64_t* poi2cat, const void* in_degree, const void* out_degree, int deg_dtype,
                      int64_t* idx, float* real, int G, int N, int rows_only, void* stream);
 
+/* Shapes of the mobgt_skinny_linear_* entry points; MOBGT_EBADDIM past them (ops.skinny_linear_ok / skinny_linear_gtl_ok ask
+ * first and route other shapes to the GEMM path).  All of them: G <= MAX_G rows, K <= MAX_K, K % 4 == 0.  The matrix-core ones
+ * (_fwd_mfma, _gtl, _rank_metrics) further: K <= MFMA_MAX_K, K % MFMA_K_STEP == 0. */
+#define MOBGT_SKINNY_MAX_G 16
+#define MOBGT_SKINNY_MAX_K 512
+#define MOBGT_SKINNY_MFMA_MAX_K 448
+#define MOBGT_SKINNY_MFMA_K_STEP 64
 /* nn.Linear on a handful of rows (G <= 16, K <= 512, K % 4 == 0; f32): y [G,V] = x [G,K] w[V,K]^T + b[V] -- the
  * classifier head out_proj on the graph tokens (model_fqandtoyo.py:1394) -- and its backward: dx [G,K] (or NULL),
  * dw [V,K] and db [V] (or NULL), all OVERWRITTEN.  Each product streams w / writes dw exactly once.  db is a by-product of the
@@ -396,9 +413,13 @@ int mobgt_rank_metrics_masked(const float* scores, const int64_t* target, int64_
 int mobgt_rank_metrics_masked_rows(const float* scores, const int64_t* target, int64_t target_offset, int64_t G, int64_t V,
                                    const uint32_t* allow, int64_t ld_allow, const void* hist, int hist_dtype, int64_t ld_hist,
                                    int64_t n_hist_cols, int64_t hist_offset, int flags, double* acc, void* work, void* stream);
+/* Largest k of mobgt_topk_rows and its _masked / _masked_rows siblings (MOBGT_EBADDIM past it).  ops.TOPK_MAX: callers that let a
+ * user choose k refuse a larger one before any launch (train.PredictLoop). */
+#define MOBGT_TOPK_MAX_K 64
 /* Row-wise top-k of stored scores: the ranked next-POI list (Graphormer.recommend_step, train.PredictLoop), replacing the
  * torch.topk a caller ran on test_step's y_pred (:1530-1544) by hand.  scores [G, V] f32 with row stride ld >= V (elements);
- * 1 <= k <= 64, k <= V, G <= 65535, else MOBGT_EBADDIM.  Writes ids [G, k] int64 = column + col_offset and vals [G, k] f32 equal to
+ * 1 <= k <= MOBGT_TOPK_MAX_K, k <= V, G <= 65535, else MOBGT_EBADDIM.  Writes ids [G, k] int64 = column + col_offset and
+ * vals [G, k] f32 equal to
  *     torch.sort(scores, dim=1, descending=True, stable=True)[:, :k]   (values, indices + col_offset)
  * bit for bit: descending score; equal scores in ascending column order (the tie rule of mobgt_target_rank's ACC position, so
  * target in ids[g, :k] <=> rank[2g] < k); -0.0 ties with +0.0; NaN of either sign above +inf; vals are the stored bits.
@@ -754,14 +775,17 @@ int mobgt_small_gemm_f32_act(const float* a, int64_t lda, const float* a_mask, f
  * Written: x1, x2, out f32 [R,C]; z, out_a (= bf16(out)) [R,C], u, h [R,F], qkv_next [R,3C] bf16; mean / rstd [R] f32 of
  * both norms.  wq_next / bq_next / qkv_next null for the last layer.  Dropout masks: those of mobgt_dropout_add_ln_fwd
  * with salt1 / salt2.  (C, F) in {(128, 1024), (192, 1024), (256, 1024)}.  ws: see mobgt_chain_ws_bytes (may be null).
- * R <= 4096: 16-row blocks on clusters of workgroups (one workgroup per block without ws); R > 4096: 64-row workgroups
- * (layer_chain_fwd_big_kernel), same results up to the f32 summation order of h w2^T (three parts). */
+ * R <= MOBGT_CHAIN_BIG_ROWS: 16-row blocks on clusters of workgroups (one workgroup per block without ws); past it: 64-row
+ * workgroups (layer_chain_fwd_big_kernel), same results up to the f32 summation order of h w2^T (three parts). */
 /* bf16 weight [N,K] row-major -> MFMA operand order (chain.hip): the 16 bytes W[16g + j][32s + 8q .. +7] go to byte offset
  * ((g K/32 + s) 64 + j + 16q) * 16, so that a wave's B-operand load is one contiguous KB.  n <= 96 jobs in one launch;
  * N % 16 == 0, K % 32 == 0.  transposed[i] != 0: src is [K,N] row-major and its TRANSPOSE is packed (the operand of
  * dX = dY W); transposed may be null. */
 int mobgt_pack_mfma_b(int n, const void* const* src, void* const* dst, const int* N, const int* K, const int* transposed,
                       void* stream);
+/* Rows R past which mobgt_layer_chain_fwd / _bwd take the 64-row form.  The caller packs a layer's weights for the form that
+ * will run and plans its launches by it (layer_plan.BIG_R; model.pack_layer_weights): R <= it and R > it need different packs. */
+#define MOBGT_CHAIN_BIG_ROWS 4096
 int mobgt_layer_chain_fwd(const void* a, const float* x, const void* wo, const void* bo, const float* n1w, const float* n1b,
                           const void* w1, const void* b1, const void* w2, const void* b2, const float* nxw, const float* nxb,
                           const void* wq_next, const void* bq_next, float* x1, void* z, void* u, void* h, float* x2, float* out,
@@ -778,7 +802,8 @@ int mobgt_layer_chain_fwd(const void* a, const float* x, const void* wo, const v
  * then holds only that layer's dx1 and dout + dqkv Wqkv is formed here, per row block; wg_*: n_wg <= 4 weight-gradient
  * problems dW [M,N] += g^T x (+ db [M] += column sums of g) over the same R rows, bf16 operands as mobgt_linear_wgrad, run
  * by extra workgroups of this launch on the compute units its 16-row blocks leave idle.
- * R > 4096: the 64-row form (layer_chain_bwd_big_kernel) -- post-LN layers only, and through THIS entry point without guests:
+ * R > MOBGT_CHAIN_BIG_ROWS: the 64-row form (layer_chain_bwd_big_kernel) -- post-LN layers only, and through THIS entry point
+ * without guests:
  * tail_dqkv / tail_wqkv_t null and n_wg == 0, else MOBGT_EBADDIM (mobgt_layer_chain_bwd_big hosts a tail); b1's gradient is then
  * the caller's mobgt_colsum of du. */
 int mobgt_layer_chain_bwd(const float* dout, const float* x2, const float* x1, const void* u, const float* mean1,
@@ -789,8 +814,8 @@ int mobgt_layer_chain_bwd(const float* dout, const float* x2, const float* x1, c
                           const void* tail_dqkv, const void* tail_wqkv_t, int n_wg, const void* const* wg_g,
                           const int64_t* wg_ldg, const void* const* wg_x, const int64_t* wg_ldx, float* const* wg_dw,
                           const int64_t* wg_ldw, float* const* wg_db, const int* wg_M, const int* wg_N, void* ws, void* stream);
-/* The 64-row form of mobgt_layer_chain_bwd on its own entry point (what that call dispatches to past 4 096 rows, for R of any
- * size): the same arguments without the weight-gradient passengers and the workspace, plus db1 [F] f32 -- b1's gradient, the
+/* The 64-row form of mobgt_layer_chain_bwd on its own entry point (what that call dispatches to past MOBGT_CHAIN_BIG_ROWS, for R
+ * of any size): the same arguments without the weight-gradient passengers and the workspace, plus db1 [F] f32 -- b1's gradient, the
  * column sums of du, ACCUMULATED like the other small gradients (null: not formed).  tail_dqkv / tail_wqkv_t as there (the layer
  * above's input gradient dout + dqkv Wqkv finished in front of the first norm; both null: none).  Row tensors 16-byte aligned. */
 int mobgt_layer_chain_bwd_big(const float* dout, const float* x2, const float* x1, const void* u, const float* mean1,
@@ -823,6 +848,10 @@ int mobgt_layer_chain_bwd_preln(const float* dout, const float* x2, const float*
  * never need resetting).  Same results as the one-workgroup form up to the f32 summation order of h w2^T and du w1 (NCL
  * partial sums).  ws = null: always the one-workgroup form.  MOBGT_CHAIN_NCL=1|2|4 caps the cluster size. */
 int64_t mobgt_chain_ws_bytes(void);
+/* Workgroups per 16-row block (4, 2 or 1) that the two chain launches use for R rows when they are given a `ws`, on the current
+ * device: the launch geometry a `ws` carries packets of.  A caller that keeps workspaces keys them by it
+ * (fused_layer.chain_workspace), so that packets of one geometry are never read by another.  Host code; launches nothing. */
+int mobgt_chain_cluster_size(int64_t R);
 /* Peer waits that give up (round 4; they used to trap, which kills the process -- under data parallelism the rank): a
  * workgroup of the cluster form that does not see its partners' packets within the poll limit counts itself in the 32-bit word at
  * byte offset mobgt_chain_ws_fault_offset() of `ws` and carries on (its results are garbage); the host reads / clears that word
@@ -899,8 +928,8 @@ int mobgt_small_gcn_bwd(const float* g, const float* ax, const float* a_t, const
                         float slope, float dropout_p, uint64_t seed, const uint64_t* seed_dev, uint32_t salt, void* stream);
 /* The same launch carrying mobgt_build_bias_bwd (with_bias != 0: its arguments follow, same meaning) as passenger workgroups
  * on the compute units the network leaves idle.  Covers the short-batch instantiation only -- idx_dtype MOBGT_I16, edge_dtype
- * MOBGT_U8, H = 8, F = 1, 0 < D <= 20, G (N+1)^2 < 2^20 -- else MOBGT_EBADDIM (callers then use the two launches).  Results as
- * the two launches (f32 atomics in another order). */
+ * MOBGT_U8, H = 8, F = 1, 0 < D <= MOBGT_HOP_DMAX, G (N+1)^2 < MOBGT_BIAS_LONG_PAIRS -- else MOBGT_EBADDIM (callers then use the
+ * two launches).  Results as the two launches (f32 atomics in another order). */
 int mobgt_small_gcn_bwd_bias(const float* g, const float* ax, const float* a_t, const float* w1, const float* w2, const float* h1,
                              const float* t, const float* h2, const float* t2, float* dw0, float* db0, float* dw1, float* db1,
                              float* dw2, float* db2, float* dt2, float* dt, int* counter, int n, int K0, int H1, int H2, int H3,

@@ -47,11 +47,11 @@ candidates per sample): the kernels' reference and the CPU form."""
 import numpy as np
 import torch
 
-from . import metrics
+from . import _baseline, metrics
 
 ORDERS = {"user": 0, "global": 1, "popularity": 2}                     # (= _baseline.ORDER_*)
-DEVICE_MAX_L = 4096                                                     # (= _baseline.MAX_L)
-MAX_K = 64                                                              # (= _baseline.MAX_K)
+DEVICE_MAX_L = _baseline.MAX_L                                          # (the header's: include/mobgt_baseline.h)
+MAX_K = _baseline.MAX_K
 _KS = (1, 5, 10, 20)
 
 
@@ -317,7 +317,6 @@ class MarkovBaseline:
         if self.device.type != "cuda":
             rank, revisit = ranks_host(*self._fitted_on, samples, order, P=self.P)
             return torch.from_numpy(rank), torch.from_numpy(revisit)
-        from . import _baseline
         from .ops import _p, _stream
         with torch.cuda.device(self.device):
             d_seq, d_off, d_users, S, M, d_session, d_cut, Q = self._upload(samples, "MarkovBaseline.ranks")
@@ -335,7 +334,6 @@ class MarkovBaseline:
         mode, k = _order(order), _k(k)
         if self.device.type != "cuda":
             return torch.from_numpy(topk_host(*self._fitted_on, samples, order, k, P=self.P))
-        from . import _baseline
         from .ops import _p, _stream
         with torch.cuda.device(self.device):
             d_seq, d_off, d_users, S, M, d_session, d_cut, Q = self._upload(samples, "MarkovBaseline.recommend")

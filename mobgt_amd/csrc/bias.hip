@@ -456,7 +456,9 @@ constexpr int HOP_LDS_ROWS = 16;      // edge ids < 16 (count <= 12) accumulate 
 // whole tile.  This replaces 20 ballot/shuffle key-combining rounds per 64 pairs (~5000 VALU instructions; the
 // kernel ran at 54 % VALU utilisation with 68 % of wave time parked) by ~1300 + 40 MFMAs.  Edge ids >= 16 (a
 // transition seen > 14 times in one trajectory) go to the atomic unit directly.
-constexpr int HOP_DMAX = 20;
+constexpr int HOP_DMAX = MOBGT_HOP_DMAX;
+// pairs from which a batch is long: the forward's super-tile form, the backward's persistent workgroups; no passenger in the GCN launch
+constexpr int64_t BIAS_LONG_PAIRS = MOBGT_BIAS_LONG_PAIRS;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 constexpr int HOP_STRIDE = HOP_LDS_ROWS + 1;
@@ -877,7 +879,7 @@ int launch_build(const BuildParams& p, hipStream_t st) {
     // relies on it -- and ld = roundup(T, 64) can exceed roundup(T, 32))
     (void)T;
     const dim3 grid(nt, 4 * nt, p.G), block(256);
-    if (p.H == 8 && (int64_t)p.G * T * T >= (1 << 20)) {
+    if (p.H == 8 && (int64_t)p.G * T * T >= BIAS_LONG_PAIRS) {
         const int nt2 = (nt + 1) / 2;
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
@@ -921,8 +923,7 @@ int launch_build_bwd(const BuildParams& p, hipStream_t st) {
     // long batches: 8-wave workgroups, one per CU (each walks its units); short ones: 4-wave workgroups, up to 3 per CU
     // (more than 64 KB of dynamic LDS has to be asked for, per kernel)
 #define BWD_LDS(K, HH_, HM_, NW_) do { shm = tables + bwd_stage_bytes<HH_, HM_, NW_>(); if (shm > 48 * 1024 && hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return MOBGT_EBADDIM; } while (0)
-    static const int64_t long_from = (1 << 20);
-    if (hopmm && pairs >= long_from) {
+    if (hopmm && pairs >= BIAS_LONG_PAIRS) {
         const int n_units8 = ((T + 63) / 64) * ((T + 7) / 8) * p.G;
         // (one persistent workgroup per compute unit; a caller that runs this launch BESIDE other work -- ops._bias_bwd_beside: on a
         //  side stream under the tail of the backward pass -- asks for fewer, so that the other stream's kernels find free units:

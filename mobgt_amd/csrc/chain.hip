@@ -852,7 +852,7 @@ __global__ __launch_bounds__(BIG_NW * 64) void layer_chain_fwd_big_kernel(const 
     STAMP_DUMP();
 }
 
-constexpr int64_t CHAIN_BIG_ROWS = 4096;         // rows past which the forward chain takes the 64-row form (the host packs for it: model.pack_layer_weights)
+constexpr int64_t CHAIN_BIG_ROWS = MOBGT_CHAIN_BIG_ROWS;   // rows past which both chains take the 64-row form (the host packs for it: model.pack_layer_weights)
 template <int C, int F>
 int launch_big(const ChainParams& p, hipStream_t st) {
     constexpr int BM = 64, LDA = C + 8, LDX = C + 4, LDC = 384 + 8;
@@ -2562,6 +2562,7 @@ extern "C" int64_t mobgt_chain_ws_bytes(void) {
 }
 extern "C" int64_t mobgt_chain_ws_fault_offset(void) { return (int64_t)WS_FAULT * (int64_t)sizeof(uint32_t); }
 extern "C" int64_t mobgt_chain_ws_limit_offset(void) { return (int64_t)WS_LIMIT * (int64_t)sizeof(uint32_t); }
+extern "C" int mobgt_chain_cluster_size(int64_t R) { return pick_ncl(R, &R); }       // (any non-null `ws`: it is not read)
 
 extern "C" int mobgt_assemble_tokens_qkv(const float* nf, const float* real, const float* add, const float* token,
                                          const float* pe0, float* out, void* out_bf16, const void* wqkv_packed, const void* bqkv,

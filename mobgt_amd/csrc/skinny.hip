@@ -15,6 +15,8 @@ namespace {
 
 constexpr int GMAX = 16;
 constexpr int KCH = 2;                       // K <= 512: lane l owns k = 4l + 256c .. +3, c < KCH
+// (the kernels' layouts fix both -- reduce16, the 16-row MFMA tile, a wave's 256 k per chunk; the header states them for callers)
+static_assert(GMAX == MOBGT_SKINNY_MAX_G && 256 * KCH == MOBGT_SKINNY_MAX_K, "include/mobgt_hip.h states the skinny kernels' limits");
 
 __device__ __forceinline__ void reduce16(float (&v)[GMAX], int lane) {
     // afterwards lane l holds in v[0] the wave-wide sum of value (l >> 2) & 15
@@ -440,6 +442,10 @@ int check_dims(int G, int K, int V) {
     return 0;
 }
 
+// the matrix-core entry points: K = 64 KT, KT <= 7 -- the instantiations their two switches name
+static_assert(MOBGT_SKINNY_MFMA_K_STEP == 64 && MOBGT_SKINNY_MFMA_MAX_K == 7 * 64, "launch_fwd_gtl / launch_rank_fused: KT = K / 64 in 1..7");
+bool mfma_k_ok(int K) { return K % MOBGT_SKINNY_MFMA_K_STEP == 0 && K <= MOBGT_SKINNY_MFMA_MAX_K; }
+
 }  // namespace
 
 extern "C" int mobgt_skinny_linear_fwd(const float* x, const float* w, const float* b, float* y, int G, int K, int V,
@@ -501,7 +507,7 @@ int fwd_gtl_dispatch(const float* x, const float* w, const float* b, const int64
 extern "C" int mobgt_skinny_linear_fwd_mfma(const float* x, const float* w, const float* b, float* y, int G, int K, int V, void* stream) {
     const int rc = check_dims(G, K, V);
     if (rc) return rc;
-    if ((K & 63) || K > 448 || !y) return MOBGT_EBADDIM;
+    if (!mfma_k_ok(K) || !y) return MOBGT_EBADDIM;
     if (((uintptr_t)x | (uintptr_t)w) & 15) return MOBGT_EALIGN;
     return fwd_gtl_dispatch(x, w, b, nullptr, 0, y, nullptr, nullptr, G, K, V, 0.f, stream);
 }
@@ -510,7 +516,7 @@ extern "C" int mobgt_skinny_linear_gtl(const float* x, const float* w, const flo
                                        float* logits, float* dlogits, float* loss, int G, int K, int V, float alpha, void* stream) {
     const int rc = check_dims(G, K, V);
     if (rc) return rc;
-    if ((K & 63) || K > 448 || !dlogits || !loss || !targets) return MOBGT_EBADDIM;
+    if (!mfma_k_ok(K) || !dlogits || !loss || !targets) return MOBGT_EBADDIM;
     if (((uintptr_t)x | (uintptr_t)w) & 15) return MOBGT_EALIGN;
     return fwd_gtl_dispatch(x, w, b, targets, target_offset, logits, dlogits, loss, G, K, V, alpha, stream);
 }
@@ -990,7 +996,7 @@ extern "C" int mobgt_skinny_linear_rank_metrics(const float* x, const float* w, 
                                                 int G, int K, int V, double* acc, void* work, void* stream) {
     const int rc = check_dims(G, K, V);
     if (rc) return rc;
-    if ((K & 63) || K > 448 || !target || !acc || !work) return MOBGT_EBADDIM;
+    if (!mfma_k_ok(K) || !target || !acc || !work) return MOBGT_EBADDIM;
     if (((uintptr_t)x | (uintptr_t)w) & 15) return MOBGT_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     char* wk = reinterpret_cast<char*>(work);

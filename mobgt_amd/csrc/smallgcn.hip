@@ -695,7 +695,7 @@ extern "C" int mobgt_small_gcn_bwd_bias(const float* g, const float* ax, const f
         const int T = N + 1;
         // only the instantiation the short-batch launch of mobgt_build_bias_bwd would pick (see launch_build_bwd)
         if (idx_dtype != MOBGT_I16 || edge_dtype != MOBGT_U8 || H != 8 || !bp.edge_input || F != 1 || D > HOP_DMAX ||
-            (int64_t)G * T * T >= (1 << 20)) return MOBGT_EBADDIM;
+            (int64_t)G * T * T >= BIAS_LONG_PAIRS) return MOBGT_EBADDIM;
         lds_rel = bp.n_rel < 512 ? bp.n_rel : 512;
         lds_poi = bp.poi_pos ? (bp.n_poi < 1024 ? bp.n_poi : 1024) : 0;
         if ((size_t)bwd_lds_dwords(lds_rel, lds_poi, bp.D, bp.H) * sizeof(float) + bwd_stage_bytes<8, true, 4>() > LDS_FLOATS * sizeof(float))

@@ -26,7 +26,7 @@
 
 namespace {
 
-constexpr int TK_MAXK = 64;
+constexpr int TK_MAXK = MOBGT_TOPK_MAX_K;
 constexpr int TK_WAVES1 = 4;                       // launch 1: 256 threads
 constexpr int TK_ITERS = 4;                        // 64-key batches per wave
 constexpr int TK_CHUNK = 64 * TK_WAVES1 * TK_ITERS;  // 1024 columns per workgroup of launch 1

@@ -253,21 +253,24 @@ def _pending_check():
                            "(was the layer's input used by something else as well?); set MOBGT_NO_DEFER_TAIL=1")
 
 
-_CHAIN_WS = {}              # device index -> workspace of the chain kernels' cluster form
+_CHAIN_WS = {}              # (device index, C, cluster size) -> workspace of the chain kernels' cluster form
+_CHAIN_NCL = {}             # (device index, rows) -> the library's cluster size for them: asked once, not per launch
 
 
 def chain_workspace(dev, C=192, R=None):
     """Hand-over counters + exchange buffers of the cluster form of the chain kernels (include/mobgt_hip.h:
     mobgt_chain_ws_bytes): zeroed once, for ONE stream at a time (the step's compute stream).  One per device AND per launch
-    geometry (model width C, cluster size 4 / 2 -- csrc/chain.hip: pick_ncl): a row block's exchange area is addressed as
-    block x members x 16 x C, so launches of different geometry on one workspace would poll words another block wrote, and
-    a stale packet whose generation happens to match would be accepted.  Must exist before a graph capture starts
-    (an eager warm-up step creates it).  forms "safe_forms" -> None (one-workgroup form)."""
+    geometry (model width C and the cluster size the library picks for R rows, mobgt_chain_cluster_size): a row block's
+    exchange area is addressed as block x members x 16 x C, so launches of different geometry on one workspace would poll
+    words another block wrote, and a stale packet whose generation happens to match would be accepted.  Must exist
+    before a graph capture starts (an eager warm-up step creates it).  forms "safe_forms" -> None (one-workgroup form)."""
     if forms.on("safe_forms"):
         return None
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    nblk = (int(R) + 15) // 16 if R is not None else 1
-    ncl = 4 if nblk * 4 <= 256 else 2                     # (as pick_ncl; beyond 2 members the launch takes the one-workgroup form)
+    R = 16 if R is None else int(R)                       # (no R: one row block)
+    ncl = _CHAIN_NCL.get((idx, R))
+    if ncl is None:
+        ncl = _CHAIN_NCL[idx, R] = _lib.lib().mobgt_chain_cluster_size(R)
     key = (idx, int(C), ncl)
     ws = _CHAIN_WS.get(key)
     if ws is None:

@@ -2,11 +2,14 @@
 that every combination can be enumerated without a GPU (tests/test_host_layer_plan.py).  `plan_forward` is filled at the top of the
 layer's forward, `plan_backward` at the top of its backward; a form is read -- by the caller, into `on` -- at the moment the pass
 that uses it starts, so switching forms between a forward and its backward acts as it always did.
-Imports nothing from the package and needs no torch (like forms.py)."""
+Of the package it imports only _lib, for the constants of the library's header: like forms.py it needs no torch, and no built
+library."""
 from collections import namedtuple
 
+from . import _lib
+
 CHAIN_SHAPES = ((128, 1024), (192, 1024), (256, 1024))     # (C, F) the chain kernels are instantiated for (csrc/chain.hip)
-BIG_R = 4096             # rows past which the library's tiles / the 64-row chain kernels take a layer's products
+BIG_R = _lib.CONSTANTS["MOBGT_CHAIN_BIG_ROWS"]     # rows past which the library's tiles / the 64-row chain kernels take a layer's products
 TAIL_MAX_R = 1024        # rows up to which the tail GEMM of mobgt_layer_backward_tail is sized
 DEFER_MAX_R = 4096       # S-GOW: 1024 / 2048 / 4096 / 16384 -> 18.96 / 19.33 / 19.65 / 19.5 k check-ins/s
 

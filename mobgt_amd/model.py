@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import forms, ops
+from . import forms, layer_plan, ops
 from .step_state import STEP
 
 
@@ -397,11 +397,11 @@ def pack_layer_weights(layers, defer=False, rows=None):
     if not forms.on("chain"):
         return
     want_t = torch.is_grad_enabled() and forms.on("chain_bwd")
-    # `rows`: the batch's token rows, when the caller knows them.  Past 4 096 rows the FORWARD runs the 64-row chain kernel
+    # `rows`: the batch's token rows, when the caller knows them.  Past layer_plan.BIG_R rows the FORWARD runs the 64-row chain kernel
     # (csrc/chain.hip: layer_chain_fwd_big_kernel / layer_chain_bwd_big_kernel, round 5): the same packs as below them.
     # MOBGT_NO_CHAIN_BIG=1: the library's GEMMs forward as well -- nothing reads a pack then but the token-assembly launch, which
     # multiplies by the FIRST layer's QKV weight.
-    big = rows is not None and rows > 4096
+    big = rows is not None and rows > layer_plan.BIG_R
     qkv0_only = big and not forms.on("chain_big")
     if big and not forms.on("chain_big"):
         want_t = False
@@ -414,7 +414,7 @@ def pack_layer_weights(layers, defer=False, rows=None):
                 or not sh[0].is_cuda):
             continue
         C, F = sh[2].shape[0], sh[4].shape[0]
-        if (C, F) not in ((128, 1024), (192, 1024), (256, 1024)) or not all(sh[i].is_contiguous() for i in (0, 2, 4, 6)):
+        if (C, F) not in layer_plan.CHAIN_SHAPES or not all(sh[i].is_contiguous() for i in (0, 2, 4, 6)):
             continue
         pk = getattr(layer, "_packed", None)
         if pk is None or pk[0].device != sh[0].device:

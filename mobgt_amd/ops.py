@@ -13,6 +13,10 @@ from ._lib import F32, BF16, I64, I32, I16, U8, check
 from .step_state import STEP
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
+# the library's shape limits and dispatch thresholds, as its header declares them: what the predicates below ask before a launch
+BIAS_LONG_PAIRS, HOP_DMAX, TOPK_MAX = _lib.LIBRARY.constants("BIAS_LONG_PAIRS", "HOP_DMAX", "TOPK_MAX_K")
+SKINNY_MAX_G, SKINNY_MAX_K, SKINNY_MFMA_MAX_K, SKINNY_MFMA_K_STEP = _lib.LIBRARY.constants(
+    "SKINNY_MAX_G", "SKINNY_MAX_K", "SKINNY_MFMA_MAX_K", "SKINNY_MFMA_K_STEP")
 _IT = {torch.int64: I64, torch.int32: I32, torch.int16: I16, torch.uint8: U8}
 
 
@@ -333,7 +337,7 @@ def _bias_bwd_alloc(shapes, dev, sinks=(None, None, None, None)):
 
 def take_bias_bwd_job():
     """The pending bias-backward job if its inputs are complete and it is the instantiation the passenger form covers
-    (int16 indices, uint8 edge ids, 8 heads, one edge feature, <= 20 hops, a short batch); None otherwise."""
+    (int16 indices, uint8 edge ids, 8 heads, one edge feature, <= HOP_DMAX hops, a short batch); None otherwise."""
     job, STEP.bias_bwd_job = STEP.bias_bwd_job, None
     if job is None or not forms.on("bias_bwd_passenger"):
         return None
@@ -341,7 +345,7 @@ def take_bias_bwd_job():
     if pack is None or pack.dbias is None or not pack.sliced or pack.n_use < 1 or pack.n_bwd < pack.n_use:
         return None
     G, N, H, D_in, D, F, n_rel, n_poi, n_edge, ld, idx_dt, edge_dt = job["args"]
-    if not (idx_dt == I16 and edge_dt == U8 and H == 8 and D > 0 and D <= 20 and F == 1 and G * (N + 1) * (N + 1) < (1 << 20)
+    if not (idx_dt == I16 and edge_dt == U8 and H == 8 and 0 < D <= HOP_DMAX and F == 1 and G * (N + 1) * (N + 1) < BIAS_LONG_PAIRS
             and job["idx"][3] is not None):
         return None
     return job
@@ -547,7 +551,7 @@ def _bias_bwd_beside(pack):
             or pack.n_use < 1 or pack.n_bwd < pack.n_use or job["done"] is not None):
         return
     G, N = job["args"][0], job["args"][1]
-    if G * (N + 1) * (N + 1) < (1 << 20) or job["idx"][3] is None:     # (short batches: the passenger of the GCN's backward launch)
+    if G * (N + 1) * (N + 1) < BIAS_LONG_PAIRS or job["idx"][3] is None:   # (short batches: the passenger of the GCN's backward launch)
         return
     dev = pack.bias.device
     main = torch.cuda.current_stream(dev)
@@ -778,7 +782,7 @@ class _SkinnyLinearFn(torch.autograd.Function):
         if ctx.all_hip:
             y = torch.empty(G, V, dtype=torch.float32, device=x.device)
             _lib.call("mobgt_skinny_linear_fwd", _p(x), _p(w), _p(bias), _p(y), G, K, V, _stream())
-        elif K % 64 == 0 and K <= 448:
+        elif _skinny_mfma_k(K):
             # one pass over W on the matrix cores (csrc/skinny.hip; the library's M = 16 GEMM: 9.2 us at K = 320, 29 us at K = 128)
             y = torch.empty(G, V, dtype=torch.float32, device=x.device)
             _lib.call("mobgt_skinny_linear_fwd_mfma", _p(x), _p(w), _p(bias), _p(y), G, K, V, _stream())
@@ -803,7 +807,7 @@ def _skinny_backward(ctx, dy):
     V = w.shape[0]
     dy = dy.contiguous()
     dx = None
-    dx_mfma = ctx.needs_input_grad[0] and not ctx.all_hip and K % 16 == 0 and K <= 512
+    dx_mfma = ctx.needs_input_grad[0] and not ctx.all_hip and K % 16 == 0 and K <= SKINNY_MAX_K
     want_db = ctx.has_bias and ctx.needs_input_grad[2]
     want_dw = ctx.needs_input_grad[1] or want_db      # (db is the dW kernel's by-product: a frozen weight still gets the launch)
     both = dx_mfma and want_dw
@@ -862,8 +866,13 @@ class _SkinnyLinearGtlFn(torch.autograd.Function):
         return (*_skinny_backward(ctx, dz), None, None, None, None)
 
 
+def _skinny_mfma_k(K):
+    """K of the matrix-core entry points (mobgt_skinny_linear_fwd_mfma / _gtl / _rank_metrics)."""
+    return K % SKINNY_MFMA_K_STEP == 0 and K <= SKINNY_MFMA_MAX_K
+
+
 def skinny_linear_gtl_ok(x, weight):
-    return (skinny_linear_ok(x, weight) and x.shape[1] % 64 == 0 and x.shape[1] <= 448)
+    return skinny_linear_ok(x, weight) and _skinny_mfma_k(x.shape[1])
 
 
 def skinny_linear_gtl(x, weight, bias, targets, alpha=0.25, target_offset=0, logits_out=None):
@@ -875,7 +884,7 @@ def skinny_linear_gtl(x, weight, bias, targets, alpha=0.25, target_offset=0, log
 
 def skinny_linear_ok(x, weight):
     return (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and weight.dtype == torch.float32
-            and 0 < x.shape[0] <= 16 and x.shape[1] % 4 == 0 and x.shape[1] <= 512 and weight.shape[0] >= 1024
+            and 0 < x.shape[0] <= SKINNY_MAX_G and x.shape[1] % 4 == 0 and x.shape[1] <= SKINNY_MAX_K and weight.shape[0] >= 1024
             and weight.is_contiguous() and weight.data_ptr() % 16 == 0)
 
 
@@ -1029,7 +1038,8 @@ def skinny_linear_rank_metrics(x, weight, bias, target, acc, target_offset=0, wo
     skinny_linear_rank_metrics_ok.  `work`: a device buffer of rank_metrics_work_bytes(G, V) bytes (default: one per stream)."""
     _require_cuda(x, weight, target, acc)
     _check_acc(acc)
-    assert skinny_linear_rank_metrics_ok(x, weight), "skinny_linear_rank_metrics: G <= 16 rows, K % 64 == 0, K <= 448, f32"
+    assert skinny_linear_rank_metrics_ok(x, weight), (f"skinny_linear_rank_metrics: G <= {SKINNY_MAX_G} rows, "
+                                                     f"K % {SKINNY_MFMA_K_STEP} == 0, K <= {SKINNY_MFMA_MAX_K}, f32")
     x = x.contiguous()
     if x.data_ptr() % 16:
         x = x.clone()
@@ -1042,9 +1052,6 @@ def skinny_linear_rank_metrics(x, weight, bias, target, acc, target_offset=0, wo
     _lib.call("mobgt_skinny_linear_rank_metrics", _p(x.detach()), _p(weight.detach()), _p(b), _p(target), int(target_offset),
               G, K, V, _p(acc), _p(work), _stream())
     return acc
-
-
-TOPK_MAX = 64                # the largest k mobgt_topk_rows takes
 
 
 def topk_work_bytes(G, V, k):

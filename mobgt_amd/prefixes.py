@@ -21,11 +21,13 @@ import collections
 import numpy as np
 import torch
 
+from . import _prefixes
+
 PrefixStats = collections.namedtuple("PrefixStats", "session cut n mult")
 PrefixStats.__doc__ = """The Q samples of a prefix dataset, numpy int32 [Q] each: the base session of sample q, its cut c (rows 0 .. c
 of the session, row c the target), n and mult of its history."""
 
-DEVICE_MAX_L = 4096                                # (= _prefixes.MAX_L: the POI column of a session in 16 KB of LDS)
+DEVICE_MAX_L = _prefixes.MAX_L                     # (the header's: the POI column of a session in 16 KB of LDS)
 
 
 # ---- what both forms check on the host ----------------------------------------------------------------------------------------------
@@ -92,7 +94,6 @@ def prefix_stats_host(ds, min_history=1, sessions=None):
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
 def _launch(d_seq, d_offsets, d_pcum, d_keep, S, M, Q, h, out):
     """The one launch: `out` is int32 [4 Q + 1] on the device -- session, cut, n, mult and the status word."""
-    from . import _prefixes
     from .ops import _p, _stream
     part = lambda k: out.data_ptr() + 4 * k * Q
     _prefixes.launch("mobgt_prefixes_stats", _p(d_seq), _p(d_offsets), _p(d_pcum), _p(d_keep), S, M, Q, h, part(0), part(1), part(2),

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 import chain_abi as abi                                       # noqa: E402
 import chain_reference as cr                                  # noqa: E402
-from mobgt_amd import _lib, ops                               # noqa: E402
+from mobgt_amd import _lib, fused_layer, ops                  # noqa: E402
 from mobgt_amd.fused_layer import chain_workspace             # noqa: E402
 
 DEV = "cuda"
@@ -313,3 +313,20 @@ def test_argument_checks_return_without_launching():
         for n, t in d.items():
             assert bool((t == SENT).all()), (n, "a refused call wrote")
     assert float(q["dw"].abs().max()) == 0.0
+
+
+def test_the_workspace_key_follows_the_library_cluster_size(monkeypatch):
+    """mobgt_chain_cluster_size answers what pick_ncl picks on this device -- 4 while 4 workgroups per 16-row block fit on its compute
+    units (at most 256 count), then 2, then 1 -- and chain_workspace keys by that answer, not by a copy of the rule: with the entry
+    point answering 2 where the library says 4, the same (device, C, R) gets another workspace.  No kernel runs."""
+    lib, cus = _lib.lib(), min(CUS, 256)
+    rows = (16, 4 * cus, 4 * cus + 16, 8 * cus, 8 * cus + 16)
+    assert [lib.mobgt_chain_cluster_size(R) for R in rows] == [4, 4, 2, 2, 1]
+    dev = torch.device(DEV, torch.cuda.current_device())
+    own = chain_workspace(dev, 192, 16)
+    assert chain_workspace(dev, 192, 4 * cus) is own and chain_workspace(dev, 192) is own
+    monkeypatch.setattr(lib, "mobgt_chain_cluster_size", lambda R: 2)
+    monkeypatch.setattr(fused_layer, "_CHAIN_NCL", {})       # (the answers are kept per device and row count: ask again)
+    other = chain_workspace(dev, 192, 16)
+    assert other is not own and other.data_ptr() != own.data_ptr()
+    assert other is chain_workspace(dev, 192, 4 * cus + 16)

@@ -34,7 +34,7 @@ def test_literal_signatures():
         assert _same(_lib.SIGNATURES[name], want), (name, _lib.SIGNATURES[name])
     assert len(_lib.SIGNATURES["mobgt_attn_bias_fwd"][1]) == 23
     assert _same(_lib_cpu.SIGNATURES["mobgt_floyd_warshall_cpu"], (ci, [vp, ci, vp, vp]))
-    assert len(_lib.SIGNATURES) == 128 and len(_lib_cpu.SIGNATURES) == 4
+    assert len(_lib.SIGNATURES) == 129 and len(_lib_cpu.SIGNATURES) == 4
 
 
 def test_synthetic_headers():
