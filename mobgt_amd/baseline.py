@@ -344,6 +344,13 @@ class MarkovBaseline:
             self._checked(status, ids, "MarkovBaseline.recommend")
         return ids
 
+    def prior(self, user=1.0, transition=1.0, popularity=1.0):
+        """-> prior.MarkovPrior on the baseline's device: f32 log-counts of cu, cg and pop with these weights, to be added to a
+        model's scores (EvalLoop / PredictLoop(prior=...), Graphormer.metric_step / recommend_step(prior=...)).  The rule is the
+        docstring of mobgt_amd/prior.py."""
+        from .prior import MarkovPrior
+        return MarkovPrior.from_baseline(self, user, transition, popularity)
+
     def evaluate(self, samples, order="user", split_revisits=False):
         """-> the dict of metrics.finalize (acc@1/5/10/20, ndcg@1/5/10/20, mrr, n) over the samples, computed from the ranks in f64
         torch: hit rank < k, gain 1 / log2(rank + 2), reciprocal rank 1 / (rank + 1).  The order is strict, so the ACC and the MRR

@@ -614,7 +614,7 @@ class Graphormer(nn.Module):
         return {"y_pred": self(batched_data), "y_true": batched_data.y.long() - 1, "idx": batched_data.idx}
 
     def metric_step(self, batched_data, acc, work=None, exclude_visited=False, allow=None, split_revisits=False, near=None,
-                    restriction=None):
+                    restriction=None, prior=None):
         """validation_step / test_step + test_epoch_end's per-batch bookkeeping in one pass: the batch's ACC / NDCG @1/5/10/20
         and MRR sums (metrics.evaluate_outputs, quirks included) are ADDED to `acc` (metrics.new_accumulator) on the device --
         no category head, no host read.  Eval mode, under no_grad.  toyotagraph ranks log_softmax(logits) against
@@ -625,12 +625,16 @@ class Graphormer(nn.Module):
         allow, so a hit at k <=> y is in that list's first k; a row whose y cannot be listed counts in n only.  split_revisits
         adds the rows whose y is not among the trajectory's POIs (batched_data.x) to slot 1, the others to slot 2.
         near: recommend_step's radius restriction (see there); a y outside its row's radius counts in n only.
-        restriction: a prebuilt restriction.Restriction in place of those four keywords (the loops build theirs once)."""
+        restriction: a prebuilt restriction.Restriction in place of those four keywords (the loops build theirs once).
+        prior: a prior.MarkovPrior whose weighted log-counts are added to the scores, in place, before they are ranked (one launch,
+        mobgt_prior_blend_rows; the rule is prior.py's docstring): every restriction then acts on the blended scores."""
         if self.training:
             raise RuntimeError("metric_step: the model is in training mode (call .eval() first)")
         r = restriction or Restriction(self.label_offset, exclude_visited, allow, split_revisits, near)
         with torch.no_grad():
             scores = self.poi_scores(self.encode(batched_data))
+            if prior is not None:
+                scores = prior.blend(scores, batched_data, self.label_offset)
             if r.active:
                 hist = r.hist(batched_data)
                 ops.rank_metrics_masked(scores, batched_data.y, acc, target_offset=-r.label_offset, allow=r.allow_for(hist),
@@ -640,7 +644,8 @@ class Graphormer(nn.Module):
                 ops.rank_metrics(scores, batched_data.y, acc, target_offset=-r.label_offset, work=work)
         return acc
 
-    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None, near=None, restriction=None):
+    def recommend_step(self, batched_data, ids, vals, work=None, exclude_visited=False, allow=None, near=None, restriction=None,
+                       prior=None):
         """The batch's top-k next POIs, best first, into ids [G, k] int64 / vals [G, k] f32 (k = ids.shape[1] <= ops.TOPK_MAX) on
         the device: the scores metric_step ranks (logits; log_softmax for toyotagraph) in ops.topk_rows' order, so equal scores
         list the lower POI first and `y in ids[:, :k]` is exactly the hit ACC@k counts.  ids are in batched_data.y's label space:
@@ -660,38 +665,44 @@ class Graphormer(nn.Module):
         distinct POIs in the order given, where it need not be.  "any" -- within r of anywhere the user has been -- does not
         depend on order.
 
-        restriction: a prebuilt restriction.Restriction in place of those three keywords (the loops build theirs once)."""
+        restriction: a prebuilt restriction.Restriction in place of those three keywords (the loops build theirs once).
+        prior: a prior.MarkovPrior blended into the scores, in place, before the lists are taken (as in metric_step); vals are the
+        blended scores."""
         if self.training:
             raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
         r = restriction or Restriction(self.label_offset, exclude_visited, allow, near=near)
         with torch.no_grad():
             scores = self.poi_scores(self.encode(batched_data))
+            if prior is not None:
+                scores = prior.blend(scores, batched_data, self.label_offset)
             hist = r.hist(batched_data)
             ops.topk_rows(scores, ids.shape[1], col_offset=r.label_offset, work=work, out=(ids, vals), allow=r.allow_for(hist),
                           exclude=r.exclude(hist))
         return ids, vals
 
     def recommend(self, dataset, collator, k=20, exclude_visited=False, candidates=None, within_km=None, coords=None, near="last",
-                  **kw):
+                  prior=None, **kw):
         """train.PredictLoop(self, collator, dataset, k=k, exclude_visited=..., candidates=..., within_km=..., coords=...,
         near=..., **kw).run(): (sample_index [n], ids [n, k], vals [n, k]) on the device.  within_km: only POIs within that many
         km of the trajectory's last node (near="last": the last history check-in for sessions and graphs made from them, see
         recommend_step) or of any of its POIs (near="any"); coords [P + 1, 2] lat / lon in degrees, default the collator's.
+        prior: a prior.MarkovPrior (mb.prior(...)) blended into the scores before the lists are taken.
         dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator."""
         from .train import PredictLoop
         max_batches = kw.pop("max_batches", None)
         return PredictLoop(self, collator, dataset, k=k, exclude_visited=exclude_visited, candidates=candidates,
-                           within_km=within_km, coords=coords, near=near, **kw).run(max_batches=max_batches)
+                           within_km=within_km, coords=coords, near=near, prior=prior, **kw).run(max_batches=max_batches)
 
     def evaluate(self, dataset, collator, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
-                 near="last", **kw):
+                 near="last", prior=None, **kw):
         """train.EvalLoop(self, collator, dataset, exclude_visited=..., candidates=..., split_revisits=..., within_km=...,
         coords=..., near=..., **kw).run(): the reference's validation / test protocol over a whole split, optionally over
-        restricted lists (within_km / coords / near as in recommend) and split by revisits.  dataset / collator as in recommend."""
+        restricted lists (within_km / coords / near as in recommend) and split by revisits.  prior: a prior.MarkovPrior blended
+        into the scores before they are ranked.  dataset / collator as in recommend."""
         from .train import EvalLoop
         max_batches = kw.pop("max_batches", None)
         return EvalLoop(self, collator, dataset, exclude_visited=exclude_visited, candidates=candidates,
-                        split_revisits=split_revisits, within_km=within_km, coords=coords, near=near,
+                        split_revisits=split_revisits, within_km=within_km, coords=coords, near=near, prior=prior,
                         **kw).run(max_batches=max_batches)
 
     def test_epoch_end(self, outputs):

@@ -1,0 +1,276 @@
+"""A fitted Markov baseline (baseline.MarkovBaseline) as a prior on a model's next-POI scores: log-counts of the baseline's three
+tables, each with a weight, added to the [G, V] scores that Graphormer.metric_step / recommend_step rank -- on the device, in one
+launch (csrc_prior/prior.hip through _prior), inside the loops' captured graphs.
+
+Tables.  `mb.prior(user=wu, transition=wg, popularity=wp)` makes a MarkovPrior of a fitted MarkovBaseline.  It holds the
+baseline's rowptr, col, ukey, U, P and three f32 tables as long as val, uval and pop:
+
+    lg[e] = f32(log1p(val[e]))      lu[e] = f32(log1p(uval[e]))      lp[p] = f32(log1p(pop[p]))
+
+All three are gathered from ONE table f32(np.log1p(np.arange(max_count + 1, dtype=float64))) made in numpy (log_table), on the
+host and on the device alike, so both forms hold the same bits: no transcendental is evaluated in a kernel or in torch.  A count
+is > 0 exactly where its logarithm is, which is what the rule tests.  The tables are counted over the TRAIN sessions only
+(baseline.py): the prior sees nothing of a validation or test session.
+
+Weights.  (wu, wg, wp) live in a device f32 [3] tensor the kernel reads, `prior.weights`; set_weights copies into it, so a
+captured graph that blends stays valid when the weights change.  Only finite weights are taken.
+
+Per row.  Row g of the scores belongs to a sample with the history ids hist[g, 0:n] (Restriction.hist(batch): the trajectory's
+nodes, 0 = padding) and user[g] (batch.user = user + 1).
+  * The anchor a is the LAST entry of hist[g] that is not 0 -- the anchor near="last" documents.  For graphs made from sessions
+    (data.SessionCollator, sessions_to_trajectories) the nodes are ordered by their last visit, so it is the last history
+    check-in; a hand-made dict stores distinct POIs in the order given, where its last node need not be the last check-in.  An
+    id outside 1 .. P means no anchor.
+  * u = user[g] - user_offset (1).  A user outside [0, U) has no user rows.
+  * Column c is POI p = c + label_offset (model.label_offset).
+  * Every operation is rounded to f32 on its own, no FMA, in exactly this order:
+
+        s = scores[g, c]
+        if 1 <= p <= P and pop(p) > 0:                      s = s + wp * lp[p - 1]
+        if a exists and cg(a, p) > 0   (entry e of row a):   s = s + wg * lg[e]
+        if additionally cu(u, a, p) > 0 (entry e'):           s = s + wu * lu[e']
+        out[g, c] = s
+
+    A term whose count is 0 is not added, so -0.0 survives where nothing applies; a term with weight 0 is added (x + 0.0: -0.0
+    becomes +0.0, nothing else changes).  Non-finite scores go through the arithmetic as IEEE gives.  Entries of col whose
+    column falls outside [0, V) are skipped silently: V and P need not agree (S-BIG has V = P + 1).
+  * Tables that are not what fit makes: a rowptr pair that is descending or beyond nnz makes the row count as empty, an entry
+    of col outside [0, P) is skipped, and both raise SBADINDEX in the status word.
+
+`blend_host` is this rule in numpy f32 with plain loops over the entries of a row: the kernel's reference and the CPU form."""
+import collections
+
+import numpy as np
+import torch
+
+from . import _prior
+
+WEIGHTS = ("user", "transition", "popularity")                          # the order of a weights row
+MAX_SWEEP = 16                                                          # weight rows of one EvalLoop(prior_weights=)
+SBADINDEX = _prior.SBADINDEX
+
+PriorTables = collections.namedtuple("PriorTables", "rowptr col lg ukey lu lp U P")
+PriorTables.__doc__ = "numpy: rowptr int64 [P + 1], col int32 [nnz], lg f32 [nnz], ukey int64 [nnzU], lu f32 [nnzU], lp f32 [P]; ints U, P"
+
+
+def log_table(max_count):
+    """f32(log1p(c)) for c in 0 .. max_count, computed in float64 and rounded once: what lg, lu and lp are gathered from."""
+    return np.log1p(np.arange(int(max_count) + 1, dtype=np.float64)).astype(np.float32)
+
+
+def check_weights(rows, what):
+    """-> f32 numpy of the same shape; ValueError unless every value is finite (as f32 too)."""
+    try:
+        w = np.asarray(rows, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the weights must be numbers, got {rows!r}") from None
+    with np.errstate(over="ignore"):
+        w32 = w.astype(np.float32)
+    if not np.isfinite(w32).all():
+        raise ValueError(f"{what}: the weights ({', '.join(WEIGHTS)}) must be finite f32 values, got {w.tolist()}")
+    return w32
+
+
+def sweep_weights(W, what="prior_weights"):
+    """A weight sweep's rows -> f32 numpy [L, 3], 1 <= L <= MAX_SWEEP, columns (user, transition, popularity), finite."""
+    w = np.asarray(W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else W, dtype=np.float64)
+    if w.ndim != 2 or w.shape[1] != 3:
+        raise ValueError(f"{what}: [L, 3] rows of ({', '.join(WEIGHTS)}) weights, got shape {tuple(w.shape)}")
+    if not 1 <= w.shape[0] <= MAX_SWEEP:
+        raise ValueError(f"{what}: {w.shape[0]} rows, one loop sweeps 1 .. {MAX_SWEEP} (MarkovPrior.tune splits a longer grid)")
+    return check_weights(w, what)
+
+
+def blend_host(scores, hist, user, prior_tables, weights, label_offset, user_offset=1, status=None):
+    """The rule of the module's docstring -> f32 numpy [G, V].  scores [G, V] f32; hist [G, n] integer ids; user [G] (or [G, 1]);
+    prior_tables a PriorTables; weights (wu, wg, wp); status: a list or array whose [0] gets the SBADINDEX bit ORed in."""
+    t = prior_tables
+    s = np.array(scores, dtype=np.float32)
+    G, V = s.shape
+    hist, user = np.asarray(hist).reshape(G, -1), np.asarray(user).reshape(G)
+    wu, wg, wp = (np.float32(w) for w in weights)
+    P, lo, nnz = int(t.P), int(label_offset), len(t.col)
+    # the popularity term: elementwise, a product rounded to f32 and then a sum rounded to f32
+    c_lo, c_hi = max(0, 1 - lo), min(V, P + 1 - lo)                    # the columns whose POI is one of 1 .. P
+    if c_hi > c_lo:
+        lp = np.asarray(t.lp, dtype=np.float32)[c_lo + lo - 1:c_hi + lo - 1]
+        term = (wp * lp).astype(np.float32)
+        part = s[:, c_lo:c_hi]
+        part[:, lp > 0] = (part[:, lp > 0] + term[lp > 0][None, :]).astype(np.float32)
+    bad = 0
+    for g in range(G):
+        ids = hist[g][hist[g] != 0]
+        a = int(ids[-1]) if len(ids) else 0
+        if not 1 <= a <= P:
+            continue
+        r0, r1 = int(t.rowptr[a - 1]), int(t.rowptr[a])
+        if r0 < 0 or r1 < r0 or r1 > nnz:
+            bad |= SBADINDEX
+            continue
+        u = int(user[g]) - int(user_offset)
+        mine = {}                                                      # cu(u, a, .): 0-based POI -> entry of ukey
+        if 0 <= u < int(t.U) and len(t.ukey):
+            base = (u * P + a - 1) * P
+            i0, i1 = np.searchsorted(t.ukey, [base, base + P])
+            mine = {int(k) - base: i for i, k in zip(range(int(i0), int(i1)), t.ukey[i0:i1])}
+        for e in range(r0, r1):
+            q = int(t.col[e])
+            if q < 0 or q >= P:
+                bad |= SBADINDEX
+                continue
+            c = q + 1 - lo
+            if c < 0 or c >= V or not t.lg[e] > 0:
+                continue
+            v = np.float32(s[g, c] + np.float32(wg * np.float32(t.lg[e])))
+            if q in mine and t.lu[mine[q]] > 0:
+                v = np.float32(v + np.float32(wu * np.float32(t.lu[mine[q]])))
+            s[g, c] = v
+    if status is not None:
+        status[0] |= bad
+    return s
+
+
+class MarkovPrior:
+    """The tables of the module's docstring on one device, their weights and a status word.
+
+    P, U                   as the baseline's
+    rowptr, col, ukey      the baseline's own tensors (shared, not copied)
+    lg, lu, lp             f32 [nnz], [nnzU], [P]
+    weights                f32 [3] on the device: (user, transition, popularity); written by set_weights only
+    status                 int32 [1] on the device: the kernel ORs SBADINDEX into it and never clears it.  The loops zero it when
+                           a run starts and read it once when it ends; after blend() calls of your own, check() reads it."""
+
+    def __init__(self, P, U, rowptr, col, lg, ukey, lu, lp, weights):
+        self.P, self.U, self.rowptr, self.col, self.lg, self.ukey, self.lu, self.lp = int(P), int(U), rowptr, col, lg, ukey, lu, lp
+        self._host_weights = check_weights(weights, "MarkovPrior").reshape(3)
+        self.weights = torch.from_numpy(self._host_weights.copy()).to(self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._host_tables = None
+
+    @property
+    def device(self):
+        return self.lp.device
+
+    @classmethod
+    def from_baseline(cls, mb, user=1.0, transition=1.0, popularity=1.0):
+        """One log_table for the largest count of the three tables, uploaded once; lg, lu and lp are gathers from it."""
+        weights = check_weights([user, transition, popularity], "MarkovBaseline.prior")
+        g = mb.graph
+        top = max([int(v.max()) for v in (g.val, mb.uval, mb.pop) if v.numel()] + [0])
+        table = torch.from_numpy(log_table(top)).to(mb.device)
+        lg, lu, lp = (table[v.long()] for v in (g.val, mb.uval, mb.pop))
+        return cls(mb.P, mb.U, g.rowptr, g.col, lg, mb.ukey, lu, lp, weights)
+
+    def tables(self):
+        """-> PriorTables: the tables as numpy arrays (one download, kept), what blend_host takes."""
+        if self._host_tables is None:
+            n = lambda v: v.detach().cpu().numpy()
+            self._host_tables = PriorTables(n(self.rowptr), n(self.col), n(self.lg), n(self.ukey), n(self.lu), n(self.lp), self.U, self.P)
+        return self._host_tables
+
+    def get_weights(self):
+        """-> {"user": wu, "transition": wg, "popularity": wp} as last set (the host's copy: no device read)."""
+        return {k: float(v) for k, v in zip(WEIGHTS, self._host_weights)}
+
+    def set_weights(self, user=None, transition=None, popularity=None):
+        """Copy new weights into the device tensor the kernel reads (None: that weight stays).  Non-finite: ValueError, and
+        nothing is changed.  Graphs captured with this prior read the new values at their next replay."""
+        new = [old if v is None else v for v, old in zip((user, transition, popularity), self._host_weights.tolist())]
+        self._host_weights = check_weights(new, "MarkovPrior.set_weights")
+        self.weights.copy_(torch.from_numpy(self._host_weights.copy()), non_blocking=False)
+        return self
+
+    def check(self, what="MarkovPrior.blend"):
+        """Read the status word (one host read); not zero: ValueError.  The word is left as it is."""
+        bits = int(self.status[0])
+        if bits:
+            raise ValueError(f"{what}: the kernel skipped table rows or entries (status {bits}): a rowptr pair was descending or beyond "
+                             "nnz, or an entry of col was outside [0, P) -- the tables are not what MarkovBaseline.fit makes")
+
+    @staticmethod
+    def _ids(rows, G, what):
+        hist, user = rows if isinstance(rows, (tuple, list)) else (rows.x.reshape(rows.x.shape[0], -1), rows.user)
+        hist, user = hist.reshape(hist.shape[0], -1), user.reshape(-1)
+        if hist.shape[0] != G or user.shape[0] != G:
+            raise ValueError(f"{what}: {G} rows of scores, {hist.shape[0]} of hist and {user.shape[0]} users")
+        for name, v in (("hist", hist), ("user", user)):
+            if v.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"{what}: {name} must be int32 or int64 ids, got {v.dtype}")
+        if hist.shape[1] and hist.stride(1) != 1:
+            hist = hist.contiguous()
+        return hist, user
+
+    def blend(self, scores, rows, label_offset, out=None, weights=None):
+        """The blend of `scores` [G, V] f32 (rows of unit column stride) -> `out`; out=None: IN PLACE, and scores is returned.
+
+        rows: a collated batch (hist = Restriction.hist(batch), user = batch.user) or a (hist [G, n], user [G]) pair of int32 /
+        int64 tensors.  label_offset: model.label_offset, 0 or 1.  out: f32 [G, >= V] that does not overlap scores; its columns
+        from V on are left alone.  weights: a device f32 [3] view read in place of the prior's own (a row of a sweep).
+
+        On the device ONE launch (mobgt_prior_blend_rows) on the current stream: no allocation, no host read -- SBADINDEX lands
+        in self.status (check()).  A CPU prior answers with blend_host and ORs the bit into self.status."""
+        what = "MarkovPrior.blend"
+        if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] and scores.stride(1) != 1):
+            raise ValueError(f"{what}: scores must be f32 [G, V] with unit column stride, got {scores.dtype} {tuple(scores.shape)}")
+        G, V = scores.shape
+        out = scores if out is None else out
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != G or out.shape[1] < V or (out.shape[1] and out.stride(1) != 1):
+            raise ValueError(f"{what}: out must be f32 [{G}, >= {V}] with unit column stride, got {out.dtype} {tuple(out.shape)}")
+        if label_offset not in (0, 1):
+            raise ValueError(f"{what}: label_offset must be 0 or 1 (model.label_offset), got {label_offset!r}")
+        hist, user = self._ids(rows, G, what)
+        w = self.weights if weights is None else weights
+        if w.dtype != torch.float32 or w.numel() != 3 or not w.is_contiguous():
+            raise ValueError(f"{what}: weights must be a contiguous f32 [3] view, got {w.dtype} {tuple(w.shape)}")
+        for name, v in (("scores", scores), ("out", out), ("hist", hist), ("user", user), ("weights", w)):
+            if v.device != self.device:
+                raise ValueError(f"{what}: {name} is on {v.device}, the prior on {self.device}")
+        if self.device.type != "cuda":
+            status = [0]
+            res = blend_host(scores.numpy(), hist.numpy(), user.numpy(), self.tables(), w.tolist(), label_offset, status=status)
+            out[:, :V] = torch.from_numpy(res)
+            self.status |= status[0]
+            return out
+        if G > _prior.MAX_G:
+            raise ValueError(f"{what}: {G} rows, one launch takes up to {_prior.MAX_G}")
+        from .ops import _p, _stream
+        code = lambda v: _prior.I64 if v.dtype == torch.int64 else _prior.I32
+        with torch.cuda.device(self.device):
+            _prior.launch("mobgt_prior_blend_rows", _p(scores), scores.stride(0) if G > 1 else max(V, scores.stride(0)), _p(out),
+                          out.stride(0) if G > 1 else max(V, out.stride(0)), G, V, int(label_offset),
+                          _p(hist), code(hist), max(hist.stride(0), hist.shape[1]), hist.shape[1],
+                          _p(user), code(user), max(user.stride(0), 1), 1,
+                          _p(self.rowptr), _p(self.col), _p(self.lg), int(self.col.numel()),
+                          _p(self.ukey), _p(self.lu), int(self.ukey.numel()), self.U, _p(self.lp), self.P, _p(w), _p(self.status),
+                          _stream())
+        return out
+
+    def for_loop(self, model, device, rows, what):
+        """What a loop checks once, on the host, before it captures anything with this prior."""
+        if torch.device(device) != self.device:
+            raise ValueError(f"{what}: the prior is on {self.device}, the loop on {torch.device(device)}: fit the baseline on the "
+                             "loop's device (MarkovBaseline.fit(..., device=...))")
+        V, lo = model.out_proj.out_features, model.label_offset
+        if self.P > V - 1 + lo:
+            raise ValueError(f"{what}: the prior has POIs 1 .. {self.P}, the model scores {V} columns for POIs {lo} .. {V - 1 + lo}: "
+                             "the baseline was not fitted on the model's universe")
+        if rows > _prior.MAX_G:
+            raise ValueError(f"{what}: batch_size {rows}, one blend launch takes up to {_prior.MAX_G} rows")
+
+    def tune(self, model, collator, val, grid, key="mrr", **loop_kw):
+        """Evaluate every weights row of `grid` ([L, 3]: user, transition, popularity) on `val` with train.EvalLoop(model, collator,
+        val, prior=self, prior_weights=..., **loop_kw) -- each batch is encoded once per loop, and a grid longer than MAX_SWEEP
+        takes one loop per MAX_SWEEP rows -- then set the weights of the largest result[key] (the first of equal ones) and return
+        the list of the L result dicts.  `val` must be held out of the sessions the baseline was fitted on, and is not the test
+        split: the weights are fitted to it."""
+        from .train import EvalLoop
+        grid = np.asarray(grid, dtype=np.float64)
+        if grid.ndim != 2 or grid.shape[1] != 3 or grid.shape[0] < 1:
+            raise ValueError(f"MarkovPrior.tune: grid must be [L >= 1, 3] rows of ({', '.join(WEIGHTS)}) weights, got shape {tuple(grid.shape)}")
+        check_weights(grid, "MarkovPrior.tune")
+        results = []
+        for i in range(0, len(grid), MAX_SWEEP):
+            results += EvalLoop(model, collator, val, prior=self, prior_weights=grid[i:i + MAX_SWEEP], **loop_kw).run()
+        best = max(range(len(results)), key=lambda i: (results[i][key], -i))
+        self.set_weights(*grid[best].tolist())
+        return results

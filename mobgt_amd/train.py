@@ -1440,17 +1440,39 @@ class EvalLoop(_FrozenModelLoop):
     dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator -- the
     loops reach the input form through the collator only (nodes_of, keeps, lengths_of, new_stage, stage_host, limit_violation,
     upload), and the collate through can_finish_into, finish_into and batch_from_views on the copy stream, or finish inside
-    the step."""
+    the step.
+
+    prior: a prior.MarkovPrior on the loop's device (mb.prior(...) of a data.MarkovBaseline fitted on the TRAIN sessions).  Its
+    weighted log-counts are added to the scores inside the captured graph, one launch between the classifier and the ranking
+    (the rule: prior.py's docstring), and exclude_visited, candidates, within_km and split_revisits act on the blended scores.
+    The anchor of a row is its trajectory's last node, with near="last"'s caveat: the last history check-in for sessions and
+    graphs made from them, not necessarily for a hand-made dict.  The graphs read the prior's weights from device memory, so
+    prior.set_weights between two runs needs no new capture.  run() zeroes the prior's status word when it starts and reads it
+    with the accumulator; a status that is not zero (tables that fit did not make) is a ValueError.
+
+    prior_weights: a sweep, [L, 3] rows of (user, transition, popularity) weights, 1 <= L <= 16.  Every batch is encoded ONCE;
+    for each row the scores are blended out of place into one scratch [batch_size, V] with that row's weights and ranked into
+    an accumulator of the row's own; run() returns the list of the L dicts, each what a loop with those weights returns.  The
+    prior's own weights are not used and not changed (prior.tune picks the best row and sets it)."""
 
     def __init__(self, model, collator, dataset, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
                  side_collate=True, exclude_visited=False, candidates=None, split_revisits=False, within_km=None, coords=None,
-                 near="last"):
+                 near="last", prior=None, prior_weights=None):
         from . import metrics
         if not hasattr(model, "metric_step"):
             raise TypeError("EvalLoop: the model has no metric_step (the fq model, model_fqandtoyo.Graphormer)")
         radius = Restriction.radius(collator, within_km, coords, near)
+        sweep = None
+        if prior_weights is not None:
+            from .prior import sweep_weights
+            if prior is None:
+                raise ValueError("EvalLoop: prior_weights without prior= (the sweep blends a prior.MarkovPrior)")
+            sweep = sweep_weights(prior_weights, "EvalLoop: prior_weights")
         super().__init__(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
         V = model.out_proj.out_features
+        self.prior = prior
+        if prior is not None:
+            prior.for_loop(model, self.device, self.batch_size, "EvalLoop")
         r = self.restriction = Restriction.on_device(model.label_offset, V, self.batch_size, self.device, exclude_visited,
                                                      candidates, split_revisits, radius)
         if r.active:
@@ -1461,28 +1483,64 @@ class EvalLoop(_FrozenModelLoop):
             nbytes = ops.rank_metrics_work_bytes(self.batch_size, V)
         self.acc, self._scratch = new_acc(), new_acc()      # (warm-up passes count in the scratch one, that is nowhere)
         self.work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.sweep = None
+        if sweep is not None:                               # [L, 3] weights, L accumulators, one [rows, V] buffer for the blends
+            self.sweep = (torch.from_numpy(sweep).to(self.device), [new_acc() for _ in sweep],
+                          torch.empty(self.batch_size, V, dtype=torch.float32, device=self.device))
 
     restricted = property(lambda self: self.restriction.active)
 
     def _step(self, slot, warm):
+        if self.sweep is not None:
+            return self._sweep_step(self._collated(slot["batch"]), warm)
         self.model.metric_step(self._collated(slot["batch"]), self._scratch if warm else self.acc, work=self.work,
-                               restriction=self.restriction)
+                               restriction=self.restriction, prior=self.prior)
+
+    def _sweep_step(self, batch, warm):
+        """metric_step with the encoder run once: the scores blended with every weights row in turn, each blend ranked by
+        metric_step's own ranking call into that row's accumulator."""
+        model, r = self.model, self.restriction
+        W, accs, blended = self.sweep
+        with torch.no_grad():
+            scores = model.poi_scores(model.encode(batch))
+            out = blended[:scores.shape[0]]
+            hist = r.hist(batch)
+            allow = r.allow_for(hist) if r.active else None  # (the rows' words do not depend on the scores: built once)
+            for l in range(W.shape[0]):
+                acc = self._scratch if warm else accs[l]
+                self.prior.blend(scores, batch, r.label_offset, out=out, weights=W[l])
+                if r.active:
+                    ops.rank_metrics_masked(out, batch.y, acc, target_offset=-r.label_offset, allow=allow, hist=hist,
+                                            hist_offset=r.label_offset, exclude_hist=r.exclude_visited, split=r.split_revisits,
+                                            work=self.work)
+                else:
+                    ops.rank_metrics(out, batch.y, acc, target_offset=-r.label_offset, work=self.work)
 
     def run(self, max_batches=None):
         """One pass over this rank's part of the split -> dict of metrics.evaluate_outputs' keys + "n" (samples counted)."""
         from . import metrics
+        accs = [self.acc] if self.sweep is None else self.sweep[1]
         with self._evaluating():
-            self.acc.zero_()
+            for acc in accs:
+                acc.zero_()
+            if self.prior is not None:
+                self.prior.status.zero_()
             for _ in self._pipeline(self.batches(max_batches)):
                 pass
             if self.world > 1 and dist.is_available() and dist.is_initialized():
-                if dist.get_backend() == "gloo":
-                    host = self.acc.cpu()
-                    dist.all_reduce(host)
-                    self.acc.copy_(host)
-                else:
-                    dist.all_reduce(self.acc)
-            return (metrics.finalize_restricted if self.restriction.active else metrics.finalize)(self.acc)    # the one host read
+                for acc in accs:
+                    if dist.get_backend() == "gloo":
+                        host = acc.cpu()
+                        dist.all_reduce(host)
+                        acc.copy_(host)
+                    else:
+                        dist.all_reduce(acc)
+            if self.prior is not None:
+                self.prior.check("EvalLoop")                # (read with the accumulator: the pass is over)
+            finalize = metrics.finalize_restricted if self.restriction.active else metrics.finalize
+            if self.sweep is not None:
+                return [finalize(acc) for acc in accs]
+            return finalize(self.acc)                       # the one host read
 
 
 class PredictLoop(_FrozenModelLoop):
@@ -1501,10 +1559,14 @@ class PredictLoop(_FrozenModelLoop):
     within_km=r limits each list to the POIs within r km of the row's anchor, with coords and near as in EvalLoop (near="last":
     the trajectory's last node, node_name[-1]: the last history check-in when the graphs come from sessions; near="any":
     within r of any POI of the trajectory).  The rows' candidate words are built inside the captured graph (ops.near_words) from
-    positions packed once here, and combine with exclude_visited and candidates."""
+    positions packed once here, and combine with exclude_visited and candidates.
+
+    prior: a prior.MarkovPrior on the loop's device, blended into the scores inside the captured graph before the lists are
+    taken, as in EvalLoop (vals are the blended scores; the anchor caveat of near="last" holds).  run() zeroes the prior's status
+    word when it starts and reads it after the pass -- the loop's one host read, made only with a prior; not zero: ValueError."""
 
     def __init__(self, model, collator, dataset, k=20, batch_size=16, rank=None, world=None, use_graph=True, buckets=None,
-                 side_collate=True, exclude_visited=False, candidates=None, within_km=None, coords=None, near="last"):
+                 side_collate=True, exclude_visited=False, candidates=None, within_km=None, coords=None, near="last", prior=None):
         if not hasattr(model, "recommend_step"):
             raise TypeError("PredictLoop: the model has no recommend_step (the fq model, model_fqandtoyo.Graphormer)")
         radius = Restriction.radius(collator, within_km, coords, near)
@@ -1515,6 +1577,9 @@ class PredictLoop(_FrozenModelLoop):
         super().__init__(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
         self.restriction = Restriction.on_device(model.label_offset, V, self.batch_size, self.device, exclude_visited, candidates,
                                                  radius=radius)
+        self.prior = prior
+        if prior is not None:
+            prior.for_loop(model, self.device, self.batch_size, "PredictLoop")
         self.outs = {}                                      # (G, N) -> the [G, k] buffers its graphs write
         self.work = torch.empty(ops.topk_work_bytes(self.batch_size, V, self.k), dtype=torch.uint8, device=self.device)
 
@@ -1527,7 +1592,8 @@ class PredictLoop(_FrozenModelLoop):
         return self.outs[key]
 
     def _step(self, slot, warm):
-        self.model.recommend_step(self._collated(slot["batch"]), *self._out(slot), work=self.work, restriction=self.restriction)
+        self.model.recommend_step(self._collated(slot["batch"]), *self._out(slot), work=self.work, restriction=self.restriction,
+                                  prior=self.prior)
 
     def run(self, max_batches=None):
         """One pass over this rank's part of the split -> (sample_index [n] int64, ids [n, k] int64, vals [n, k] f32), device
@@ -1554,6 +1620,10 @@ class PredictLoop(_FrozenModelLoop):
                 r = e
 
         with self._evaluating():
+            if self.prior is not None:
+                self.prior.status.zero_()
             for _ in self._pipeline(batches, launch):
                 pass
+        if self.prior is not None:
+            self.prior.check("PredictLoop")
         return sample_index, ids, vals
