@@ -292,7 +292,9 @@ int mobgt_embed_scatter_concat(float* const* d_tables, const void* const* indice
  * and the additive degree / frequency / positional rows of model_fqandtoyo.py:1259-1298.  backward != 0: buf_t is the
  * gradient buffer, scatter-added into d_table_t (f32 atomics; rows equal to skip_t and null d_tables skipped); extra_row0
  * (optional, [width of job extra_job]) is added to ROW 0 of d_table[extra_job] -- the graph token's share of pe[0]'s
- * gradient (model_fqandtoyo.py:1338-1342), so that the positional table has ONE gradient producer. */
+ * gradient (model_fqandtoyo.py:1338-1342), so that the positional table has ONE gradient producer.  MOBGT_EBADDIM: a null index
+ * list or buffer, a null table in a forward call (`tables` itself may be null in a backward call), extra_row0 in a forward call or
+ * next to a folded table. */
 int mobgt_embed_gather_multi(int n, const float* const* tables, float* const* d_tables, const void* const* idx,
                              const int64_t* skip, const int* width, const int* coff, const int* accum, float* const* buf,
                              const int64_t* ld, int64_t R, int idx_dtype, int backward, const float* extra_row0, int extra_job,
@@ -647,12 +649,19 @@ int mobgt_layer_backward_tail(int n, const void* const* g, const int64_t* ldg, c
  * nf, add [G,N,C], real [G,N], token, pe0 [C], out [G,N+1,C], all f32 (out_bf16: optional bf16 copy of out, the
  * first layer's GEMM operand, or NULL); p_pos / p_in the two dropout probabilities (0 = off), masks from the library's
  * counter hash with the given salts (row numbering g*N+n / g / g*T+t).
- * Backward: d_nf, d_add [G,N,C] overwritten; d_token [C] ACCUMULATED (sum over graphs; zero it first). */
+ * Backward: d_nf, d_add [G,N,C] overwritten; d_token [C] ACCUMULATED (sum over graphs; zero it first).
+ * G >= 1 (MOBGT_EBADDIM otherwise).  N = 0 (graphs of the graph token alone) is ACCEPTED by mobgt_assemble_tokens_fwd, _qkv, _bwd and
+ * by mobgt_token_fwd_chain: the node buffers (nf, real, add, pt, x4; d_nf, d_add) are then neither read nor written -- _fwd, _qkv and
+ * _bwd take null pointers for them, the chain still wants its outputs non-null and aligned --, out holds the G dropped `token + pe0`
+ * rows, d_token receives the G graph-token rows of dout.  mobgt_token_bwd_chain REFUSES N = 0 (MOBGT_EBADDIM): without node rows
+ * there is no chain to run, mobgt_assemble_tokens_bwd is the call for that batch.  A null pointer among the buffers an entry point
+ * does read or write is MOBGT_EBADDIM. */
 int mobgt_assemble_tokens_fwd(const float* nf, const float* real, const float* add, const float* token, const float* pe0,
                               float* out, void* out_bf16, int G, int N, int C, float p_pos, float p_in, uint64_t seed,
                               const uint64_t* seed_dev, uint32_t salt_nf, uint32_t salt_tok, uint32_t salt_in, void* stream);
 /* mobgt_assemble_tokens_fwd plus the FIRST encoder layer's QKV projection (qkv [G*(N+1), 3C] bf16 = rows wqkv^T + bqkv, weight
- * packed by mobgt_pack_mfma_b) in one launch (csrc/chain.hip); out_bf16 is required; C in {192, 256}. */
+ * packed by mobgt_pack_mfma_b) in one launch (csrc/chain.hip); out_bf16 is required; C in {192, 256}; wqkv_packed and qkv 16-byte
+ * aligned (MOBGT_EALIGN).  N = 0 accepted (see above). */
 int mobgt_assemble_tokens_qkv(const float* nf, const float* real, const float* add, const float* token, const float* pe0,
                               float* out, void* out_bf16, const void* wqkv_packed, const void* bqkv, void* qkv, int G, int N, int C,
                               float p_pos, float p_in, uint64_t seed, const uint64_t* seed_dev, uint32_t salt_nf,
@@ -663,7 +672,12 @@ int mobgt_assemble_tokens_qkv(const float* nf, const float* real, const float* a
  * trailing columns of x4 [G*N, C], 2 = add [G*N, C]), FuseEmbeddings-2 and -4 (model_fqandtoyo.py:444-456, :1268-1269:
  * x4[:, :W2] = leaky(pt w2^T + b2), nf = leaky(x4 w4^T + b4); F.linear layout, f32, full-f32 MFMA products) and
  * mobgt_assemble_tokens_qkv.  pt, x4, add, nf are OUTPUTS (what the backward pass and the weight gradients read).
- * C = 192 and W2 = 160 only (MOBGT_EBADDIM otherwise): the fq model at hidden_dim 128. */
+ * C = 192 and W2 = 160 only (MOBGT_EBADDIM otherwise): the fq model at hidden_dim 128.  N = 0 accepted (see above): no table and no
+ * index is read, pt / x4 / add / nf stay untouched.  3 <= n <= 10; the job list: one or two slot-0 tables (copies, inside
+ * [0, W2)), folded tables only directly behind the FIRST slot-0 table and of its width, exactly one slot-1 table (a copy inside
+ * [W2, C)), one to four slot-2 tables of width C at coff 0, the first a copy and the others accum = 1; widths and coffs multiples of
+ * 4 -- anything else MOBGT_EBADDIM.  Indices int64 / int32 (MOBGT_EDTYPE otherwise); tables, pt, x4, add, nf, w2, w4, wqkv_packed,
+ * qkv 16-byte aligned (MOBGT_EALIGN). */
 int mobgt_token_fwd_chain(int n, const float* const* tables, const void* const* idx, const int* width, const int* coff,
                           const int* accum, const int* slot, int idx_dtype, float* pt, float* x4, float* add, float* nf, int W2,
                           const float* w2, const float* b2, float slope2, const float* w4, const float* b4, float slope4,
@@ -866,7 +880,8 @@ int64_t mobgt_chain_ws_limit_offset(void);
  * dx4 = (d_nf * leaky'(y4)) w4;  d_pt = (dx4[:, :W2] * leaky'(y2)) w2;  d_token += sum of the graph-token rows' d.
  * y4 [G*N, C] / y2 [G*N, W2] (row stride ld_y2): the two activations' OUTPUTS; w4 [C,C], w2 [W2,W2] row-major (out, in).
  * Written: d_nf, d_add [G*N, C], dx4 [G*N, C] (row stride ld_dx4), d_pt [G*N, W2]; d_token [C] accumulated (zero it first).
- * Masks / salts as mobgt_assemble_tokens_bwd.  (C, W2) = (192, 160). */
+ * Masks / salts as mobgt_assemble_tokens_bwd.  (C, W2) = (192, 160), ld_y2 >= W2, ld_dx4 >= C, w4 / w2 16-byte aligned.
+ * G >= 1 and N >= 1: N = 0 is REFUSED (MOBGT_EBADDIM; mobgt_assemble_tokens_bwd takes such a batch), and so is a null buffer. */
 int mobgt_token_bwd_chain(const float* dout, const float* real, const float* y4, const float* y2, int64_t ld_y2, const float* w4,
                           const float* w2, float* d_nf, float* d_add, float* dx4, int64_t ld_dx4, float* d_pt, float* d_token,
                           int G, int N, int C, int W2, float slope4, float slope2, float p_pos, float p_in, uint64_t seed,

@@ -2570,6 +2570,8 @@ extern "C" int mobgt_assemble_tokens_qkv(const float* nf, const float* real, con
                                          const uint64_t* seed_dev, uint32_t salt_nf, uint32_t salt_tok, uint32_t salt_in,
                                          void* stream) {
     if (G <= 0 || N < 0 || !out_bf16 || !wqkv_packed || !bqkv || !qkv) return MOBGT_EBADDIM;
+    if (!token || !pe0 || !out || (N > 0 && (!nf || !real || !add))) return MOBGT_EBADDIM;     // (N = 0: the node buffers are not read)
+    if (C != 192 && C != 256) return MOBGT_EBADDIM;
     if (((uintptr_t)wqkv_packed | (uintptr_t)qkv) & 15) return MOBGT_EALIGN;
     AsmQkvParams p = {};
     p.nf = nf; p.real = real; p.add = add; p.token = token; p.pe0 = pe0; p.out = out; p.out16 = (uint16_t*)out_bf16;
@@ -2598,6 +2600,7 @@ extern "C" int mobgt_token_fwd_chain(int n, const float* const* tables, const vo
                                      float p_pos, float p_in, uint64_t seed, const uint64_t* seed_dev, uint32_t salt_nf,
                                      uint32_t salt_tok, uint32_t salt_in, void* stream) {
     if (G <= 0 || N < 0 || !out_bf16 || !wqkv_packed || !bqkv || !qkv || !pt || !x4 || !add || !nf || !w2 || !b2 || !w4 || !b4) return MOBGT_EBADDIM;
+    if (!token || !pe0 || !out || (N > 0 && !real) || !tables || !idx || !width || !coff || !accum || !slot) return MOBGT_EBADDIM;
     if (C != 192 || W2 != 160 || n < 3 || n > 7 + TokGather::MAXFOLD) return MOBGT_EBADDIM;
     if (idx_dtype != MOBGT_I64 && idx_dtype != MOBGT_I32) return MOBGT_EDTYPE;
     if (((uintptr_t)wqkv_packed | (uintptr_t)qkv | (uintptr_t)pt | (uintptr_t)x4 | (uintptr_t)add | (uintptr_t)nf | (uintptr_t)w2 | (uintptr_t)w4) & 15)
@@ -2613,6 +2616,7 @@ extern "C" int mobgt_token_fwd_chain(int n, const float* const* tables, const vo
             p.g.fold[p.g.n_fold++] = tables[t];
             continue;
         }
+        if (N > 0 && !idx[t]) return MOBGT_EBADDIM;
         if (slot[t] == 0) {
             if (p.g.n0 >= 2 || accum[t] || coff[t] + width[t] > W2) return MOBGT_EBADDIM;
             p.g.s0_tab[p.g.n0] = tables[t]; p.g.s0_idx[p.g.n0] = idx[t]; p.g.s0_w[p.g.n0] = width[t]; p.g.s0_coff[p.g.n0] = coff[t];

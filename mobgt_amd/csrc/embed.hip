@@ -441,6 +441,7 @@ extern "C" int mobgt_embed_gather_multi(int n, const float* const* tables, float
                                         const float* extra_row0, int extra_job, void* stream) {
     if (n < 1 || n > MAXJ + MAXFOLD) return MOBGT_EBADDIM;
     if (extra_row0 && (extra_job < 0 || extra_job >= n || !backward)) return MOBGT_EBADDIM;
+    if (!idx || !width || !coff || !buf || !ld || (!backward && !tables)) return MOBGT_EBADDIM;
     if (R <= 0) return 0;
     MultiParams p = {};
     int k = 0;
@@ -455,7 +456,8 @@ extern "C" int mobgt_embed_gather_multi(int n, const float* const* tables, float
             continue;
         }
         if (k >= MAXJ) return MOBGT_EBADDIM;
-        if (width[t] <= 0 || (width[t] & 3) || (coff[t] & 3) || (ld[t] & 3) || !buf[t]) return MOBGT_EBADDIM;
+        if (width[t] <= 0 || (width[t] & 3) || (coff[t] & 3) || (ld[t] & 3) || !buf[t] || !idx[t] ||
+            (!backward && !tables[t])) return MOBGT_EBADDIM;
         if (((uintptr_t)buf[t] | (uintptr_t)(tables ? tables[t] : nullptr)) & 15) return MOBGT_EALIGN;
         p.tables[k] = tables ? tables[t] : nullptr;
         p.d_tables[k] = d_tables ? d_tables[t] : nullptr;

@@ -1426,6 +1426,7 @@ extern "C" int mobgt_assemble_tokens_fwd(const float* nf, const float* real, con
                                          float p_in, uint64_t seed, const uint64_t* seed_dev, uint32_t salt_nf,
                                          uint32_t salt_tok, uint32_t salt_in, void* stream) {
     if (G <= 0 || N < 0 || C <= 0) return MOBGT_EBADDIM;
+    if (!token || !pe0 || !out || (N > 0 && (!nf || !real || !add))) return MOBGT_EBADDIM;     // (N = 0: the node buffers are not read)
     TokParams p = {};
     p.nf = nf; p.real = real; p.add = add; p.token = token; p.pe0 = pe0; p.out = out; p.G = G; p.N = N; p.C = C;
     p.out16 = reinterpret_cast<bf16_t*>(out_bf16);
@@ -1440,6 +1441,7 @@ extern "C" int mobgt_assemble_tokens_bwd(const float* dout, const float* real, f
                                          const uint64_t* seed_dev, uint32_t salt_nf, uint32_t salt_tok, uint32_t salt_in,
                                          void* stream) {
     if (G <= 0 || N < 0 || C <= 0) return MOBGT_EBADDIM;
+    if (!dout || !d_token || (N > 0 && (!real || !d_nf || !d_add))) return MOBGT_EBADDIM;      // (N = 0: only d_token is touched)
     TokParams p = {};
     p.dout = dout; p.real = real; p.d_nf = d_nf; p.d_add = d_add; p.d_token = d_token; p.G = G; p.N = N; p.C = C;
     fill_tok(p, p_pos, p_in, seed, seed_dev, salt_nf, salt_tok, salt_in);

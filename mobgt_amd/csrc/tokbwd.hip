@@ -211,6 +211,8 @@ extern "C" int mobgt_token_bwd_chain(const float* dout, const float* real, const
                                      uint32_t salt_tok, uint32_t salt_in, void* stream) {
     if (G <= 0 || N <= 0) return MOBGT_EBADDIM;
     if (!(C == 192 && W2 == 160)) return MOBGT_EBADDIM;          // the instantiated widths (MobGT's hidden 128: C = 192, [poi ; time] = 160)
+    if (!dout || !real || !y4 || !y2 || !w4 || !w2 || !d_nf || !d_add || !dx4 || !d_pt || !d_token || ld_y2 < W2 || ld_dx4 < C)
+        return MOBGT_EBADDIM;
     if (((uintptr_t)w4 | (uintptr_t)w2) & 15) return MOBGT_EALIGN;
     TokBwdParams p = {};
     p.dout = dout; p.real = real; p.y4 = y4; p.y2 = y2; p.ld2 = ld_y2; p.w4 = w4; p.w2 = w2; p.d_nf = d_nf; p.d_add = d_add;
