@@ -351,6 +351,13 @@ class MarkovBaseline:
         from .prior import MarkovPrior
         return MarkovPrior.from_baseline(self, user, transition, popularity)
 
+    def distance_prior(self, pair_bins, distance=1.0):
+        """-> geoprior.DistancePrior on the baseline's device: the log of how much more often than chance a train transition lands
+        in each distance bin of `pair_bins` (a geo.PairBins of the same POIs, on the same device), with this weight, to be added
+        to a model's scores alone or in a prior.Stack beside prior().  The rule is the docstring of mobgt_amd/geoprior.py."""
+        from .geoprior import DistancePrior
+        return DistancePrior.fit(self, pair_bins, distance)
+
     def evaluate(self, samples, order="user", split_revisits=False):
         """-> the dict of metrics.finalize (acc@1/5/10/20, ndcg@1/5/10/20, mrr, n) over the samples, computed from the ranks in f64
         torch: hit rank < k, gain 1 / log2(rank + 2), reciprocal rank 1 / (rank + 1).  The order is strict, so the ACC and the MRR

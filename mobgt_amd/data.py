@@ -758,3 +758,4 @@ from .prefixes import PrefixDataset, PrefixStats, prefix_stats, prefix_stats_hos
 # ---- the Markov baseline on the same samples (baseline.py) --------------------------------------------------------------------------
 from .baseline import MarkovBaseline  # noqa: E402,F401
 from .prior import MarkovPrior  # noqa: E402,F401
+from .geoprior import DistancePrior  # noqa: E402,F401

@@ -626,7 +626,8 @@ class Graphormer(nn.Module):
         adds the rows whose y is not among the trajectory's POIs (batched_data.x) to slot 1, the others to slot 2.
         near: recommend_step's radius restriction (see there); a y outside its row's radius counts in n only.
         restriction: a prebuilt restriction.Restriction in place of those four keywords (the loops build theirs once).
-        prior: a prior.MarkovPrior whose weighted log-counts are added to the scores, in place, before they are ranked (one launch,
+        prior: a prior.MarkovPrior, a geoprior.DistancePrior or a prior.Stack of them (one launch per member, in its order); a
+        MarkovPrior's weighted log-counts are added to the scores, in place, before they are ranked (one launch,
         mobgt_prior_blend_rows; the rule is prior.py's docstring): every restriction then acts on the blended scores."""
         if self.training:
             raise RuntimeError("metric_step: the model is in training mode (call .eval() first)")
@@ -666,7 +667,7 @@ class Graphormer(nn.Module):
         depend on order.
 
         restriction: a prebuilt restriction.Restriction in place of those three keywords (the loops build theirs once).
-        prior: a prior.MarkovPrior blended into the scores, in place, before the lists are taken (as in metric_step); vals are the
+        prior: a prior.MarkovPrior, geoprior.DistancePrior or prior.Stack blended into the scores, in place, before the lists are taken (as in metric_step); vals are the
         blended scores."""
         if self.training:
             raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
@@ -686,7 +687,8 @@ class Graphormer(nn.Module):
         near=..., **kw).run(): (sample_index [n], ids [n, k], vals [n, k]) on the device.  within_km: only POIs within that many
         km of the trajectory's last node (near="last": the last history check-in for sessions and graphs made from them, see
         recommend_step) or of any of its POIs (near="any"); coords [P + 1, 2] lat / lon in degrees, default the collator's.
-        prior: a prior.MarkovPrior (mb.prior(...)) blended into the scores before the lists are taken.
+        prior: a prior.MarkovPrior (mb.prior(...)), a geoprior.DistancePrior (mb.distance_prior(pair_bins)) or a prior.Stack of
+        both, blended into the scores before the lists are taken.
         dataset / collator: trajectory dicts with a DeviceCollator, or a data.SessionDataset with a data.SessionCollator."""
         from .train import PredictLoop
         max_batches = kw.pop("max_batches", None)
@@ -697,8 +699,8 @@ class Graphormer(nn.Module):
                  near="last", prior=None, **kw):
         """train.EvalLoop(self, collator, dataset, exclude_visited=..., candidates=..., split_revisits=..., within_km=...,
         coords=..., near=..., **kw).run(): the reference's validation / test protocol over a whole split, optionally over
-        restricted lists (within_km / coords / near as in recommend) and split by revisits.  prior: a prior.MarkovPrior blended
-        into the scores before they are ranked.  dataset / collator as in recommend."""
+        restricted lists (within_km / coords / near as in recommend) and split by revisits.  prior: a prior.MarkovPrior, a
+        geoprior.DistancePrior or a prior.Stack blended into the scores before they are ranked.  dataset / collator as in recommend."""
         from .train import EvalLoop
         max_batches = kw.pop("max_batches", None)
         return EvalLoop(self, collator, dataset, exclude_visited=exclude_visited, candidates=candidates,

@@ -58,8 +58,8 @@ def log_table(max_count):
     return np.log1p(np.arange(int(max_count) + 1, dtype=np.float64)).astype(np.float32)
 
 
-def check_weights(rows, what):
-    """-> f32 numpy of the same shape; ValueError unless every value is finite (as f32 too)."""
+def check_weights(rows, what, names=WEIGHTS):
+    """-> f32 numpy of the same shape; ValueError unless every value is finite (as f32 too).  names: what the weights are called."""
     try:
         w = np.asarray(rows, dtype=np.float64)
     except (TypeError, ValueError):
@@ -67,18 +67,19 @@ def check_weights(rows, what):
     with np.errstate(over="ignore"):
         w32 = w.astype(np.float32)
     if not np.isfinite(w32).all():
-        raise ValueError(f"{what}: the weights ({', '.join(WEIGHTS)}) must be finite f32 values, got {w.tolist()}")
+        raise ValueError(f"{what}: the weights ({', '.join(names)}) must be finite f32 values, got {w.tolist()}")
     return w32
 
 
-def sweep_weights(W, what="prior_weights"):
-    """A weight sweep's rows -> f32 numpy [L, 3], 1 <= L <= MAX_SWEEP, columns (user, transition, popularity), finite."""
+def sweep_weights(W, what="prior_weights", names=WEIGHTS):
+    """A weight sweep's rows -> f32 numpy [L, len(names)], 1 <= L <= MAX_SWEEP, finite; names: the columns, a prior's WEIGHTS
+    (default MarkovPrior's: user, transition, popularity)."""
     w = np.asarray(W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else W, dtype=np.float64)
-    if w.ndim != 2 or w.shape[1] != 3:
-        raise ValueError(f"{what}: [L, 3] rows of ({', '.join(WEIGHTS)}) weights, got shape {tuple(w.shape)}")
+    if w.ndim != 2 or w.shape[1] != len(names):
+        raise ValueError(f"{what}: [L, {len(names)}] rows of ({', '.join(names)}) weights, got shape {tuple(w.shape)}")
     if not 1 <= w.shape[0] <= MAX_SWEEP:
         raise ValueError(f"{what}: {w.shape[0]} rows, one loop sweeps 1 .. {MAX_SWEEP} (MarkovPrior.tune splits a longer grid)")
-    return check_weights(w, what)
+    return check_weights(w, what, names)
 
 
 def blend_host(scores, hist, user, prior_tables, weights, label_offset, user_offset=1, status=None):
@@ -140,6 +141,9 @@ class MarkovPrior:
     status                 int32 [1] on the device: the kernel ORs SBADINDEX into it and never clears it.  The loops zero it when
                            a run starts and read it once when it ends; after blend() calls of your own, check() reads it."""
 
+    WEIGHTS = WEIGHTS                                                   # (what the loops ask of any prior: the names of a weights row,
+    n_weights = 3                                                       #  and their number)
+
     def __init__(self, P, U, rowptr, col, lg, ukey, lu, lp, weights):
         self.P, self.U, self.rowptr, self.col, self.lg, self.ukey, self.lu, self.lp = int(P), int(U), rowptr, col, lg, ukey, lu, lp
         self._host_weights = check_weights(weights, "MarkovPrior").reshape(3)
@@ -179,6 +183,10 @@ class MarkovPrior:
         self._host_weights = check_weights(new, "MarkovPrior.set_weights")
         self.weights.copy_(torch.from_numpy(self._host_weights.copy()), non_blocking=False)
         return self
+
+    def reset_status(self):
+        """Zero the status word on the current stream (what a loop does when a run starts)."""
+        self.status.zero_()
 
     def check(self, what="MarkovPrior.blend"):
         """Read the status word (one host read); not zero: ValueError.  The word is left as it is."""
@@ -273,4 +281,109 @@ class MarkovPrior:
             results += EvalLoop(model, collator, val, prior=self, prior_weights=grid[i:i + MAX_SWEEP], **loop_kw).run()
         best = max(range(len(results)), key=lambda i: (results[i][key], -i))
         self.set_weights(*grid[best].tolist())
+        return results
+
+
+class Stack:
+    """One or more priors blended in the order given, behind the interface the loops use of any prior (EvalLoop / PredictLoop,
+    Graphormer.metric_step / recommend_step): prior.Stack(mb.prior(), mb.distance_prior(pair_bins)).
+
+    priors      the members, a tuple: MarkovPrior, geoprior.DistancePrior, or anything with their interface
+    WEIGHTS     the members' names concatenated, e.g. ("user", "transition", "popularity", "distance"); no name twice
+    n_weights   len(WEIGHTS): the width of a weights row (blend(weights=), EvalLoop(prior_weights=), tune's grid)
+
+    Each member keeps its own device weights and status word; a blend is one launch per member: the first writes `out`, the rest
+    run in place on it, so the result is the members' rules applied in turn, bit for bit."""
+
+    def __init__(self, *priors):
+        if not priors:
+            raise ValueError("prior.Stack: at least one prior")
+        for p in priors:
+            missing = [a for a in ("WEIGHTS", "n_weights", "blend", "for_loop", "check", "reset_status", "set_weights", "get_weights")
+                       if not hasattr(p, a)]
+            if missing:
+                raise TypeError(f"prior.Stack: {type(p).__name__} is no prior (it has no {', '.join(missing)})")
+        self.priors = tuple(priors)
+        self.WEIGHTS = tuple(n for p in priors for n in p.WEIGHTS)
+        self.n_weights = len(self.WEIGHTS)
+        twice = list(dict.fromkeys(n for n in self.WEIGHTS if self.WEIGHTS.count(n) > 1))
+        if twice:
+            raise ValueError(f"prior.Stack: the weights {', '.join(twice)} belong to more than one member: set_weights could not tell them apart")
+        devices = {str(p.device) for p in priors}
+        if len(devices) > 1:
+            raise ValueError(f"prior.Stack: the members are on {', '.join(sorted(devices))}: fit them on one device")
+
+    @property
+    def device(self):
+        return self.priors[0].device
+
+    def _split(self, weights, what):
+        """A contiguous f32 [n_weights] view -> one view per member (None: every member reads its own)."""
+        if weights is None:
+            return [None] * len(self.priors)
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.numel() != self.n_weights or not weights.is_contiguous():
+            got = f"{weights.dtype} {tuple(weights.shape)}" if isinstance(weights, torch.Tensor) else type(weights).__name__
+            raise ValueError(f"{what}: weights must be a contiguous f32 [{self.n_weights}] view ({', '.join(self.WEIGHTS)}), got {got}")
+        flat, out, at = weights.reshape(-1), [], 0
+        for p in self.priors:
+            out.append(flat[at:at + p.n_weights])
+            at += p.n_weights
+        return out
+
+    def blend(self, scores, rows, label_offset, out=None, weights=None):
+        """The members' blends in turn: the first from `scores` into `out` (out=None: in place, and scores is returned), the
+        others in place on the V columns it wrote.  weights: a device f32 [n_weights] view, split per member in order."""
+        views = self._split(weights, "prior.Stack.blend")
+        res = self.priors[0].blend(scores, rows, label_offset, out=out, weights=views[0])
+        into = res[:, :scores.shape[1]]
+        for p, w in zip(self.priors[1:], views[1:]):
+            p.blend(into, rows, label_offset, weights=w)
+        return res
+
+    def for_loop(self, model, device, rows, what):
+        for p in self.priors:
+            p.for_loop(model, device, rows, what)
+
+    def reset_status(self):
+        for p in self.priors:
+            p.reset_status()
+
+    def check(self, what="prior.Stack.blend"):
+        for p in self.priors:
+            p.check(what)
+
+    def get_weights(self):
+        """-> {name: weight} of every member, in WEIGHTS' order (the hosts' copies: no device read)."""
+        return {k: v for p in self.priors for k, v in p.get_weights().items()}
+
+    def set_weights(self, **by_name):
+        """set_weights of the members that own the names given; an unknown name or a non-finite value: ValueError, and nothing
+        is changed."""
+        unknown = [k for k in by_name if k not in self.WEIGHTS]
+        if unknown:
+            raise ValueError(f"prior.Stack.set_weights: no weight called {', '.join(unknown)} (the stack has {', '.join(self.WEIGHTS)})")
+        check_weights([v for v in by_name.values() if v is not None], "prior.Stack.set_weights", tuple(k for k, v in by_name.items() if v is not None))
+        for p in self.priors:
+            mine = {k: v for k, v in by_name.items() if k in p.WEIGHTS}
+            if mine:
+                p.set_weights(**mine)
+        return self
+
+    def tune(self, model, collator, val, grid, key="mrr", **loop_kw):
+        """MarkovPrior.tune for the stack: evaluate every weights row of `grid` ([L, n_weights], columns WEIGHTS) on `val` with
+        train.EvalLoop(model, collator, val, prior=self, prior_weights=..., **loop_kw) -- each batch encoded once per loop, one
+        loop per MAX_SWEEP rows -- then set the weights of the largest result[key] (the first of equal ones) and return the
+        list of the L result dicts.  `val` must be held out of the sessions the members were fitted on, and is not the test
+        split."""
+        from .train import EvalLoop
+        grid = np.asarray(grid, dtype=np.float64)
+        if grid.ndim != 2 or grid.shape[1] != self.n_weights or grid.shape[0] < 1:
+            raise ValueError(f"prior.Stack.tune: grid must be [L >= 1, {self.n_weights}] rows of ({', '.join(self.WEIGHTS)}) weights, "
+                             f"got shape {tuple(grid.shape)}")
+        check_weights(grid, "prior.Stack.tune", self.WEIGHTS)
+        results = []
+        for i in range(0, len(grid), MAX_SWEEP):
+            results += EvalLoop(model, collator, val, prior=self, prior_weights=grid[i:i + MAX_SWEEP], **loop_kw).run()
+        best = max(range(len(results)), key=lambda i: (results[i][key], -i))
+        self.set_weights(**dict(zip(self.WEIGHTS, grid[best].tolist())))
         return results

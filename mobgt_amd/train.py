@@ -1450,7 +1450,11 @@ class EvalLoop(_FrozenModelLoop):
     prior.set_weights between two runs needs no new capture.  run() zeroes the prior's status word when it starts and reads it
     with the accumulator; a status that is not zero (tables that fit did not make) is a ValueError.
 
-    prior_weights: a sweep, [L, 3] rows of (user, transition, popularity) weights, 1 <= L <= 16.  Every batch is encoded ONCE;
+    prior may also be a geoprior.DistancePrior (mb.distance_prior(pair_bins): a fitted distance-decay table, the rule in
+    geoprior.py's docstring, the same anchor) or a prior.Stack of several priors, blended in the order given, one launch each.
+
+    prior_weights: a sweep, [L, prior.n_weights] rows of prior.WEIGHTS -- (user, transition, popularity) for a MarkovPrior,
+    (distance,) for a DistancePrior, the members' names concatenated for a Stack -- 1 <= L <= 16.  Every batch is encoded ONCE;
     for each row the scores are blended out of place into one scratch [batch_size, V] with that row's weights and ranked into
     an accumulator of the row's own; run() returns the list of the L dicts, each what a loop with those weights returns.  The
     prior's own weights are not used and not changed (prior.tune picks the best row and sets it)."""
@@ -1466,8 +1470,8 @@ class EvalLoop(_FrozenModelLoop):
         if prior_weights is not None:
             from .prior import sweep_weights
             if prior is None:
-                raise ValueError("EvalLoop: prior_weights without prior= (the sweep blends a prior.MarkovPrior)")
-            sweep = sweep_weights(prior_weights, "EvalLoop: prior_weights")
+                raise ValueError("EvalLoop: prior_weights without prior= (the sweep blends a prior: prior.MarkovPrior, geoprior.DistancePrior, prior.Stack)")
+            sweep = sweep_weights(prior_weights, "EvalLoop: prior_weights", prior.WEIGHTS)
         super().__init__(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
         V = model.out_proj.out_features
         self.prior = prior
@@ -1484,7 +1488,7 @@ class EvalLoop(_FrozenModelLoop):
         self.acc, self._scratch = new_acc(), new_acc()      # (warm-up passes count in the scratch one, that is nowhere)
         self.work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.sweep = None
-        if sweep is not None:                               # [L, 3] weights, L accumulators, one [rows, V] buffer for the blends
+        if sweep is not None:                               # [L, n_weights] weights, L accumulators, one [rows, V] buffer for the blends
             self.sweep = (torch.from_numpy(sweep).to(self.device), [new_acc() for _ in sweep],
                           torch.empty(self.batch_size, V, dtype=torch.float32, device=self.device))
 
@@ -1524,7 +1528,7 @@ class EvalLoop(_FrozenModelLoop):
             for acc in accs:
                 acc.zero_()
             if self.prior is not None:
-                self.prior.status.zero_()
+                self.prior.reset_status()
             for _ in self._pipeline(self.batches(max_batches)):
                 pass
             if self.world > 1 and dist.is_available() and dist.is_initialized():
@@ -1561,7 +1565,7 @@ class PredictLoop(_FrozenModelLoop):
     within r of any POI of the trajectory).  The rows' candidate words are built inside the captured graph (ops.near_words) from
     positions packed once here, and combine with exclude_visited and candidates.
 
-    prior: a prior.MarkovPrior on the loop's device, blended into the scores inside the captured graph before the lists are
+    prior: a prior.MarkovPrior, a geoprior.DistancePrior or a prior.Stack on the loop's device, blended into the scores inside the captured graph before the lists are
     taken, as in EvalLoop (vals are the blended scores; the anchor caveat of near="last" holds).  run() zeroes the prior's status
     word when it starts and reads it after the pass -- the loop's one host read, made only with a prior; not zero: ValueError."""
 
@@ -1621,7 +1625,7 @@ class PredictLoop(_FrozenModelLoop):
 
         with self._evaluating():
             if self.prior is not None:
-                self.prior.status.zero_()
+                self.prior.reset_status()
             for _ in self._pipeline(batches, launch):
                 pass
         if self.prior is not None:
