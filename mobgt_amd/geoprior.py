@@ -305,6 +305,19 @@ class DistancePrior:
                              int(pb.thresholds.numel()), _p(self.table), _p(w), _stream())
         return out
 
+    def features(self, rows, label_offset, out, V=None, zeros=None):
+        """out[0, g, c] = table[bin(anchor of row g, POI of column c)], 0 where the rule adds nothing: one blend of zeros with
+        weight 1 (prior.features_by_blend).  out: f32 [1, G, >= V]; rows, label_offset as blend's."""
+        from .prior import features_by_blend
+        return features_by_blend(self, rows, label_offset, out, V, zeros)
+
+    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
+        """Fit the weight by maximum likelihood of val's targets under softmax(blend) (priorfit.fit: Newton passes of
+        train.PriorFitLoop(model, collator, val, self, **loop_kw), no grid), set it and return the priorfit.FitResult.  `val` must
+        be held out of the sessions the table was fitted on, and is not the test split: the weight is fitted to it."""
+        from .priorfit import fit
+        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)
+
     def for_loop(self, model, device, rows, what):
         """What a loop checks once, on the host, before it captures anything with this prior."""
         if torch.device(device) != self.device:

@@ -82,6 +82,33 @@ def sweep_weights(W, what="prior_weights", names=WEIGHTS):
     return check_weights(w, what, names)
 
 
+def features_by_blend(prior, rows, label_offset, out, V=None, zeros=None):
+    """What MarkovPrior.features and DistancePrior.features do: `prior`'s blend of a zero buffer, once per weight of its own, with
+    a unit weight row taken from a small identity kept on the prior's device -- plane k of out is then exactly the table value
+    the rule adds for weight k, 0 where it adds nothing (a term with weight 0 adds +0.0).  out: f32 [n_weights, G, >= V] with
+    unit column stride, its columns from V on left alone; V: the scored columns (default out.shape[2]); zeros: f32 [G, >= V]
+    zeros to blend (default: allocated).  One launch per weight, no host read."""
+    what = f"{type(prior).__name__}.features"
+    n = prior.n_weights
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != n or (out.shape[2] and out.stride(2) != 1):
+        got = f"{out.dtype} {tuple(out.shape)}" if isinstance(out, torch.Tensor) else type(out).__name__
+        raise ValueError(f"{what}: out must be f32 [{n}, G, >= V] with unit column stride, got {got}")
+    G = out.shape[1]
+    V = out.shape[2] if V is None else int(V)
+    if not 0 <= V <= out.shape[2]:
+        raise ValueError(f"{what}: V = {V} of {out.shape[2]} columns")
+    if zeros is None:
+        zeros = torch.zeros(G, V, dtype=torch.float32, device=out.device)
+    elif zeros.dtype != torch.float32 or zeros.dim() != 2 or zeros.shape[0] != G or zeros.shape[1] < V:
+        raise ValueError(f"{what}: zeros must be f32 [{G}, >= {V}], got {zeros.dtype} {tuple(zeros.shape)}")
+    eye = getattr(prior, "_eye", None)
+    if eye is None:
+        eye = prior._eye = torch.eye(n, dtype=torch.float32, device=prior.device)
+    for k in range(n):
+        prior.blend(zeros[:, :V], rows, label_offset, out=out[k], weights=eye[k])
+    return out
+
+
 def blend_host(scores, hist, user, prior_tables, weights, label_offset, user_offset=1, status=None):
     """The rule of the module's docstring -> f32 numpy [G, V].  scores [G, V] f32; hist [G, n] integer ids; user [G] (or [G, 1]);
     prior_tables a PriorTables; weights (wu, wg, wp); status: a list or array whose [0] gets the SBADINDEX bit ORed in."""
@@ -283,6 +310,18 @@ class MarkovPrior:
         self.set_weights(*grid[best].tolist())
         return results
 
+    def features(self, rows, label_offset, out, V=None, zeros=None):
+        """out[k, g, c] = what the rule adds to scores[g, c] per unit of weight k (user, transition, popularity; 0 where it adds
+        nothing): three blends of zeros, one per weight (features_by_blend).  out: f32 [3, G, >= V]; rows, label_offset as blend's."""
+        return features_by_blend(self, rows, label_offset, out, V, zeros)
+
+    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
+        """Fit the weights by maximum likelihood of val's targets under softmax(blend) (priorfit.fit: Newton passes of
+        train.PriorFitLoop(model, collator, val, self, **loop_kw), no grid), set them and return the priorfit.FitResult.  `val` must
+        be held out of the sessions the baseline was fitted on, and is not the test split: the weights are fitted to it."""
+        from .priorfit import fit
+        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)
+
 
 class Stack:
     """One or more priors blended in the order given, behind the interface the loops use of any prior (EvalLoop / PredictLoop,
@@ -387,3 +426,21 @@ class Stack:
         best = max(range(len(results)), key=lambda i: (results[i][key], -i))
         self.set_weights(**dict(zip(self.WEIGHTS, grid[best].tolist())))
         return results
+
+    def features(self, rows, label_offset, out, V=None, zeros=None):
+        """The members' features in WEIGHTS' order: member i fills its n_weights planes of out, f32 [n_weights, G, >= V]."""
+        if not isinstance(out, torch.Tensor) or out.dim() != 3 or out.shape[0] != self.n_weights:
+            got = tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__
+            raise ValueError(f"prior.Stack.features: out must be f32 [{self.n_weights}, G, >= V], got {got}")
+        at = 0
+        for p in self.priors:
+            p.features(rows, label_offset, out[at:at + p.n_weights], V, zeros)
+            at += p.n_weights
+        return out
+
+    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
+        """MarkovPrior.fit_weights for the stack: all n_weights weights at once, by maximum likelihood (priorfit.fit), set and
+        returned as a priorfit.FitResult.  `val` must be held out of the sessions the members were fitted on, and is not the test
+        split: the weights are fitted to it."""
+        from .priorfit import fit
+        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)

@@ -1631,3 +1631,108 @@ class PredictLoop(_FrozenModelLoop):
         if self.prior is not None:
             self.prior.check("PredictLoop")
         return sample_index, ids, vals
+
+
+class PriorFitLoop(_FrozenModelLoop):
+    """One pass of the priors' maximum-likelihood weight fit (priorfit.py's docstring is the rule) over a held-out split, on
+    EvalLoop's device data path: the eval loader's order, EpochLoop's buckets and staging, the weights as they are when run()
+    starts, and per (G, bucket, forms.on("safe_forms")) ONE captured graph of
+
+        model.poi_scores(model.encode(batch))                      the scores, [G, V]
+        prior.features(batch, label_offset, ...)                   one blend of zeros per weight, into planes of ONE [K, rows, V] buffer
+                                                                   (with scale_model the scores are copied into plane 0)
+        mobgt_priorfit_terms                                       n, nll, gradient, Hessian of every (weight row, sample)
+        acc += terms.sum(1)                                        ONE f64 [rows, NT] accumulator
+
+    -- eager with use_graph=False and for collators whose finish needs torch ops, as in the other loops.
+
+    prior: a prior.MarkovPrior, a geoprior.DistancePrior or a prior.Stack on the loop's device.  scale_model: the model's scores are
+    feature 0 and scaled by a weight of their own, K = 1 + prior.n_weights; else they are the base and K = prior.n_weights.
+    weights: the first weight rows, [L, K] (default: one row, `start` -- the prior's current weights, after a 1 for the model's
+    scale).  rows: how many weight rows every launch evaluates (default 4: a Newton pass's step lengths); the graphs always
+    evaluate that many, so a pass with fewer repeats its first row and no pass needs a new capture.
+
+    set_rows(W) overwrites the device f64 [rows, K] the graphs read; run() zeroes the accumulator and the status words, makes one
+    pass and reads the accumulator once: -> f64 numpy [L, NT], the terms summed over this split's samples for each row set.
+    SNONFINITE (scores or features that are not finite) and a prior's SBADINDEX are a ValueError.  A fit on several ranks or
+    under a restriction is not offered: world > 1, exclude_visited, candidates and within_km are refused."""
+
+    def __init__(self, model, collator, dataset, prior, weights=None, scale_model=True, batch_size=16, use_graph=True, rows=4,
+                 rank=None, world=None, buckets=None, side_collate=True, exclude_visited=False, candidates=None, within_km=None):
+        import numpy as np
+        from . import _priorfit, priorfit
+        if not (hasattr(model, "poi_scores") and hasattr(model, "encode")):
+            raise TypeError("PriorFitLoop: the model has no encode / poi_scores (the fq model, model_fqandtoyo.Graphormer)")
+        if exclude_visited or candidates is not None or within_km is not None:
+            raise ValueError("PriorFitLoop: a fit under a restriction (exclude_visited, candidates, within_km) is not offered: the "
+                             "likelihood is that of the unrestricted softmax")
+        self.scale_model = bool(scale_model)
+        self.K = prior.n_weights + self.scale_model
+        if self.K > _priorfit.MAX_K:
+            raise ValueError(f"PriorFitLoop: {prior.n_weights} prior weights" + " and the model's scale" * self.scale_model +
+                             f" are {self.K} features, one launch takes up to {_priorfit.MAX_K} (MOBGT_PRIORFIT_MAX_K)")
+        self.rows = int(rows)
+        if not 1 <= self.rows <= _priorfit.MAX_L:
+            raise ValueError(f"PriorFitLoop: rows = {rows} outside 1 .. {_priorfit.MAX_L} (MOBGT_PRIORFIT_MAX_L)")
+        super().__init__(model, collator, dataset, batch_size, rank, world, use_graph, buckets, side_collate)
+        if self.world > 1:
+            raise ValueError(f"PriorFitLoop: world = {self.world}: a fit on several ranks is not offered (run it on one)")
+        prior.for_loop(model, self.device, self.batch_size, "PriorFitLoop")
+        self.prior = prior
+        V, B, K, L = model.out_proj.out_features, self.batch_size, self.K, self.rows
+        self.NT = priorfit.nt_of(K)
+        dev = self.device
+        self.start = np.r_[[1.0] * self.scale_model, [prior.get_weights()[k] for k in prior.WEIGHTS]].astype(np.float64)
+        self.W = torch.zeros(_priorfit.MAX_L, K, dtype=torch.float64, device=dev)
+        self.feats = torch.zeros(K, B, V, dtype=torch.float32, device=dev)
+        self.zeros = torch.zeros(B, V, dtype=torch.float32, device=dev)
+        self.terms = torch.zeros(L * B * self.NT, dtype=torch.float64, device=dev)
+        self.work = torch.empty(max(priorfit.work_bytes(K, B, V, L), 8), dtype=torch.uint8, device=dev)
+        self.acc, self._scratch = (torch.zeros(L, self.NT, dtype=torch.float64, device=dev) for _ in range(2))
+        self.status, self._scratch_status = (torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2))
+        self.live = 0
+        self.set_rows(self.start[None, :] if weights is None else weights)
+
+    def set_rows(self, W):
+        """The weight rows of the next run(): [L, K] finite numbers, 1 <= L <= rows; the rows beyond L repeat the first."""
+        import numpy as np
+        W = np.asarray(W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.K or not 1 <= W.shape[0] <= self.rows or not np.isfinite(W).all():
+            names = ("scale",) * self.scale_model + tuple(self.prior.WEIGHTS)
+            raise ValueError(f"PriorFitLoop.set_rows: 1 .. {self.rows} finite rows of ({', '.join(names)}) weights, got shape {tuple(W.shape)}")
+        full = np.concatenate([W, np.repeat(W[:1], self.rows - len(W), axis=0)])
+        self.W[:self.rows].copy_(torch.from_numpy(full))
+        self.live = len(W)
+        return self
+
+    def _step(self, slot, warm):
+        from . import priorfit
+        model, lo, s = self.model, self.model.label_offset, int(self.scale_model)
+        batch = self._collated(slot["batch"])
+        with torch.no_grad():
+            scores = model.poi_scores(model.encode(batch))
+            G, V = scores.shape
+            feats = self.feats[:, :G]
+            if s:
+                feats[0].copy_(scores)
+            self.prior.features(batch, lo, feats[s:], V, self.zeros[:G])
+            terms = self.terms[:self.rows * G * self.NT].view(self.rows, G, self.NT)
+            priorfit.terms(None if s else scores, feats, batch.y, -lo, self.W[:self.rows], V=V, work=self.work, out=terms,
+                           status=self._scratch_status if warm else self.status)
+            (self._scratch if warm else self.acc).add_(terms.sum(1))
+
+    def run(self, max_batches=None):
+        """One pass over the split with the rows last set -> f64 numpy [L, NT]: sums of (n, nll, g_k, H_kj) over the samples."""
+        with self._evaluating():
+            self.acc.zero_()
+            self.status.zero_()
+            self.prior.reset_status()
+            for _ in self._pipeline(self.batches(max_batches)):
+                pass
+            sums = self.acc.cpu().numpy()                   # the one read of the accumulator: the pass is over
+            bits = int(self.status[0])
+            self.prior.check("PriorFitLoop")
+        if bits:
+            raise ValueError(f"PriorFitLoop: scores or features that are not finite (status {bits}): a row held NaN or +inf, a "
+                             "feature that is not finite, nothing but -inf, or -inf at its target; such rows were left out")
+        return sums[:self.live]
