@@ -915,8 +915,10 @@ int mobgt_head_chain_bwd(const float* dout, const float* u3, const float* mean, 
  *   forward   h1 = leaky(ax w0 + b0);  t = a h1;  h2 = dropout(leaky(t w1 + b1));  t2 = a h2;  out = t2 w2 + b2
  *             ax = a @ x precomputed [n,K0]; a [n,n]; w* [in,out] row-major; h1/t [n,H1], h2/t2 [n,H2] are kept for the
  *             backward; out [n,H3].  (H1, H2, H3) = (16, 64, 32) (the widths MobGT uses; others: MOBGT_EBADDIM); n <= 4096.  Dropout mask / slope as mobgt_bias_act_fwd.
+ *             w0, w1, w2, h1 and h2 16-byte aligned (else MOBGT_EALIGN).
  *   backward  g = d(out); a_t = a^T [n,n]; dw* / db* are ACCUMULATED (f32 atomics: zero them first); dt2 [n,H2] and
- *             dt [n,H1] are scratch. */
+ *             dt [n,H1] are scratch.  w1, w2, dt2 and dt 16-byte aligned (else MOBGT_EALIGN).
+ *   A refused call launches nothing and leaves `counter` alone. */
 int mobgt_small_gcn_fwd(const float* ax, const float* a, const float* w0, const float* b0, const float* w1, const float* b1,
                         const float* w2, const float* b2, float* h1, float* t, float* h2, float* t2, float* out, int* counter,
                         int n, int K0, int H1, int H2, int H3, float slope, float dropout_p, uint64_t seed,

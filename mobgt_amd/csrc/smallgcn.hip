@@ -382,7 +382,17 @@ __global__ __launch_bounds__(NT) void small_gcn_fwd_kernel(const SmallGcnParams 
     STAMP(1);
     // layer 1 (the constant product A X comes in precomputed)
     if (early) tile_product<H1, true, true, false>(smem, smem + OFF_L2, p.AX, p.K0, p.W0, p.K0, r0, p.n, tl);
-    else tile_product<H1, false, false, false>(smem, Lc, p.AX, p.K0, p.W0, p.K0, r0, p.n, tl);
+    else {
+        tile_product<H1, false, false, false>(smem, Lc, p.AX, p.K0, p.W0, p.K0, r0, p.n, tl);
+        if (p.n <= KC) {
+            // n <= KC < K0: layers 2 and 3 take Lc for this workgroup's rows of A (L_STAGED with a single chunk), but layer 1 has
+            // just streamed its chunks of AX through it -- stage the rows of A now (the product's last barrier freed Lc)
+            BurstL la;
+            la.load(p.A, p.n, 0, p.n, np, r0, p.n);
+            la.store(Lc, np);
+            __syncthreads();
+        }
+    }
     STAMP(2);
 #pragma unroll
     for (int u = 0; u < RB * H1 / NT; ++u) {
@@ -619,7 +629,7 @@ extern "C" int mobgt_small_gcn_fwd_pack(const float* ax, const float* a, const f
     int rc = check(p);
     if (rc) return rc;
     set_drop(p, dropout_p, seed, seed_dev, salt);
-    if (((uintptr_t)w0 | (uintptr_t)h1 | (uintptr_t)h2) & 15) return MOBGT_EALIGN;
+    if (((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)h1 | (uintptr_t)h2) & 15) return MOBGT_EALIGN;   // float4 loads
     if ((rc = lds_opt_in((const void*)small_gcn_fwd_kernel<16, 64, 32>))) return rc;
     p.nwg = (n + RB - 1) / RB;
     static mobgt_pack::PackJobs jobs;            // (by value into the launch; 3 KB -- not on the stack of every call)
@@ -684,7 +694,7 @@ extern "C" int mobgt_small_gcn_bwd_bias(const float* g, const float* ax, const f
     int rc = check(p);
     if (rc) return rc;
     set_drop(p, dropout_p, seed, seed_dev, salt);
-    if (((uintptr_t)dt2 | (uintptr_t)dt) & 15) return MOBGT_EALIGN;
+    if (((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)dt2 | (uintptr_t)dt) & 15) return MOBGT_EALIGN;           // float4 loads
     if ((rc = lds_opt_in((const void*)small_gcn_bwd_kernel<16, 64, 32>))) return rc;
     p.nwg = (n + RB - 1) / RB;
     BuildParams bp = {};

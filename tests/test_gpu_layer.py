@@ -924,7 +924,7 @@ def test_weight_pack_as_passenger_of_the_category_gcn_launch_equals_the_pack_lau
     x[torch.arange(N)[None, :] >= torch.randint(3, N + 1, (G, 1), generator=g)] = 0
     x = x.to(DEV)
     tn = torch.rand(G, N, generator=g).to(DEV)
-    poi2cat = torch.randint(0, 300, (P,), generator=g).to(DEV)
+    poi2cat = torch.randint(0, 300, (P + 1,), generator=g).to(DEV)             # [P + 1]: indexed by the POI id itself
     indeg, outdeg = (torch.randint(0, 64, (G, N), generator=g).to(DEV) for _ in range(2))
     D, E, H = 20, 40, 8
     ew, dw = torch.randn(E, H, generator=g).to(DEV), torch.randn(D * H * H, 1, generator=g).to(DEV)

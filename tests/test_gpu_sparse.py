@@ -185,7 +185,7 @@ def test_mask_gemm_matches_the_dense_normalised_adjacency():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,k0,training", [(300, 300, True), (300, 300, False), (37, 21, True), (513, 40, True)])
+@pytest.mark.parametrize("n,k0,training", [(300, 300, True), (300, 300, False), (37, 21, True), (513, 40, True), (300, 400, False)])
 def test_small_gcn_single_launch_matches_the_layer_by_layer_path(n, k0, training, monkeypatch):
     """csrc/smallgcn.hip (the category GCN as one persistent launch each way) against the same GCN evaluated layer by
     layer (GraphConvolution + bias_act launches) and against plain torch fp32: same dropout mask, same values."""
