@@ -759,3 +759,4 @@ from .prefixes import PrefixDataset, PrefixStats, prefix_stats, prefix_stats_hos
 from .baseline import MarkovBaseline  # noqa: E402,F401
 from .prior import MarkovPrior  # noqa: E402,F401
 from .geoprior import DistancePrior  # noqa: E402,F401
+from .ctxprior import ContextPrior  # noqa: E402,F401

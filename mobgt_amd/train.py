@@ -1451,10 +1451,13 @@ class EvalLoop(_FrozenModelLoop):
     with the accumulator; a status that is not zero (tables that fit did not make) is a ValueError.
 
     prior may also be a geoprior.DistancePrior (mb.distance_prior(pair_bins): a fitted distance-decay table, the rule in
-    geoprior.py's docstring, the same anchor) or a prior.Stack of several priors, blended in the order given, one launch each.
+    geoprior.py's docstring, the same anchor), a ctxprior.ContextPrior (data.ContextPrior.fit(ds, train): the category-transition
+    and time-of-day tables, the rule in ctxprior.py's docstring, the same anchor, its category and its slot read from batch.cat
+    and batch.time) or a prior.Stack of several priors, blended in the order given, one launch each.
 
     prior_weights: a sweep, [L, prior.n_weights] rows of prior.WEIGHTS -- (user, transition, popularity) for a MarkovPrior,
-    (distance,) for a DistancePrior, the members' names concatenated for a Stack -- 1 <= L <= 16.  Every batch is encoded ONCE;
+    (distance,) for a DistancePrior, (category, time) for a ContextPrior, the members' names concatenated for a Stack --
+    1 <= L <= 16.  Every batch is encoded ONCE;
     for each row the scores are blended out of place into one scratch [batch_size, V] with that row's weights and ranked into
     an accumulator of the row's own; run() returns the list of the L dicts, each what a loop with those weights returns.  The
     prior's own weights are not used and not changed (prior.tune picks the best row and sets it)."""
