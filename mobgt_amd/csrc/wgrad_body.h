@@ -107,12 +107,16 @@ struct Slab {
 // partial tiles -- the upper half of the waves hand their tiles to the lower half first -- and NWAVE column partials
 template <int NWAVE> constexpr int wgrad_lds_floats() { return (NWAVE / 2) * TILE * TILE + NWAVE * TILE; }
 
-template <bool F32, int NWAVE, bool XF32 = F32>
+// WGW: the waves of the workgroup that calls this, when they are more than NWAVE (csrc/tokbwd.hip: 12); the first NWAVE do the
+// work -- the sums are then those of an NWAVE-wave launch, bit for bit -- and the others only keep the barriers company
+template <bool F32, int NWAVE, bool XF32 = F32, int WGW = NWAVE>
 __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int tile, const int split, const int nsplit,
                                            float* __restrict__ lds) {
+    static_assert(WGW >= NWAVE, "a workgroup of at least NWAVE waves");
     float (*part)[TILE * TILE] = reinterpret_cast<float (*)[TILE * TILE]>(lds);
     float (*colpart)[TILE] = reinterpret_cast<float (*)[TILE]>(lds + (NWAVE / 2) * TILE * TILE);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool act = WGW == NWAVE || wave < NWAVE;
     const int i = lane & 15, kq = lane >> 4;
     const int m0 = (tile / p.tiles_n) * TILE, n0 = (tile % p.tiles_n) * TILE;
     const int k0 = split * p.k_per_wg;
@@ -137,7 +141,7 @@ __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int tile,
         if (masked) s_.template load_masked<F32>(p, gp, xp, gm, xm, r0_, k1, m_ok, n_ok, gkeep);
         else s_.template load<F32, XF32>(gp, xp, p.ldg, p.ldx, r0_, k1, m_ok, n_ok);
     };
-    int kb = k0 + wave * KSTEP;
+    int kb = act ? k0 + wave * KSTEP : k1;
     Slab cur, nxt;
     if (kb < k1) fetch(cur, kb + 8 * kq);
     for (; kb < k1; kb += NWAVE * KSTEP) {
@@ -162,7 +166,7 @@ __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int tile,
 
     // register v of lane (j = lane & 15, q = lane >> 4) is MFMA row 4q + v, column j; operand row i / column j
     // stand for tile rows 2i+a and columns 2j+b
-    if (wave >= NWAVE / 2) {
+    if (wave >= NWAVE / 2 && act) {
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -179,13 +183,13 @@ __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int tile,
 #pragma unroll
                 for (int v = 0; v < 4; ++v) part[wave][(2 * (4 * kq + v) + a) * TILE + 2 * i + b] += acc[a][b][v];
     }
-    if (want_db) {
+    if (want_db && act) {
         se += __shfl_xor(se, 16, 64); se += __shfl_xor(se, 32, 64);
         so += __shfl_xor(so, 16, 64); so += __shfl_xor(so, 32, 64);
         if (kq == 0) { colpart[wave][2 * i] = se; colpart[wave][2 * i + 1] = so; }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < TILE * TILE; e += NWAVE * 64) {
+    for (int e = act ? threadIdx.x : TILE * TILE; e < TILE * TILE; e += NWAVE * 64) {
         const int r = e >> 5, c = e & 31;
         float s = 0.f;
 #pragma unroll

@@ -32,6 +32,10 @@ _ROWS = (
     Form("skinny_all", "MOBGT_SKINNY_ALL", False, "all three classifier products on csrc/skinny.hip (off: dW / db only)"),
     Form("token_fwd_chain", "MOBGT_NO_TOKEN_FWD_CHAIN", True, "the encoder input's forward as one launch (off: four)"),
     Form("token_bwd_chain", "MOBGT_NO_TOKEN_BWD_CHAIN", True, "the encoder input's backward as one launch, csrc/tokbwd.hip (off: three)"),
+    Form("l0_token_host", "MOBGT_NO_L0_TOKEN_HOST", True, "the first encoder layer leaves dx and its weight gradients to the encoder "
+         "input's one-launch backward (off: it finishes its own backward); no workgroup waits for another, so safe_forms keeps it"),
+    Form("l0_token_host_eager", "MOBGT_L0_TOKEN_HOST_EAGER", False, "l0_token_host outside a graph capture as well (off: only a step "
+         "that is being captured defers; an eager step is bound by the host, gains nothing and keeps its launch list)"),
     # ---- jobs that ride in another launch (off: a launch of their own)
     Form("pack_passenger", "MOBGT_NO_PACK_PASSENGER", True, "the layers' weight pack, in the next front launch"),
     Form("front_passengers", "MOBGT_NO_FRONT_PASSENGERS", True, "hop table forward and node-feature indices, in the category GCN's forward"),

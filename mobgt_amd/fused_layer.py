@@ -355,7 +355,8 @@ class LayerConfig:
         self.seed, self.seed_dev, self.salt = int(seed), seed_dev, int(salt) & 0xFFFFFFFF
         self.pack = pack
         self.act_dtype = act_dtype
-        self.from_layer = False   # the layer's input is the output of another fused layer (model.fused_layer_forward)
+        self.from_layer = False   # the layer's input is the output of another fused layer (model.fused_layer_forward) ...
+        self.token_host = False   # ... or of the one-launch encoder input, whose backward launch is then the host (forms "l0_token_host")
         self.next_qkv = None      # (packed wqkv, bqkv) of the NEXT fused layer: its QKV projection rides in this layer's chain
         self.packed = None        # (wo, w1, w2) of this layer in MFMA operand order (model.pack_layer_weights)
         self.packed_t = None      # (w2^T, w1^T, wo^T, wqkv^T) likewise, for the backward chain
@@ -647,6 +648,9 @@ class _FusedLayerFn(torch.autograd.Function):
         busy = getattr(ctx, "_mobgt_pending", None)     # (model.note_pending_backward: the layer's shadows may be rewritten again)
         if busy is not None:
             busy.done()
+        if cfg.token_host and not (STEP.wgrad_on and forms.on("l0_token_host") and forms.on("token_bwd_chain")):
+            # (the encoder input's backward is the one launch only inside a train step, and the switches are read now)
+            plan = plan._replace(below_hosts=False)
         preln = plan.body == "preln_chain"
         dout = dout.contiguous().view(R, C).float()
         if preln:

@@ -2,16 +2,19 @@
 that every combination can be enumerated without a GPU (tests/test_host_layer_plan.py).  `plan_forward` is filled at the top of the
 layer's forward, `plan_backward` at the top of its backward; a form is read -- by the caller, into `on` -- at the moment the pass
 that uses it starts, so switching forms between a forward and its backward acts as it always did.
-Of the package it imports only _lib, for the constants of the library's header: like forms.py it needs no torch, and no built
+Of the package it imports only _lib and _tokhost, for the constants of the libraries' headers: like forms.py it needs no torch, and no built
 library."""
 from collections import namedtuple
 
-from . import _lib
+from . import _lib, _tokhost
 
 CHAIN_SHAPES = ((128, 1024), (192, 1024), (256, 1024))     # (C, F) the chain kernels are instantiated for (csrc/chain.hip)
 BIG_R = _lib.CONSTANTS["MOBGT_CHAIN_BIG_ROWS"]     # rows past which the library's tiles / the 64-row chain kernels take a layer's products
 TAIL_MAX_R = 1024        # rows up to which the tail GEMM of mobgt_layer_backward_tail is sized
 DEFER_MAX_R = 4096       # S-GOW: 1024 / 2048 / 4096 / 16384 -> 18.96 / 19.33 / 19.65 / 19.5 k check-ins/s
+# rows up to which the encoder input's backward launch hosts the FIRST layer's tail (forms "l0_token_host"; model.fused_layer_forward
+# then names that launch as the layer's host through Given.from_layer, and the rules below are those of any hosted layer)
+TOKEN_HOST_MAX_R = _tokhost.MAX_ROWS
 
 FORWARD_FORMS = ("own_gemm", "ln_gemm", "stock_ln_qkv", "chain", "chain_big", "chain_bwd")
 BACKWARD_FORMS = ("ln_gemm_bwd", "wgrad_big", "defer_tail", "tail")

@@ -231,7 +231,16 @@ def fused_layer_forward(layer, variant, x, attn_bias, n1, nx, next_layer=None):
     cfg = LayerConfig(variant, mha.num_heads, mha.scale, p, p_att, seed, mha.seed_dev, mha._layer_index * 8, pack, act)
     # (a layer the trainer cuts the backward pass in front of -- train.TrainStep's layer-wise gradient buckets -- finishes its own
     # input gradient: the layer below runs in another autograd pass and cannot host this one's tail)
-    cfg.from_layer = bool(getattr(x, "_mobgt_from_layer", False)) and not getattr(layer, "_mobgt_cut", False)
+    cut = getattr(layer, "_mobgt_cut", False)
+    # The FIRST layer behind the one-launch encoder input (ops.assemble_tokens marks its output): that input's backward launch hosts
+    # the layer's tail the way a lower layer's chain launch would (csrc/tokbwd.hip; fq variant, the rows mobgt_layer_backward_tail
+    # serves).  The switches are read again when the backward runs (fused_layer: outside a train step nothing is deferred).
+    cfg.token_host = bool(variant != "stock" and getattr(x, "_mobgt_token_host", False) and not cut and forms.on("l0_token_host")
+                          and forms.on("token_bwd_chain") and G * T <= layer_plan.TOKEN_HOST_MAX_R
+                          # (a launch boundary costs in a replayed graph; an eager step waits for the host between launches, so
+                          #  it keeps the layer's own launch unless forms "l0_token_host_eager" asks)
+                          and (torch.cuda.is_current_stream_capturing() or forms.on("l0_token_host_eager")))
+    cfg.from_layer = (bool(getattr(x, "_mobgt_from_layer", False)) and not cut) or cfg.token_host
     # the next layer's QKV projection rides in this layer's chain kernel (csrc/chain.hip) when that layer is fused, has
     # the same activation dtype and its bf16 shadows are current (refresh_shadows / the trainer refreshed ALL layers)
     nxt = next_layer

@@ -8,7 +8,7 @@ import math
 
 import torch
 
-from . import _lib, forms
+from . import _lib, _tokhost, forms
 from ._lib import F32, BF16, I64, I32, I16, U8, check
 from .step_state import STEP
 
@@ -1762,12 +1762,32 @@ def _token_park_linear(g, w, y):
         W2 = ent["w2"].shape[0]
         d_pt = torch.empty(G * N, W2, dtype=torch.float32, device=g.device)
         dx4 = pend["dx4"]
-        _lib.call("mobgt_token_bwd_chain", _p(pend["dout"]), _p(pend["real"]), _p(ent["nf"]), _p(ent["x4"]), ent["x4"].stride(0),
-                  _p(ent["w4"]), _p(ent["w2"]), _p(pend["d_nf"]), _p(pend["d_add"]), _p(dx4), dx4.stride(0),
-                  _p(d_pt), _p(pend["d_tok"]), G, N, C, W2, ent["slope4"], ent["slope2"], p_pos, p_in, seed,
-                  _p(seed_dev), salts[0], salts[1], salts[2], _stream())
+        args = (_p(pend["dout"]), _p(pend["real"]), _p(ent["nf"]), _p(ent["x4"]), ent["x4"].stride(0),
+                _p(ent["w4"]), _p(ent["w2"]), _p(pend["d_nf"]), _p(pend["d_add"]), _p(dx4), dx4.stride(0),
+                _p(d_pt), _p(pend["d_tok"]), G, N, C, W2, ent["slope4"], ent["slope2"], p_pos, p_in, seed,
+                _p(seed_dev), salts[0], salts[1], salts[2])
+        tail = pend.get("tail")
+        if tail is None:
+            _lib.call("mobgt_token_bwd_chain", *args, _stream())
+        else:
+            # the first encoder layer's parked tail (forms "l0_token_host"): `dout` holds its dx1; the launch finishes
+            # dx1 + dqkv Wqkv per row block before it reads the rows and runs the four weight gradients as extra workgroups
+            from .fused_layer import _wgrad_arrays
+            _tokhost.launch("mobgt_tokhost_token_bwd_chain", *args, _p(tail["dqkv"]), _p(tail["wqt"]), _p(tail["dx1"]),
+                      *_wgrad_arrays(tail["items"]), _stream())
         return d_pt
     return None
+
+
+def _token_can_host(tail, dout, rows, C):
+    """The one-launch encoder-input backward takes a parked layer tail along: dx and four bf16 weight-gradient problems of the
+    layer whose input gradient `dout` is, within the row count mobgt_layer_backward_tail serves."""
+    dqkv, wqt, items = tail["dqkv"], tail["wqt"], tail["items"]
+    return (forms.on("l0_token_host") and tail["kind"] == "layer" and tail["R"] == rows and C == 192
+            and rows <= _tokhost.MAX_ROWS and 1 <= len(items) <= _tokhost.MAX_WG and tail["dx1"].data_ptr() == dout.data_ptr()
+            and dout.dtype == torch.float32 and dout.data_ptr() % 16 == 0 and dqkv.dtype == torch.bfloat16 and dqkv.is_contiguous()
+            and tuple(dqkv.shape) == (rows, 3 * C) and dqkv.data_ptr() % 16 == 0 and wqt.data_ptr() % 16 == 0
+            and all(g_.dtype == torch.bfloat16 and x_.dtype == torch.bfloat16 and g_.shape[0] == rows for g_, x_, _, _ in items))
 
 
 class _LinearSplitKFn(torch.autograd.Function):
@@ -2210,11 +2230,19 @@ class _AssembleTokensFn(torch.autograd.Function):
             d_tok = zeros_f32((C,), dout.device)
             d_pe = d_tok.view(pshape)
         ent = STEP.token_chain
-        if (ent is not None and ent["nf_ptr"] == ctx.nf_ptr and STEP.wgrad_on and C == ent["nf"].shape[1]
-                and G * N == ent["nf"].shape[0] and forms.on("token_bwd_chain")):
+        park = (ent is not None and ent["nf_ptr"] == ctx.nf_ptr and STEP.wgrad_on and C == ent["nf"].shape[1]
+                and G * N == ent["nf"].shape[0] and forms.on("token_bwd_chain"))
+        # what the first encoder layer parked under this gradient (fused_layer._park_tail; forms "l0_token_host"): it travels with
+        # the parked chain to the one launch -- or, without one, is finished right here as the launch the layer would have issued
+        from . import fused_layer
+        tail = fused_layer._take_tail(dout)
+        if tail is not None and not (park and _token_can_host(tail, dout, G * (N + 1), C)):
+            fused_layer._complete_pending(tail)
+            tail = None
+        if park:
             # park: FuseEmbeddings-2's backward, two autograd nodes further down, launches the one kernel that fills d_nf / d_add
             STEP.token_pending[d_nf.data_ptr()] = dict(stage=1, ent=ent, dout=dout, real=real, d_nf=d_nf, d_add=d_add, d_tok=d_tok,
-                                                       misc=(G, N, C, p_pos, p_in, seed, seed_dev, salts))
+                                                       misc=(G, N, C, p_pos, p_in, seed, seed_dev, salts), tail=tail)
         else:
             _lib.call("mobgt_assemble_tokens_bwd", _p(dout), _p(real), _p(d_nf), _p(d_add), _p(d_tok), G, N, C, p_pos, p_in, seed,
                       _p(seed_dev), salts[0], salts[1], salts[2], _stream())
@@ -2251,6 +2279,11 @@ def assemble_tokens(nf, real, add, token, pe0, p_pos, p_in, training, salts=(0x1
         out._mobgt_act = side[0]          # bf16 copy for the first fused layer's QKV GEMM (no cast launch)
         if len(side) > 1:
             out._mobgt_qkv = side[1]      # `first_qkv` = (packed wqkv, bqkv) of that layer: its QKV projection, from this launch
+            ent = STEP.token_chain
+            if ent is not None and ent["nf_ptr"] == nf.data_ptr() and nf.shape[-1] == 192:
+                # ... and the backward of this encoder input can be the one launch: it may then finish what that layer's backward
+                # leaves undone, as the chain launch of a layer below would (model.fused_layer_forward; forms "l0_token_host")
+                out._mobgt_token_host = True
     return out
 
 

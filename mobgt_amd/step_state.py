@@ -23,7 +23,8 @@ FIELDS = (
     Field("token_fwd", PARKED, dict, "'gather' / 'f2' / 'f4': _GatherMultiFn / _LinearSplitKFn.forward record; _AssembleTokensFn launches them as one"),
     Field("token_fwd_fused_calls", CARRIED, int, "how often mobgt_token_fwd_chain took the three records (a counter for tests)"),
     Field("token_chain", CARRIED, _none, "ops.register_token_chain: the encoder-input chain of the forward that just ran; its backward reads it"),
-    Field("token_pending", PARKED, dict, "_AssembleTokensFn.backward parks under a gradient's address; FuseEmbeddings-4 / -2's backward re-park / launch"),
+    Field("token_pending", PARKED, dict, "_AssembleTokensFn.backward parks under a gradient's address (with the first layer's tail, taken from layer_tails, "
+          "under 'tail'); FuseEmbeddings-4 / -2's backward re-park / launch"),
     Field("front_sgemm", PARKED, dict, "'job': ops.front_small_gemm parks, the bias assembly's launch takes; 'done': its result until ops.small_gemm asks"),
     Field("wgrad_on", SWITCH, bool, "ops.recording_wgrads around the trainer's backward"),
     Field("wgrad_items", PARKED, list, "leaf weight gradients (ops.linear_wgrad*, fused layers) for ops.flush_deferred_wgrads' grouped launch"),
@@ -31,7 +32,8 @@ FIELDS = (
     Field("wgrad_hop_wide", PARKED, _none, "_HopTableFn.backward past 256 edge ids; shares the flush's stock tail launch"),
     Field("wgrad_stock_tok", PARKED, _none, "_StockTokensFn.backward parks; the flush's stock tail launch takes"),
     Field("wgrad_psum", PARKED, list, "ops.defer_partial_sum: split-K partial sums for the flush's one reduction launch"),
-    Field("layer_tails", PARKED, dict, "(graph task, device, address of dx1) -> a fused layer's tail; the chain launch of the layer below takes"),
+    Field("layer_tails", PARKED, dict, "(graph task, device, address of dx1) -> a fused layer's tail; the chain launch of the layer below (first layer: "
+          "the encoder input's backward) takes"),
     Field("tail_check_task", PARKED, _none, "graph task whose end-of-backward check (fused_layer._pending_check) is queued"),
     Field("weight_pack", PARKED, list, "model.pack_layer_weights(defer=True) parks; the category GCN's / stock front's forward launch takes"),
     Field("gcn_prelaunched", PARKED, dict, "modelGNN.prelaunch_small_gcn: id(module) -> (key, result); that module's forward adopts it"),
