@@ -96,8 +96,8 @@ int mobgt_ctxprior_slot_hist(const void* seq, int64_t M, const void* offsets, in
  *      poi_cat [P] int32;  cat_table [n_cat, n_cat] f32;  slot_table [n_slots, n_cat] f32
  *      weights [2] f32 (category, time), read on the device
  * Out: out [G, >= V] f32, ld_out elements between rows; columns from V on are left alone
- * A workgroup of THREADS threads per (chunk of CHUNK columns, row).  It finds the row's anchor position (a maximum over the
- * positions of the entries that are not 0), reads ca and ta there, stages the PRODUCTS w_category * Tc[ca - 1, :] and
+ * A workgroup of THREADS threads per (chunk of CHUNK columns, row).  It finds the row's anchor position (the search of
+ * mobgt_amd/csrc_prior/blend_rows.h, shared by the three priors), reads ca and ta there, stages the PRODUCTS w_category * Tc[ca - 1, :] and
  * w_time * Tt[ta, :] in LDS (n_cat floats each, only those whose context is valid), and every thread blends CHUNK / THREADS
  * columns: the score and poi_cat, two LDS reads, two adds, one store.  An element is read and written by the same thread, so in
  * place is safe.

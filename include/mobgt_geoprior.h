@@ -90,7 +90,7 @@ int mobgt_geoprior_csr_hist(const void* unit, int64_t P, const void* thresholds,
  *      unit, thresholds as above;  table [nthr + 1] f32;  weight [1] f32, read on the device
  * Out: out [G, >= V] f32, ld_out elements between rows; columns from V on are left alone
  * A workgroup of THREADS threads per (chunk of CHUNK columns, row).  It stages the coarse thresholds and finds the row's anchor
- * (a maximum over the positions of the entries that are not 0), stages the anchor's unit vector, and every thread blends
+ * (the search of mobgt_amd/csrc_prior/blend_rows.h, shared by the three priors), stages the anchor's unit vector, and every thread blends
  * CHUNK / THREADS columns: one f64 chord, one search, one gather from the table.  An element is read and written by the same
  * thread, so in place is safe.
  * Limits: 0 <= G <= MAX_G; 0 <= V, n_hist_cols < 2^31; P and nthr as above; ld_scores, ld_out >= V; ld_hist >= n_hist_cols;

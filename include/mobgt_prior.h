@@ -68,8 +68,8 @@ int mobgt_prior_abi_version(void);
  * Out: out [G, >= V] f32, ld_out elements between rows; columns from V on are left alone
  *      status [1] int32       SBADINDEX is ORed in with a vector atomic; never cleared here
  *
- * A workgroup of THREADS threads per (chunk of CHUNK columns, row).  It finds the row's anchor (a maximum over the positions of
- * the entries that are not 0), checks the anchor's rowptr pair, and finds -- by searches that probe 64 places a step, a lane a
+ * A workgroup of THREADS threads per (chunk of CHUNK columns, row).  It finds the row's anchor (the search of
+ * mobgt_amd/csrc_prior/blend_rows.h, shared by the three priors), checks the anchor's rowptr pair, and finds -- by searches that probe 64 places a step, a lane a
  * place, with the same result in every lane -- the part of CSR row a whose columns lie in its chunk and, if that part is not
  * empty, the (u, a) range of ukey.  It loads its chunk of the row into LDS with the popularity term added, adds the entries'
  * terms there (a thread an entry; cu(u, a, p) by a binary search of the (u, a) range), and stores the chunk.  A rowptr pair

@@ -12,6 +12,7 @@ class MobgtCtxpriorError(NativeError):
 
 
 LIBRARY = Library("mobgt_ctxprior.h", "csrc_ctxprior", "libmobgt_ctxprior.so", "MOBGT_CTXPRIOR_", error=MobgtCtxpriorError,
+                  extra_inputs=("csrc_prior/blend_rows.h",),
                   missing="the context prior is counted and blended on the device only (host forms: ctxprior.slot_hist_host, "
                           "blend_host).",
                   errors={"EBADDIM": "size or parameter outside the supported limits", "EALIGN": "null or misaligned pointer",

@@ -12,6 +12,7 @@ class MobgtGeopriorError(NativeError):
 
 
 LIBRARY = Library("mobgt_geoprior.h", "csrc_geoprior", "libmobgt_geoprior.so", "MOBGT_GEOPRIOR_", error=MobgtGeopriorError,
+                  extra_inputs=("csrc_prior/blend_rows.h", "csrc_bins/bins_search.h", "../include/mobgt_bins.h"),
                   missing="the distance prior is fitted and blended on the device only (host forms: geoprior.pair_hist_host, "
                           "csr_hist_host, blend_host).",
                   errors={"EBADDIM": "size or parameter outside the supported limits", "EALIGN": "null or misaligned pointer",

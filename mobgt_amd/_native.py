@@ -32,10 +32,12 @@ class Library:
     are; `path` overrides `so`).  `prefix`: what the header's constants -- and in lower case its functions -- begin with.
     `missing` completes "<path> is missing:".  `errors`: {constant's name without the prefix: text} of the status codes that have
     a text; any other non-zero status is reported as a hipError_t.  `hip`: a HIP library -- built through hip.mk with hipcc, and
-    torch is imported before it is loaded."""
+    torch is imported before it is loaded.  `extra_inputs`: files outside `csrc` that its sources include (the Makefile's DEPS
+    beyond the header), relative to this module's directory or absolute: build() counts them as it counts the sources."""
 
-    def __init__(self, header, csrc, so, prefix, missing, error=NativeError, errors=None, hip=True, path=None):
+    def __init__(self, header, csrc, so, prefix, missing, error=NativeError, errors=None, hip=True, path=None, extra_inputs=()):
         self.header, self.csrc = os.path.join(_INCLUDE, header), os.path.join(_HERE, csrc)
+        self.extra_inputs = tuple(os.path.join(_HERE, f) for f in extra_inputs)
         self.path = path or os.path.join(_HERE, so)
         self.prefix, self.missing, self.error, self.hip = prefix, missing, error, hip
         self.SIGNATURES, self.CONSTANTS = _cabi.load(self.header)
@@ -47,10 +49,10 @@ class Library:
         return tuple(self.CONSTANTS[self.prefix + n] for n in names)
 
     def build(self, force=False):
-        """Run the source directory's Makefile if the library is missing or older than a source, a header, the Makefile or hip.mk
-        (hipcc cross-compiles for gfx950 without a GPU); `force`: run it anyway and leave the decision to make."""
+        """Run the source directory's Makefile if the library is missing or older than a source, a header, the Makefile, hip.mk or
+        one of `extra_inputs` (hipcc cross-compiles for gfx950 without a GPU); `force`: run it anyway and leave the decision to make."""
         inputs = [os.path.join(self.csrc, f) for f in os.listdir(self.csrc) if f.endswith((".hip", ".h", ".cpp", ".c", "Makefile"))]
-        inputs += [self.header] + [HIP_MK] * self.hip
+        inputs += [self.header, *self.extra_inputs] + [HIP_MK] * self.hip
         if force or not os.path.exists(self.path) or any(os.path.getmtime(s) > os.path.getmtime(self.path) for s in inputs):
             subprocess.check_call(["make", "-s", "-j4", "-C", self.csrc])
         return self.path

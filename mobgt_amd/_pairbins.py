@@ -12,6 +12,7 @@ class MobgtPairBinsError(NativeError):
 
 
 LIBRARY = Library("mobgt_pairbins.h", "csrc_pairbins", "libmobgt_pairbins.so", "MOBGT_PAIRBINS_", error=MobgtPairBinsError,
+                  extra_inputs=("csrc_bins/bins_search.h", "../include/mobgt_bins.h"),
                   missing="the distance bins of a batch's pairs are searched on the device only (host form: geo.batch_bins_host).",
                   errors={"EBADDIM": "size outside the supported limits", "EALIGN": "null or misaligned pointer"})
 lib, launch = LIBRARY.lib, LIBRARY.launch

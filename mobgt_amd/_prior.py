@@ -13,6 +13,7 @@ class MobgtPriorError(NativeError):
 
 
 LIBRARY = Library("mobgt_prior.h", "csrc_prior", "libmobgt_prior.so", "MOBGT_PRIOR_", error=MobgtPriorError,
+                  extra_inputs=("csrc_prior/blend_rows.h",),
                   missing="the Markov prior is blended on the device only (host form: prior.blend_host).",
                   errors={"EBADDIM": "size or parameter outside the supported limits", "EALIGN": "null or misaligned pointer",
                           "EDTYPE": "ids that are neither int32 nor int64"})

@@ -11,7 +11,8 @@
 // the grid, so it clears and flushes once however many sessions it counts.  With more cells every add is a 64-bit atomic on
 // global memory.
 //
-// blend_kernel -- ONE WORKGROUP PER (CHUNK OF COLUMNS, ROW): the anchor position, its category and slot, then the two rows of
+// blend_kernel -- ONE WORKGROUP PER (CHUNK OF COLUMNS, ROW): the anchor position (../csrc_prior/blend_rows.h), its category and
+// slot, then the two rows of
 // PRODUCTS w * T[.][k] staged in LDS, one f32 product per category -- the same bits as a product per element, and no multiply
 // is left in the column loop.  A thread blends CHUNK / THREADS columns, each read and written by that thread only, so in place
 // is safe: where both rows are 16-byte aligned four consecutive columns per lane (one 16-byte load and store), else one column
@@ -23,10 +24,10 @@
 #include <stdint.h>
 
 #include "mobgt_ctxprior.h"
+#include "../csrc_prior/blend_rows.h"
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int TPB = MOBGT_CTXPRIOR_THREADS;
 constexpr int WAVES = TPB / WAVE;
 constexpr int LDS_CELLS = MOBGT_CTXPRIOR_LDS_CELLS;
@@ -39,6 +40,7 @@ static_assert(LDS_MAX <= 160 * 1024, "the histogram fits a CU's LDS");
 static_assert(2 * sizeof(float) * MOBGT_CTXPRIOR_MAX_CAT <= 64 * 1024, "the blend's two rows of products fit the default LDS limit");
 static_assert((int64_t)MOBGT_CTXPRIOR_MAX_SLOTS * MOBGT_CTXPRIOR_MAX_CAT > LDS_CELLS, "the global form is reachable");
 static_assert((int64_t)MOBGT_CTXPRIOR_MAX_SLOTS * MOBGT_CTXPRIOR_MAX_CAT <= INT32_MAX, "a cell is an int");
+static_assert(MOBGT_CTXPRIOR_I32 == ROWS_I32 && MOBGT_CTXPRIOR_I64 == ROWS_I64, "blend_rows.h's dtype codes are this header's");
 
 // counts[slot * n_cat + b - 1] += 1 for every pair of a train session.  Dynamic LDS: IN_LDS only, n_slots * n_cat counts.
 template <bool IN_LDS>
@@ -85,22 +87,13 @@ __global__ __launch_bounds__(TPB) void slot_hist_kernel(const int32_t* __restric
     }
 }
 
-struct Rows {
-    const float* scores;
-    float* out;
-    int64_t ld_scores, ld_out, V, label_offset;
-    const void* hist;
-    int64_t ld_hist, n_hist;
+struct Rows : BlendRows {
     int hist64;
     const void* time;
     const void* cat;
     int64_t ld_ctx;
     int ctx64;
 };
-
-__device__ inline int64_t load_id(const void* p, int wide, int64_t i) {
-    return wide ? static_cast<const int64_t*>(p)[i] : static_cast<const int32_t*>(p)[i];
-}
 
 // Dynamic LDS: 2 * C floats, the category products then the time products.
 __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, const int32_t* __restrict__ poi_cat, int64_t P, const float* __restrict__ Tc,
@@ -109,25 +102,15 @@ __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, const int32_t* __re
     __shared__ int32_t last_of_wave[WAVES];
     float* s_c = s_terms;
     float* s_t = s_terms + C;
-    const int tid = threadIdx.x, lane = tid % WAVE;
+    const int tid = threadIdx.x;
     const int64_t g = blockIdx.y;
     const int64_t c0 = (int64_t)blockIdx.x * CHUNK;                     // < V
     const int32_t width = (int32_t)(in.V - c0 < CHUNK ? in.V - c0 : CHUNK);
 
-    // the anchor: the last entry of the history row that is not 0
-    int32_t last = -1;
-    for (int64_t i = tid; i < in.n_hist; i += TPB) {
-        if (load_id(in.hist, in.hist64, g * in.ld_hist + i) != 0) last = (int32_t)i;
-    }
-#pragma unroll
-    for (int d = WAVE / 2; d; d /= 2) {
-        const int32_t o = __shfl_xor(last, d, WAVE);
-        last = o > last ? o : last;
-    }
-    if (lane == 0) last_of_wave[tid / WAVE] = last;
+    // the anchor: the last entry of the history row that is not 0 (blend_rows.h)
+    int32_t last = anchor_scan<TPB>(in, g, tid, last_of_wave);
     __syncthreads();
-#pragma unroll
-    for (int v = 0; v < WAVES; ++v) last = last_of_wave[v] > last ? last_of_wave[v] : last;
+    last = anchor_max<TPB>(last, last_of_wave);
 
     // the same in every lane of the workgroup; an id, a category or a slot outside its range is never an index
     const int64_t a = last >= 0 ? load_id(in.hist, in.hist64, g * in.ld_hist + last) : 0;
@@ -177,13 +160,6 @@ __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, const int32_t* __re
     }
 }
 
-// null only where the buffer has no element
-bool bad_ptr(const void* p, uintptr_t align, int64_t n) {
-    return (p == nullptr && n > 0) || (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0;
-}
-
-bool bad_size(int64_t v) { return v < 0 || v > INT32_MAX; }
-
 bool bad_tables(int n_slots, int n_cat) {
     return n_slots < 1 || n_slots > MOBGT_CTXPRIOR_MAX_SLOTS || n_cat < 1 || n_cat > MOBGT_CTXPRIOR_MAX_CAT;
 }
@@ -231,20 +207,17 @@ extern "C" int mobgt_ctxprior_blend_rows(const float* scores, int64_t ld_scores,
                                          const void* time, const void* cat, int ctx_dtype, int64_t ld_ctx, const int32_t* poi_cat, int64_t P,
                                          const float* cat_table, const float* slot_table, int n_cat, int n_slots, const float* weights,
                                          void* stream) {
-    if (G < 0 || G > MOBGT_CTXPRIOR_MAX_G || bad_size(V) || bad_size(n_hist_cols) || P < 1 || P > INT32_MAX || bad_tables(n_slots, n_cat) ||
-        ld_scores < V || ld_out < V || ld_hist < n_hist_cols || ld_ctx < n_hist_cols || label_offset < 0 || label_offset > 1 ||
-        (out == scores && out != nullptr && ld_out != ld_scores))
+    const Rows in = {{scores, out, ld_scores, ld_out, V, label_offset, hist, ld_hist, n_hist_cols}, hist_dtype == MOBGT_CTXPRIOR_I64,
+                     time, cat, ld_ctx, ctx_dtype == MOBGT_CTXPRIOR_I64};
+    if (bad_rows_dims(in, G, MOBGT_CTXPRIOR_MAX_G) || P < 1 || P > INT32_MAX || bad_tables(n_slots, n_cat) || ld_ctx < n_hist_cols)
         return MOBGT_CTXPRIOR_EBADDIM;
-    if ((hist_dtype != MOBGT_CTXPRIOR_I32 && hist_dtype != MOBGT_CTXPRIOR_I64) || (ctx_dtype != MOBGT_CTXPRIOR_I32 && ctx_dtype != MOBGT_CTXPRIOR_I64))
-        return MOBGT_CTXPRIOR_EDTYPE;
-    const uintptr_t ctx_align = ctx_dtype == MOBGT_CTXPRIOR_I64 ? 8 : 4;
-    if (bad_ptr(scores, 4, G * V) || bad_ptr(out, 4, G * V) || bad_ptr(hist, hist_dtype == MOBGT_CTXPRIOR_I64 ? 8 : 4, G * n_hist_cols) ||
-        bad_ptr(time, ctx_align, G * n_hist_cols) || bad_ptr(cat, ctx_align, G * n_hist_cols) || bad_ptr(poi_cat, 4, P) ||
-        bad_ptr(cat_table, 4, (int64_t)n_cat * n_cat) || bad_ptr(slot_table, 4, (int64_t)n_slots * n_cat) || bad_ptr(weights, 4, 2))
+    if (bad_id_dtype(hist_dtype) || bad_id_dtype(ctx_dtype)) return MOBGT_CTXPRIOR_EDTYPE;
+    const uintptr_t ctx_align = in.ctx64 ? 8 : 4;
+    if (bad_rows_ptrs(in, in.hist64, G) || bad_ptr(time, ctx_align, G * n_hist_cols) || bad_ptr(cat, ctx_align, G * n_hist_cols) ||
+        bad_ptr(poi_cat, 4, P) || bad_ptr(cat_table, 4, (int64_t)n_cat * n_cat) || bad_ptr(slot_table, 4, (int64_t)n_slots * n_cat) ||
+        bad_ptr(weights, 4, 2))
         return MOBGT_CTXPRIOR_EALIGN;
     if (G == 0 || V == 0) return 0;
-    const Rows in = {scores, out, ld_scores, ld_out, V, label_offset, hist, ld_hist, n_hist_cols, hist_dtype == MOBGT_CTXPRIOR_I64,
-                     time, cat, ld_ctx, ctx_dtype == MOBGT_CTXPRIOR_I64};
     const dim3 grid((unsigned)((V + CHUNK - 1) / CHUNK), (unsigned)G);
     hipLaunchKernelGGL(blend_kernel, grid, dim3(TPB), 2 * sizeof(float) * (size_t)n_cat, (hipStream_t)stream, in, poi_cat, P, cat_table,
                        slot_table, n_cat, n_slots, weights);

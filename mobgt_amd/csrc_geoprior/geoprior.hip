@@ -14,7 +14,8 @@
 // 64-bit vector atomics on global memory (there are nnz entries, not P^2).  A rowptr pair and an entry of col are checked before
 // they are used as indices.
 //
-// blend_kernel -- ONE WORKGROUP PER (CHUNK OF COLUMNS, ROW): the coarse thresholds and the anchor's unit vector are staged once,
+// blend_kernel -- ONE WORKGROUP PER (CHUNK OF COLUMNS, ROW): the anchor is found as ../csrc_prior/blend_rows.h describes, the
+// coarse thresholds and the anchor's unit vector are staged once,
 // then a thread blends CHUNK / THREADS columns, each read and written by that thread only, so in place is safe.
 //
 // Built with -ffp-contract=off (Makefile): c2 is mobgt_bins.h's bit-exact expression, and a term is one product and one sum, each
@@ -25,10 +26,10 @@
 #include "mobgt_bins.h"
 #include "mobgt_geoprior.h"
 #include "../csrc_bins/bins_search.h"
+#include "../csrc_prior/blend_rows.h"
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int TPB = MOBGT_GEOPRIOR_THREADS;
 constexpr int WAVES = TPB / WAVE;
 constexpr int TILE = MOBGT_GEOPRIOR_TILE;
@@ -44,6 +45,7 @@ static_assert(TPB % WAVE == 0 && ROWS % WAVES == 0 && TILE % WAVE == 0 && CHUNK 
 static_assert((uint64_t)ROWS * MOBGT_BINS_MAX_P < (1ull << 32), "a workgroup's pairs fit a 32-bit count");
 static_assert(LDS_MAX <= 160 * 1024, "the histogram fits beside the thresholds and the tile");
 static_assert(MOBGT_BINS_MAX_THRESHOLDS + 1 > LDS_BINS, "the global form is reachable");
+static_assert(MOBGT_GEOPRIOR_I32 == ROWS_I32 && MOBGT_GEOPRIOR_I64 == ROWS_I64, "blend_rows.h's dtype codes are this header's");
 
 // counts[b] += 2 * #{(i, j), i < j, bin(i, j) = b}, + P at bin(i, i).  Dynamic LDS: COARSE thresholds, the tile, then -- IN_LDS
 // only -- nthr + 1 counts.
@@ -149,45 +151,24 @@ __global__ __launch_bounds__(TPB) void csr_hist_kernel(const double* __restrict_
     if (flag) atomicOr(status, MOBGT_GEOPRIOR_SBADINDEX);
 }
 
-struct Rows {
-    const float* scores;
-    float* out;
-    int64_t ld_scores, ld_out, V, label_offset;
-    const void* hist;
-    int64_t ld_hist, n_hist;
-    int hist64;
-};
-
-__device__ inline int64_t load_id(const void* p, int wide, int64_t i) {
-    return wide ? static_cast<const int64_t*>(p)[i] : static_cast<const int32_t*>(p)[i];
-}
+struct Rows : BlendRows { int hist64; };
 
 __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, const double* __restrict__ unit, int64_t P, const double* __restrict__ thr, int nthr,
                                                     int stride, int ncoarse, const float* __restrict__ table, const float* __restrict__ weight) {
     __shared__ double s_c[COARSE];
     __shared__ double s_a[3];
     __shared__ int32_t last_of_wave[WAVES];
-    const int tid = threadIdx.x, lane = tid % WAVE;
+    const int tid = threadIdx.x;
     const int64_t g = blockIdx.y;
     const int64_t c0 = (int64_t)blockIdx.x * CHUNK;                     // < V
     const int32_t width = (int32_t)(in.V - c0 < CHUNK ? in.V - c0 : CHUNK);
     const float w = weight[0];
 
     for (int q = tid; q < ncoarse; q += TPB) s_c[q] = thr[(int64_t)q * stride];
-    // the anchor: the last entry of the history row that is not 0
-    int32_t last = -1;
-    for (int64_t i = tid; i < in.n_hist; i += TPB) {
-        if (load_id(in.hist, in.hist64, g * in.ld_hist + i) != 0) last = (int32_t)i;
-    }
-#pragma unroll
-    for (int d = WAVE / 2; d; d /= 2) {
-        const int32_t o = __shfl_xor(last, d, WAVE);
-        last = o > last ? o : last;
-    }
-    if (lane == 0) last_of_wave[tid / WAVE] = last;
+    // the anchor: the last entry of the history row that is not 0 (blend_rows.h)
+    int32_t last = anchor_scan<TPB>(in, g, tid, last_of_wave);
     __syncthreads();
-#pragma unroll
-    for (int v = 0; v < WAVES; ++v) last = last_of_wave[v] > last ? last_of_wave[v] : last;
+    last = anchor_max<TPB>(last, last_of_wave);
 
     // the same in every lane of the workgroup; an id outside 1 .. P is never an index
     const int64_t a = last >= 0 ? load_id(in.hist, in.hist64, g * in.ld_hist + last) : 0;
@@ -209,13 +190,6 @@ __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, const double* __res
         dst[j] = s;
     }
 }
-
-// null only where the buffer has no element
-bool bad_ptr(const void* p, uintptr_t align, int64_t n) {
-    return (p == nullptr && n > 0) || (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0;
-}
-
-bool bad_size(int64_t v) { return v < 0 || v > INT32_MAX; }
 
 bool bad_bins(int64_t P, int nthr) {
     return P < 1 || P > MOBGT_BINS_MAX_P || nthr < MOBGT_BINS_MIN_THRESHOLDS || nthr > MOBGT_BINS_MAX_THRESHOLDS;
@@ -274,15 +248,12 @@ extern "C" int mobgt_geoprior_blend_rows(const float* scores, int64_t ld_scores,
                                          int64_t label_offset, const void* hist, int hist_dtype, int64_t ld_hist, int64_t n_hist_cols,
                                          const void* unit, int64_t P, const void* thresholds, int nthr, const float* table,
                                          const float* weight, void* stream) {
-    if (G < 0 || G > MOBGT_GEOPRIOR_MAX_G || bad_size(V) || bad_size(n_hist_cols) || bad_bins(P, nthr) || ld_scores < V || ld_out < V ||
-        ld_hist < n_hist_cols || label_offset < 0 || label_offset > 1 || (out == scores && out != nullptr && ld_out != ld_scores))
-        return MOBGT_GEOPRIOR_EBADDIM;
-    if (hist_dtype != MOBGT_GEOPRIOR_I32 && hist_dtype != MOBGT_GEOPRIOR_I64) return MOBGT_GEOPRIOR_EDTYPE;
-    if (bad_ptr(scores, 4, G * V) || bad_ptr(out, 4, G * V) || bad_ptr(hist, hist_dtype == MOBGT_GEOPRIOR_I64 ? 8 : 4, G * n_hist_cols) ||
-        bad_ptr(unit, 8, P * 3) || bad_ptr(thresholds, 8, nthr) || bad_ptr(table, 4, nthr + 1) || bad_ptr(weight, 4, 1))
+    const Rows in = {{scores, out, ld_scores, ld_out, V, label_offset, hist, ld_hist, n_hist_cols}, hist_dtype == MOBGT_GEOPRIOR_I64};
+    if (bad_rows_dims(in, G, MOBGT_GEOPRIOR_MAX_G) || bad_bins(P, nthr)) return MOBGT_GEOPRIOR_EBADDIM;
+    if (bad_id_dtype(hist_dtype)) return MOBGT_GEOPRIOR_EDTYPE;
+    if (bad_rows_ptrs(in, in.hist64, G) || bad_ptr(unit, 8, P * 3) || bad_ptr(thresholds, 8, nthr) || bad_ptr(table, 4, nthr + 1) || bad_ptr(weight, 4, 1))
         return MOBGT_GEOPRIOR_EALIGN;
     if (G == 0 || V == 0) return 0;
-    const Rows in = {scores, out, ld_scores, ld_out, V, label_offset, hist, ld_hist, n_hist_cols, hist_dtype == MOBGT_GEOPRIOR_I64};
     const int stride = (nthr + COARSE - 1) / COARSE, ncoarse = (nthr + stride - 1) / stride;
     const dim3 grid((unsigned)((V + CHUNK - 1) / CHUNK), (unsigned)G);
     hipLaunchKernelGGL(blend_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, in, (const double*)unit, P, (const double*)thresholds, nthr,

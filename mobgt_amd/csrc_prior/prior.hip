@@ -1,7 +1,8 @@
 // include/mobgt_prior.h: the fitted Markov tables blended into a model's scores.  The rule is the docstring of
 // mobgt_amd/prior.py; the header repeats it in short.
 //
-// ONE WORKGROUP PER (CHUNK OF COLUMNS, ROW).  Whatever a workgroup indexes with -- the anchor, its rowptr pair, the part of the
+// ONE WORKGROUP PER (CHUNK OF COLUMNS, ROW).  The anchor search is blend_rows.h's, shared with the other two priors; its one
+// barrier is also the chunk's.  Whatever a workgroup indexes with -- the anchor, its rowptr pair, the part of the
 // row inside the chunk, the (u, a) range of the keys -- is found with the same value in every lane and checked before it is used.
 // The chunk lives in LDS between its one load and its one store: the entries of the CSR row are added there, a thread an entry,
 // and a row's columns are distinct, so no two threads meet on one element.  A workgroup reads the tables and its chunk of
@@ -12,20 +13,16 @@
 #include <stdint.h>
 
 #include "mobgt_prior.h"
+#include "blend_rows.h"
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int TPB = MOBGT_PRIOR_THREADS;
 constexpr int CHUNK = MOBGT_PRIOR_CHUNK;
 static_assert(TPB % WAVE == 0 && CHUNK % TPB == 0, "a workgroup is whole waves and takes CHUNK / THREADS columns a thread");
+static_assert(MOBGT_PRIOR_I32 == ROWS_I32 && MOBGT_PRIOR_I64 == ROWS_I64, "blend_rows.h's dtype codes are this header's");
 
-struct Rows {
-    const float* scores;
-    float* out;
-    int64_t ld_scores, ld_out, V, label_offset;
-    const void* hist;
-    int64_t ld_hist, n_hist;
+struct Rows : BlendRows {
     const void* user;
     int64_t ld_user, user_offset;
     int hist64, user64;
@@ -42,10 +39,6 @@ struct Tables {
     const float* lp;
     int64_t P;
 };
-
-__device__ inline int64_t load_id(const void* p, int wide, int64_t i) {
-    return wide ? static_cast<const int64_t*>(p)[i] : static_cast<const int32_t*>(p)[i];
-}
 
 // the first i in [lo, hi) with a[i] >= x, hi if there is none; a ascending.  One lane's search.
 template <class T>
@@ -87,17 +80,8 @@ __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, Tables tb, const fl
     const int32_t width = (int32_t)(in.V - c0 < CHUNK ? in.V - c0 : CHUNK);
     const float wu = weights[0], wg = weights[1], wp = weights[2];
 
-    // the anchor: the last entry of the history row that is not 0
-    int32_t last = -1;
-    for (int64_t i = tid; i < in.n_hist; i += TPB) {
-        if (load_id(in.hist, in.hist64, g * in.ld_hist + i) != 0) last = (int32_t)i;
-    }
-#pragma unroll
-    for (int d = WAVE / 2; d; d /= 2) {
-        const int32_t o = __shfl_xor(last, d, WAVE);
-        last = o > last ? o : last;
-    }
-    if (lane == 0) last_of_wave[tid / WAVE] = last;
+    // the anchor: the last entry of the history row that is not 0 (blend_rows.h)
+    int32_t last = anchor_scan<TPB>(in, g, tid, last_of_wave);
 
     // meanwhile the chunk with the popularity term
     const float* src = in.scores + g * in.ld_scores + c0;
@@ -111,8 +95,7 @@ __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, Tables tb, const fl
         tile[j] = s;
     }
     __syncthreads();
-#pragma unroll
-    for (int w = 0; w < TPB / WAVE; ++w) last = last_of_wave[w] > last ? last_of_wave[w] : last;
+    last = anchor_max<TPB>(last, last_of_wave);
 
     // from here to the loop over the entries everything is the same in every lane of the workgroup
     int32_t e_lo = 0, e_hi = 0;
@@ -170,15 +153,6 @@ __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, Tables tb, const fl
     for (int32_t j = tid; j < width; j += TPB) dst[j] = tile[j];
 }
 
-// null only where the buffer has no element
-bool bad_ptr(const void* p, uintptr_t align, int64_t n) {
-    return (p == nullptr && n > 0) || (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0;
-}
-
-bool bad_size(int64_t v) { return v < 0 || v > INT32_MAX; }
-
-bool bad_dtype(int d) { return d != MOBGT_PRIOR_I32 && d != MOBGT_PRIOR_I64; }
-
 }  // namespace
 
 extern "C" int mobgt_prior_abi_version(void) { return MOBGT_PRIOR_ABI_VERSION; }
@@ -188,19 +162,17 @@ extern "C" int mobgt_prior_blend_rows(const float* scores, int64_t ld_scores, fl
                                       const void* user, int user_dtype, int64_t ld_user, int64_t user_offset, const void* rowptr,
                                       const void* col, const float* lg, int64_t nnz, const void* ukey, const float* lu, int64_t nnzU,
                                       int64_t U, const float* lp, int64_t P, const float* weights, void* status, void* stream) {
-    if (G < 0 || G > MOBGT_PRIOR_MAX_G || bad_size(V) || bad_size(nnz) || bad_size(nnzU) || bad_size(n_hist_cols) || P < 1 ||
-        P > INT32_MAX || U < 0 || U > INT64_MAX / (P * P) || ld_scores < V || ld_out < V || ld_hist < n_hist_cols || ld_user < 1 ||
-        label_offset < 0 || label_offset > 1 || user_offset < 0 || user_offset > 1 || (out == scores && out != nullptr && ld_out != ld_scores))
+    const Rows in = {{scores, out, ld_scores, ld_out, V, label_offset, hist, ld_hist, n_hist_cols}, user, ld_user, user_offset,
+                     hist_dtype == MOBGT_PRIOR_I64, user_dtype == MOBGT_PRIOR_I64};
+    if (bad_rows_dims(in, G, MOBGT_PRIOR_MAX_G) || bad_size(nnz) || bad_size(nnzU) || P < 1 || P > INT32_MAX || U < 0 ||
+        U > INT64_MAX / (P * P) || ld_user < 1 || user_offset < 0 || user_offset > 1)
         return MOBGT_PRIOR_EBADDIM;
-    if (bad_dtype(hist_dtype) || bad_dtype(user_dtype)) return MOBGT_PRIOR_EDTYPE;
-    if (bad_ptr(scores, 4, G * V) || bad_ptr(out, 4, G * V) || bad_ptr(hist, hist_dtype == MOBGT_PRIOR_I64 ? 8 : 4, G * n_hist_cols) ||
-        bad_ptr(user, user_dtype == MOBGT_PRIOR_I64 ? 8 : 4, G) || bad_ptr(rowptr, 8, P + 1) || bad_ptr(col, 4, nnz) ||
+    if (bad_id_dtype(hist_dtype) || bad_id_dtype(user_dtype)) return MOBGT_PRIOR_EDTYPE;
+    if (bad_rows_ptrs(in, in.hist64, G) || bad_ptr(user, in.user64 ? 8 : 4, G) || bad_ptr(rowptr, 8, P + 1) || bad_ptr(col, 4, nnz) ||
         bad_ptr(lg, 4, nnz) || bad_ptr(ukey, 8, nnzU) || bad_ptr(lu, 4, nnzU) || bad_ptr(lp, 4, P) || bad_ptr(weights, 4, 3) ||
         bad_ptr(status, 4, 1))
         return MOBGT_PRIOR_EALIGN;
     if (G == 0 || V == 0) return 0;
-    const Rows in = {scores, out, ld_scores, ld_out, V, label_offset, hist, ld_hist, n_hist_cols, user, ld_user, user_offset,
-                     hist_dtype == MOBGT_PRIOR_I64, user_dtype == MOBGT_PRIOR_I64};
     const Tables tb = {(const int64_t*)rowptr, (const int32_t*)col, lg, nnz, (const int64_t*)ukey, lu, nnzU, U, lp, P};
     const dim3 grid((unsigned)((V + CHUNK - 1) / CHUNK), (unsigned)G);
     hipLaunchKernelGGL(blend_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, in, tb, weights, (int32_t*)status);

@@ -63,7 +63,7 @@ import numpy as np
 import torch
 
 from . import _ctxprior
-from .prior import MAX_SWEEP, check_weights
+from .prior import Prior, check_weights
 
 WEIGHTS = ("category", "time")                                          # the order of a weights row
 SBADINDEX, SBADVALUE = _ctxprior.SBADINDEX, _ctxprior.SBADVALUE
@@ -148,13 +148,6 @@ def blend_host(scores, hist, time, cat, tables, weights, label_offset):
     return s
 
 
-def _refuse(bits, what):
-    if bits:
-        raise ValueError(f"{what}: the kernel skipped sessions or pairs (status {bits}): an offsets pair was descending or beyond the "
-                         "check-ins, a slot was outside [0, n_slots) or a category outside 1 .. n_cat -- which the host checks should "
-                         "have refused")
-
-
 def _rows_of(rows, G, what):
     """rows of blend -> (hist, time, cat), each [G, n] int32 / int64 with unit column stride, time and cat of one dtype and one
     row stride (a batch or any object with .x, .time, .cat, or a (hist, time, cat) triple)"""
@@ -185,20 +178,25 @@ def _rows_of(rows, G, what):
     return hist, time, cat
 
 
-class ContextPrior:
-    """The fitted tables of the module's docstring on one device, their weights and a status word.
+class ContextPrior(Prior):
+    """The fitted tables of the module's docstring on one device, their weights (category, time) and a status word (prior.Prior).
 
     P, n_cat, n_slots      the POIs and the categories, as the UniverseCounts'; the time slots
     graph_cat              gc, numpy int64 [n_cat, n_cat] (the UniverseCounts' own counts)
     slot_cat               st, numpy int64 [n_slots, n_cat]
     poi_cat                int32 [P] on the device (the UniverseCounts' own tensor: shared, not copied)
     cat_table, slot_table  Tc f32 [n_cat, n_cat], Tt f32 [n_slots, n_cat] on the device
-    weights                f32 [2] on the device: (category, time); written by set_weights only
-    status                 int32 [1] on the device: the fit's slot_hist ORs SBADINDEX / SBADVALUE into it and nothing clears it
-                           but reset_status (the loops call it when a run starts); check() reads it"""
+    status                 the fit's slot_hist ORs SBADINDEX / SBADVALUE into it; the blend flags nothing
 
-    WEIGHTS = WEIGHTS
-    n_weights = 2
+    rows of blend: a collated batch or any object with .x, .time, .cat (hist = batch.x, the raw slots batch.time, the categories
+    batch.cat), or a (hist, time, cat) triple of [G, n] (or [G, n, 1]) int32 / int64 tensors.  A (hist, user) pair as
+    MarkovPrior.blend takes it is refused: it carries neither; a stack that holds both priors is given a batch.  The launch is
+    mobgt_ctxprior_blend_rows."""
+
+    NAME, WEIGHTS, LIB = "ContextPrior", WEIGHTS, _ctxprior
+    SKIPPED = ("sessions or pairs", "an offsets pair was descending or beyond the check-ins, a slot was outside [0, n_slots) or a "
+               "category outside 1 .. n_cat -- which the host checks should have refused")
+    HINTS = ("fit the prior on the loop's device (ContextPrior.fit(..., device=...))", "the counts were not taken over the model's universe")
 
     def __init__(self, poi_cat, graph_cat, slot_cat, cat_table, slot_table, category=1.0, time=1.0, status=None):
         self.poi_cat, self.P = poi_cat, int(poi_cat.numel())
@@ -208,10 +206,7 @@ class ContextPrior:
         self._host_slot_table = np.ascontiguousarray(slot_table, dtype=np.float32)
         self.cat_table = torch.from_numpy(self._host_cat_table.copy()).to(self.device)
         self.slot_table = torch.from_numpy(self._host_slot_table.copy()).to(self.device)
-        self._host_weights = check_weights([category, time], "ContextPrior", WEIGHTS).reshape(2)
-        self.weights = torch.from_numpy(self._host_weights.copy()).to(self.device)
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.device) if status is None else status
-        self._host_tables = None
+        super().__init__([category, time], status)
 
     @property
     def device(self):
@@ -275,7 +270,7 @@ class ContextPrior:
                 _ctxprior.launch("mobgt_ctxprior_slot_hist", _p(d_seq), M, _p(d_offsets), n_sessions, _p(d_train), S, C, _p(cells),
                                  _p(word), _stream())
                 st = cells.cpu().numpy()
-        _refuse(int(word[0]), what)                                     # (before the tables: counts with skipped pairs mean nothing)
+        cls.refuse(int(word[0]), what)                                   # (before the tables: counts with skipped pairs mean nothing)
         if int(st.sum()) != int(gc.sum()):
             raise RuntimeError(f"{what}: the slot histogram holds {int(st.sum())} pairs, graph_cat {int(gc.sum())}: the counts are not "
                                "those of this ds and train")
@@ -297,110 +292,12 @@ class ContextPrior:
             raise ValueError(f"ContextPrior.lift: kind must be one of {', '.join(WEIGHTS)}, got {kind!r}")
         return (self.graph_cat, self._host_cat_table) if kind == "category" else (self.slot_cat, self._host_slot_table)
 
-    def get_weights(self):
-        """-> {"category": w, "time": w} as last set (the host's copy: no device read)."""
-        return {k: float(v) for k, v in zip(WEIGHTS, self._host_weights)}
+    _rows = staticmethod(lambda rows, G, what: tuple(zip(("hist", "time", "cat"), _rows_of(rows, G, what))))
 
-    def set_weights(self, category=None, time=None):
-        """Copy new weights into the device tensor the kernel reads (None: that weight stays).  Non-finite: ValueError, and
-        nothing is changed.  Graphs captured with this prior read the new values at their next replay."""
-        new = [old if v is None else v for v, old in zip((category, time), self._host_weights.tolist())]
-        self._host_weights = check_weights(new, "ContextPrior.set_weights", WEIGHTS).reshape(2)
-        self.weights.copy_(torch.from_numpy(self._host_weights.copy()), non_blocking=False)
-        return self
+    def _blend_host(self, scores, ids, w, label_offset):
+        return blend_host(scores, *ids, self.tables(), w, label_offset)
 
-    def reset_status(self):
-        """Zero the status word on the current stream (what a loop does when a run starts)."""
-        self.status.zero_()
-
-    def check(self, what="ContextPrior.blend"):
-        """Read the status word (one host read); not zero: ValueError.  The word is left as it is."""
-        _refuse(int(self.status[0]), what)
-
-    def blend(self, scores, rows, label_offset, out=None, weights=None):
-        """The blend of `scores` [G, V] f32 (rows of unit column stride) -> `out`; out=None: IN PLACE, and scores is returned.
-
-        rows: a collated batch or any object with .x, .time, .cat (hist = batch.x, the raw slots batch.time, the categories
-        batch.cat), or a (hist, time, cat) triple of [G, n] (or [G, n, 1]) int32 / int64 tensors.  A (hist, user) pair as
-        MarkovPrior.blend takes it is refused: it carries neither; a stack that holds both priors is given a batch.
-        label_offset: model.label_offset, 0 or 1.  out: f32 [G, >= V], scores itself or a buffer that does not overlap it; its
-        columns from V on are left alone.  weights: a device f32 [2] view read in place of the prior's own (a row of a sweep).
-
-        On the device ONE launch (mobgt_ctxprior_blend_rows) on the current stream: no allocation for a batch as the collators
-        make it, no host read.  A CPU prior answers with blend_host."""
-        what = "ContextPrior.blend"
-        if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] and scores.stride(1) != 1):
-            raise ValueError(f"{what}: scores must be f32 [G, V] with unit column stride, got {scores.dtype} {tuple(scores.shape)}")
-        G, V = scores.shape
-        out = scores if out is None else out
-        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != G or out.shape[1] < V or (out.shape[1] and out.stride(1) != 1):
-            raise ValueError(f"{what}: out must be f32 [{G}, >= {V}] with unit column stride, got {out.dtype} {tuple(out.shape)}")
-        if label_offset not in (0, 1):
-            raise ValueError(f"{what}: label_offset must be 0 or 1 (model.label_offset), got {label_offset!r}")
-        hist, time, cat = _rows_of(rows, G, what)
-        w = self.weights if weights is None else weights
-        if w.dtype != torch.float32 or w.numel() != 2 or not w.is_contiguous():
-            raise ValueError(f"{what}: weights must be a contiguous f32 [2] view, got {w.dtype} {tuple(w.shape)}")
-        for name, v in (("scores", scores), ("out", out), ("hist", hist), ("time", time), ("cat", cat), ("weights", w)):
-            if v.device != self.device:
-                raise ValueError(f"{what}: {name} is on {v.device}, the prior on {self.device}")
-        if self.device.type != "cuda":
-            res = blend_host(scores.numpy(), hist.numpy(), time.numpy(), cat.numpy(), self.tables(), w.tolist(), label_offset)
-            out[:, :V] = torch.from_numpy(res)
-            return out
-        if G > _ctxprior.MAX_G:
-            raise ValueError(f"{what}: {G} rows, one launch takes up to {_ctxprior.MAX_G}")
-        from .ops import _p, _stream
-        code = lambda v: _ctxprior.I64 if v.dtype == torch.int64 else _ctxprior.I32
-        ld = lambda v: v.stride(0) if G > 1 else max(V, v.stride(0))
-        n = hist.shape[1]
-        if out.data_ptr() == scores.data_ptr() and ld(out) != ld(scores):
-            raise ValueError(f"{what}: out starts where scores starts with another row stride: in place means out is scores")
-        with torch.cuda.device(self.device):
-            _ctxprior.launch("mobgt_ctxprior_blend_rows", _p(scores), ld(scores), _p(out), ld(out), G, V, int(label_offset),
-                             _p(hist), code(hist), max(hist.stride(0), n), n, _p(time), _p(cat), code(time), max(time.stride(0), n),
-                             _p(self.poi_cat), self.P, _p(self.cat_table), _p(self.slot_table), self.n_cat, self.n_slots, _p(w),
-                             _stream())
-        return out
-
-    def features(self, rows, label_offset, out, V=None, zeros=None):
-        """out[0, g, c] = Tc[ca - 1, k - 1] and out[1, g, c] = Tt[ta, k - 1] of the rule, 0 where it adds nothing: two blends of
-        zeros, one per weight (prior.features_by_blend).  out: f32 [2, G, >= V]; rows, label_offset as blend's."""
-        from .prior import features_by_blend
-        return features_by_blend(self, rows, label_offset, out, V, zeros)
-
-    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
-        """Fit the weights by maximum likelihood of val's targets under softmax(blend) (priorfit.fit: Newton passes of
-        train.PriorFitLoop(model, collator, val, self, **loop_kw), no grid), set them and return the priorfit.FitResult.  `val` must
-        be held out of the sessions the tables were fitted on, and is not the test split: the weights are fitted to it."""
-        from .priorfit import fit
-        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)
-
-    def tune(self, model, collator, val, grid, key="mrr", **loop_kw):
-        """prior.Stack.tune for a bare prior: evaluate every weights row of `grid` ([L, 2]: category, time) on `val` with
-        train.EvalLoop(model, collator, val, prior=self, prior_weights=..., **loop_kw), one loop per MAX_SWEEP rows, then set the
-        weights of the largest result[key] (the first of equal ones) and return the list of the L result dicts.  `val` must be
-        held out of the sessions the tables were fitted on, and is not the test split."""
-        from .train import EvalLoop
-        grid = np.asarray(grid, dtype=np.float64)
-        if grid.ndim != 2 or grid.shape[1] != 2 or grid.shape[0] < 1:
-            raise ValueError(f"ContextPrior.tune: grid must be [L >= 1, 2] rows of ({', '.join(WEIGHTS)}) weights, got shape {tuple(grid.shape)}")
-        check_weights(grid, "ContextPrior.tune", WEIGHTS)
-        results = []
-        for i in range(0, len(grid), MAX_SWEEP):
-            results += EvalLoop(model, collator, val, prior=self, prior_weights=grid[i:i + MAX_SWEEP], **loop_kw).run()
-        best = max(range(len(results)), key=lambda i: (results[i][key], -i))
-        self.set_weights(*grid[best].tolist())
-        return results
-
-    def for_loop(self, model, device, rows, what):
-        """What a loop checks once, on the host, before it captures anything with this prior."""
-        if torch.device(device) != self.device:
-            raise ValueError(f"{what}: the prior is on {self.device}, the loop on {torch.device(device)}: fit the prior on the loop's "
-                             "device (ContextPrior.fit(..., device=...))")
-        V, lo = model.out_proj.out_features, model.label_offset
-        if self.P > V - 1 + lo:
-            raise ValueError(f"{what}: the prior has POIs 1 .. {self.P}, the model scores {V} columns for POIs {lo} .. {V - 1 + lo}: "
-                             "the counts were not taken over the model's universe")
-        if rows > _ctxprior.MAX_G:
-            raise ValueError(f"{what}: batch_size {rows}, one blend launch takes up to {_ctxprior.MAX_G} rows")
+    def _launch(self, head, ids, w, _p, code, stream):
+        _, time, cat = ids
+        _ctxprior.launch("mobgt_ctxprior_blend_rows", *head, _p(time), _p(cat), code(time), max(time.stride(0), time.shape[1]),
+                         _p(self.poi_cat), self.P, _p(self.cat_table), _p(self.slot_table), self.n_cat, self.n_slots, _p(w), stream)

@@ -45,7 +45,7 @@ import torch
 
 from . import _geoprior
 from .geo import PairBins, _checked_thresholds, _chord2_rows_host, chord2_to_km
-from .prior import check_weights
+from .prior import Prior, check_weights
 
 WEIGHTS = ("distance",)                                                 # the order of a weights row
 SBADINDEX = _geoprior.SBADINDEX
@@ -137,12 +137,6 @@ def blend_host(scores, hist, tables, weight, label_offset):
     return s
 
 
-def _refuse(bits, what):
-    if bits:
-        raise ValueError(f"{what}: the kernel skipped CSR rows or entries (status {bits}): a rowptr pair was descending or beyond "
-                         "nnz, or an entry of col was outside [0, P) -- the tables are not what MarkovBaseline.fit makes")
-
-
 def _hist_of(rows, G, what):
     """rows of blend -> hist [G, n] int32 / int64 with unit column stride (a batch, a (hist, user) pair, or hist itself)"""
     hist = rows if isinstance(rows, torch.Tensor) else rows[0] if isinstance(rows, (tuple, list)) else rows.x
@@ -154,30 +148,31 @@ def _hist_of(rows, G, what):
     return hist.contiguous() if hist.shape[1] and hist.stride(1) != 1 else hist
 
 
-class DistancePrior:
-    """The fitted table of the module's docstring on one device, its weight and a status word.
+class DistancePrior(Prior):
+    """The fitted table of the module's docstring on one device, its weight (distance) and a status word (prior.Prior).  tune is
+    Prior's, as every prior's: a grid of [L, 1] rows is one weight swept.
 
     P                      the POIs, as the baseline's and the bins'
     pair_bins              the geo.PairBins it was fitted on (shared, not copied): unit, thresholds
     pair_counts            n, numpy int64 [B]
     transition_counts      t, numpy int64 [B]
     table                  f32 [B] on the device
-    weights                f32 [1] on the device: (distance,); written by set_weights only
-    status                 int32 [1] on the device: the fit's csr_hist ORs SBADINDEX into it and nothing clears it but
-                           reset_status (the loops call it when a run starts); check() reads it"""
+    status                 the fit's csr_hist ORs SBADINDEX into it; the blend flags nothing
 
-    WEIGHTS = WEIGHTS
-    n_weights = 1
+    rows of blend: a collated batch (hist = Restriction.hist(batch)), a (hist [G, n], user [G]) pair as MarkovPrior.blend takes it
+    (the users are not read), or hist alone; int32 / int64.  The launch is mobgt_geoprior_blend_rows."""
+
+    NAME, WEIGHTS, LIB = "DistancePrior", WEIGHTS, _geoprior
+    SKIPPED = ("CSR rows or entries", "a rowptr pair was descending or beyond nnz, or an entry of col was outside [0, P) -- the "
+               "tables are not what MarkovBaseline.fit makes")
+    HINTS = ("fit the baseline and the bins on the loop's device", "the baseline was not fitted on the model's universe")
 
     def __init__(self, pair_bins, pair_counts, transition_counts, table, distance=1.0, status=None):
         self.pair_bins, self.P = pair_bins, int(pair_bins.P)
         self.pair_counts, self.transition_counts = pair_counts, transition_counts
         self._host_table = np.ascontiguousarray(table, dtype=np.float32)
         self.table = torch.from_numpy(self._host_table.copy()).to(self.device)
-        self._host_weights = check_weights([distance], "DistancePrior", WEIGHTS).reshape(1)
-        self.weights = torch.from_numpy(self._host_weights.copy()).to(self.device)
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.device) if status is None else status
-        self._host_tables = None
+        super().__init__([distance], status)
 
     @property
     def device(self):
@@ -223,7 +218,7 @@ class DistancePrior:
                 _geoprior.launch("mobgt_geoprior_csr_hist", _p(unit), P, _p(thresholds), nthr, _p(rowptr), _p(col), _p(val),
                                  int(col.numel()), _p(counts[1]), _p(word), _stream())
                 n, t = counts.cpu().numpy()
-        _refuse(int(word[0]), what)                                     # (before the table: a broken CSR's counts mean nothing)
+        cls.refuse(int(word[0]), what)                                   # (before the table: a broken CSR's counts mean nothing)
         if int(n.sum()) != P * P:
             raise RuntimeError(f"{what}: the pair histogram holds {int(n.sum())} pairs, {P} POIs have {P * P}")
         return cls(pb, n, t, table_from_counts(n, t), float(weight[0]), status=word)
@@ -241,91 +236,12 @@ class DistancePrior:
         thr = self.tables().thresholds
         return np.append(chord2_to_km(thr), np.inf), self.pair_counts, self.transition_counts, self._host_table
 
-    def get_weights(self):
-        """-> {"distance": w} as last set (the host's copy: no device read)."""
-        return {k: float(v) for k, v in zip(WEIGHTS, self._host_weights)}
+    _rows = staticmethod(lambda rows, G, what: (("hist", _hist_of(rows, G, what)),))
 
-    def set_weights(self, distance=None):
-        """Copy a new weight into the device tensor the kernel reads (None: it stays).  Non-finite: ValueError, and nothing is
-        changed.  Graphs captured with this prior read the new value at their next replay."""
-        new = [self._host_weights[0] if distance is None else distance]
-        self._host_weights = check_weights(new, "DistancePrior.set_weights", WEIGHTS).reshape(1)
-        self.weights.copy_(torch.from_numpy(self._host_weights.copy()), non_blocking=False)
-        return self
+    def _blend_host(self, scores, ids, w, label_offset):
+        return blend_host(scores, ids[0], self.tables(), w, label_offset)
 
-    def reset_status(self):
-        """Zero the status word on the current stream (what a loop does when a run starts)."""
-        self.status.zero_()
-
-    def check(self, what="DistancePrior.blend"):
-        """Read the status word (one host read); not zero: ValueError.  The word is left as it is."""
-        _refuse(int(self.status[0]), what)
-
-    def blend(self, scores, rows, label_offset, out=None, weights=None):
-        """The blend of `scores` [G, V] f32 (rows of unit column stride) -> `out`; out=None: IN PLACE, and scores is returned.
-
-        rows: a collated batch (hist = Restriction.hist(batch)), a (hist [G, n], user [G]) pair as MarkovPrior.blend takes it (the
-        users are not read), or hist alone; int32 / int64.  label_offset: model.label_offset, 0 or 1.  out: f32 [G, >= V], scores
-        itself or a buffer that does not overlap it; its columns from V on are left alone.  weights: a device f32 [1] view read in
-        place of the prior's own (a row of a sweep).
-
-        On the device ONE launch (mobgt_geoprior_blend_rows) on the current stream: no allocation, no host read.  A CPU prior
-        answers with blend_host."""
-        what = "DistancePrior.blend"
-        if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] and scores.stride(1) != 1):
-            raise ValueError(f"{what}: scores must be f32 [G, V] with unit column stride, got {scores.dtype} {tuple(scores.shape)}")
-        G, V = scores.shape
-        out = scores if out is None else out
-        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != G or out.shape[1] < V or (out.shape[1] and out.stride(1) != 1):
-            raise ValueError(f"{what}: out must be f32 [{G}, >= {V}] with unit column stride, got {out.dtype} {tuple(out.shape)}")
-        if label_offset not in (0, 1):
-            raise ValueError(f"{what}: label_offset must be 0 or 1 (model.label_offset), got {label_offset!r}")
-        hist = _hist_of(rows, G, what)
-        w = self.weights if weights is None else weights
-        if w.dtype != torch.float32 or w.numel() != 1 or not w.is_contiguous():
-            raise ValueError(f"{what}: weights must be a contiguous f32 [1] view, got {w.dtype} {tuple(w.shape)}")
-        for name, v in (("scores", scores), ("out", out), ("hist", hist), ("weights", w)):
-            if v.device != self.device:
-                raise ValueError(f"{what}: {name} is on {v.device}, the prior on {self.device}")
-        if self.device.type != "cuda":
-            res = blend_host(scores.numpy(), hist.numpy(), self.tables(), w.tolist(), label_offset)
-            out[:, :V] = torch.from_numpy(res)
-            return out
-        if G > _geoprior.MAX_G:
-            raise ValueError(f"{what}: {G} rows, one launch takes up to {_geoprior.MAX_G}")
-        from .ops import _p, _stream
+    def _launch(self, head, ids, w, _p, code, stream):
         pb = self.pair_bins
-        ld = lambda v: v.stride(0) if G > 1 else max(V, v.stride(0))
-        if out.data_ptr() == scores.data_ptr() and ld(out) != ld(scores):
-            raise ValueError(f"{what}: out starts where scores starts with another row stride: in place means out is scores")
-        with torch.cuda.device(self.device):
-            _geoprior.launch("mobgt_geoprior_blend_rows", _p(scores), ld(scores), _p(out), ld(out), G, V, int(label_offset),
-                             _p(hist), _geoprior.I64 if hist.dtype == torch.int64 else _geoprior.I32,
-                             max(hist.stride(0), hist.shape[1]), hist.shape[1], _p(pb.unit), self.P, _p(pb.thresholds),
-                             int(pb.thresholds.numel()), _p(self.table), _p(w), _stream())
-        return out
-
-    def features(self, rows, label_offset, out, V=None, zeros=None):
-        """out[0, g, c] = table[bin(anchor of row g, POI of column c)], 0 where the rule adds nothing: one blend of zeros with
-        weight 1 (prior.features_by_blend).  out: f32 [1, G, >= V]; rows, label_offset as blend's."""
-        from .prior import features_by_blend
-        return features_by_blend(self, rows, label_offset, out, V, zeros)
-
-    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
-        """Fit the weight by maximum likelihood of val's targets under softmax(blend) (priorfit.fit: Newton passes of
-        train.PriorFitLoop(model, collator, val, self, **loop_kw), no grid), set it and return the priorfit.FitResult.  `val` must
-        be held out of the sessions the table was fitted on, and is not the test split: the weight is fitted to it."""
-        from .priorfit import fit
-        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)
-
-    def for_loop(self, model, device, rows, what):
-        """What a loop checks once, on the host, before it captures anything with this prior."""
-        if torch.device(device) != self.device:
-            raise ValueError(f"{what}: the prior is on {self.device}, the loop on {torch.device(device)}: fit the baseline and the "
-                             "bins on the loop's device")
-        V, lo = model.out_proj.out_features, model.label_offset
-        if self.P > V - 1 + lo:
-            raise ValueError(f"{what}: the prior has POIs 1 .. {self.P}, the model scores {V} columns for POIs {lo} .. {V - 1 + lo}: "
-                             "the baseline was not fitted on the model's universe")
-        if rows > _geoprior.MAX_G:
-            raise ValueError(f"{what}: batch_size {rows}, one blend launch takes up to {_geoprior.MAX_G} rows")
+        _geoprior.launch("mobgt_geoprior_blend_rows", *head, _p(pb.unit), self.P, _p(pb.thresholds), int(pb.thresholds.numel()),
+                         _p(self.table), _p(w), stream)

@@ -626,7 +626,7 @@ class Graphormer(nn.Module):
         adds the rows whose y is not among the trajectory's POIs (batched_data.x) to slot 1, the others to slot 2.
         near: recommend_step's radius restriction (see there); a y outside its row's radius counts in n only.
         restriction: a prebuilt restriction.Restriction in place of those four keywords (the loops build theirs once).
-        prior: a prior.MarkovPrior, a geoprior.DistancePrior or a prior.Stack of them (one launch per member, in its order); a
+        prior: any prior (a prior.Prior) or a prior.Stack of them (one launch per member, in its order); a
         MarkovPrior's weighted log-counts are added to the scores, in place, before they are ranked (one launch,
         mobgt_prior_blend_rows; the rule is prior.py's docstring): every restriction then acts on the blended scores."""
         if self.training:
@@ -667,7 +667,7 @@ class Graphormer(nn.Module):
         depend on order.
 
         restriction: a prebuilt restriction.Restriction in place of those three keywords (the loops build theirs once).
-        prior: a prior.MarkovPrior, geoprior.DistancePrior or prior.Stack blended into the scores, in place, before the lists are taken (as in metric_step); vals are the
+        prior: any prior (a prior.Prior) or a prior.Stack blended into the scores, in place, before the lists are taken (as in metric_step); vals are the
         blended scores."""
         if self.training:
             raise RuntimeError("recommend_step: the model is in training mode (call .eval() first)")
@@ -699,8 +699,8 @@ class Graphormer(nn.Module):
                  near="last", prior=None, **kw):
         """train.EvalLoop(self, collator, dataset, exclude_visited=..., candidates=..., split_revisits=..., within_km=...,
         coords=..., near=..., **kw).run(): the reference's validation / test protocol over a whole split, optionally over
-        restricted lists (within_km / coords / near as in recommend) and split by revisits.  prior: a prior.MarkovPrior, a
-        geoprior.DistancePrior or a prior.Stack blended into the scores before they are ranked.  dataset / collator as in recommend."""
+        restricted lists (within_km / coords / near as in recommend) and split by revisits.  prior: any prior (a
+        prior.Prior) or a prior.Stack blended into the scores before they are ranked.  dataset / collator as in recommend."""
         from .train import EvalLoop
         max_batches = kw.pop("max_batches", None)
         return EvalLoop(self, collator, dataset, exclude_visited=exclude_visited, candidates=candidates,

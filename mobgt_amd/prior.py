@@ -83,7 +83,7 @@ def sweep_weights(W, what="prior_weights", names=WEIGHTS):
 
 
 def features_by_blend(prior, rows, label_offset, out, V=None, zeros=None):
-    """What MarkovPrior.features and DistancePrior.features do: `prior`'s blend of a zero buffer, once per weight of its own, with
+    """What Prior.features does: `prior`'s blend of a zero buffer, once per weight of its own, with
     a unit weight row taken from a small identity kept on the prior's device -- plane k of out is then exactly the table value
     the rule adds for weight k, 0 where it adds nothing (a term with weight 0 adds +0.0).  out: f32 [n_weights, G, >= V] with
     unit column stride, its columns from V on left alone; V: the scored columns (default out.shape[2]); zeros: f32 [G, >= V]
@@ -158,25 +158,166 @@ def blend_host(scores, hist, user, prior_tables, weights, label_offset, user_off
     return s
 
 
-class MarkovPrior:
-    """The tables of the module's docstring on one device, their weights and a status word.
+class Tuned:
+    """tune and fit_weights of whatever has the priors' interface (WEIGHTS, n_weights, set_weights by name): what Prior and Stack
+    share, so a bare prior and a stack are tuned and fitted by the same code.  NAME: what the messages call the class."""
+
+    def tune(self, model, collator, val, grid, key="mrr", **loop_kw):
+        """Evaluate every weights row of `grid` ([L, n_weights], columns WEIGHTS) on `val` with train.EvalLoop(model, collator, val,
+        prior=self, prior_weights=..., **loop_kw) -- each batch is encoded once per loop, and a grid longer than MAX_SWEEP takes
+        one loop per MAX_SWEEP rows -- then set the weights of the largest result[key] (the first of equal ones) and return the
+        list of the L result dicts.  `val` must be held out of the sessions the tables were fitted on, and is not the test split:
+        the weights are fitted to it."""
+        from .train import EvalLoop
+        what, n = f"{self.NAME}.tune", self.n_weights
+        grid = np.asarray(grid, dtype=np.float64)
+        if grid.ndim != 2 or grid.shape[1] != n or grid.shape[0] < 1:
+            raise ValueError(f"{what}: grid must be [L >= 1, {n}] rows of ({', '.join(self.WEIGHTS)}) weights, got shape {tuple(grid.shape)}")
+        check_weights(grid, what, self.WEIGHTS)
+        results = []
+        for i in range(0, len(grid), MAX_SWEEP):
+            results += EvalLoop(model, collator, val, prior=self, prior_weights=grid[i:i + MAX_SWEEP], **loop_kw).run()
+        best = max(range(len(results)), key=lambda i: (results[i][key], -i))
+        self.set_weights(**dict(zip(self.WEIGHTS, grid[best].tolist())))
+        return results
+
+    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
+        """Fit all n_weights weights at once by maximum likelihood of val's targets under softmax(blend) (priorfit.fit: Newton
+        passes of train.PriorFitLoop(model, collator, val, self, **loop_kw), no grid), set them and return the priorfit.FitResult.
+        `val` must be held out of the sessions the tables were fitted on, and is not the test split: the weights are fitted to it."""
+        from .priorfit import fit
+        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)
+
+
+class Prior(Tuned):
+    """What MarkovPrior, geoprior.DistancePrior and ctxprior.ContextPrior are: tables on one device, one weight per name of WEIGHTS
+    and a status word, blended into [G, V] scores by one launch -- the interface the loops and Stack use of any prior.
+
+    weights                f32 [n_weights] on the device, in WEIGHTS' order; written by set_weights only
+    status                 int32 [1] on the device: kernels OR their S* bits into it and nothing clears it but reset_status (the
+                           loops call it when a run starts and read the word once when it ends); check() reads it
+
+    A subclass sets NAME, WEIGHTS, LIB (its ctypes module: MAX_G, I32, I64, launch), SKIPPED (what a status that is not zero
+    means: the two halves of check's message) and HINTS (how for_loop's two refusals end), has `device` and `P` and a tables()
+    that fills _host_tables, and gives blend its three own pieces: _rows, _blend_host and _launch."""
+
+    n_weights = property(lambda self: len(self.WEIGHTS))
+
+    def __init__(self, weights, status=None):
+        self._host_weights = check_weights(weights, self.NAME, self.WEIGHTS).reshape(len(self.WEIGHTS))
+        self.weights = torch.from_numpy(self._host_weights.copy()).to(self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device) if status is None else status
+        self._host_tables = None
+
+    def get_weights(self):
+        """-> {name: weight} in WEIGHTS' order, as last set (the host's copy: no device read)."""
+        return {k: float(v) for k, v in zip(self.WEIGHTS, self._host_weights)}
+
+    def set_weights(self, *in_order, **by_name):
+        """Copy new weights into the device tensor the kernel reads: positionally in WEIGHTS' order, or by name; None: that weight
+        stays.  Non-finite: ValueError, and nothing is changed.  Graphs captured with this prior read the new values at their
+        next replay."""
+        what = f"{self.NAME}.set_weights"
+        given = dict(zip(self.WEIGHTS, in_order))
+        if len(in_order) > len(self.WEIGHTS) or not set(by_name) <= set(self.WEIGHTS) or set(by_name) & set(given):
+            raise TypeError(f"{what}: the weights are ({', '.join(self.WEIGHTS)}), each given once; got {in_order!r} and {by_name!r}")
+        given.update(by_name)
+        new = [old if given.get(k) is None else given[k] for k, old in zip(self.WEIGHTS, self._host_weights.tolist())]
+        self._host_weights = check_weights(new, what, self.WEIGHTS).reshape(len(self.WEIGHTS))
+        self.weights.copy_(torch.from_numpy(self._host_weights.copy()), non_blocking=False)
+        return self
+
+    def reset_status(self):
+        """Zero the status word on the current stream (what a loop does when a run starts)."""
+        self.status.zero_()
+
+    @classmethod
+    def refuse(cls, bits, what):
+        if bits:
+            raise ValueError(f"{what}: the kernel skipped {cls.SKIPPED[0]} (status {bits}): {cls.SKIPPED[1]}")
+
+    def check(self, what=None):
+        """Read the status word (one host read); not zero: ValueError.  The word is left as it is."""
+        self.refuse(int(self.status[0]), what or f"{self.NAME}.blend")
+
+    def blend(self, scores, rows, label_offset, out=None, weights=None):
+        """The blend of `scores` [G, V] f32 (rows of unit column stride) -> `out`; out=None: IN PLACE, and scores is returned.
+
+        rows: what the subclass's _rows takes -- a collated batch, or the tensors themselves.  label_offset: model.label_offset,
+        0 or 1.  out: f32 [G, >= V], scores itself or a buffer that does not overlap it; its columns from V on are left alone.
+        weights: a device f32 [n_weights] view read in place of the prior's own (a row of a sweep).
+
+        On the device ONE launch on the current stream: no allocation for a batch as the collators make it, no host read -- what
+        the kernel flags lands in self.status (check()).  A CPU prior answers with its module's blend_host."""
+        what = f"{self.NAME}.blend"
+        if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] and scores.stride(1) != 1):
+            raise ValueError(f"{what}: scores must be f32 [G, V] with unit column stride, got {scores.dtype} {tuple(scores.shape)}")
+        G, V = scores.shape
+        out = scores if out is None else out
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != G or out.shape[1] < V or (out.shape[1] and out.stride(1) != 1):
+            raise ValueError(f"{what}: out must be f32 [{G}, >= {V}] with unit column stride, got {out.dtype} {tuple(out.shape)}")
+        if label_offset not in (0, 1):
+            raise ValueError(f"{what}: label_offset must be 0 or 1 (model.label_offset), got {label_offset!r}")
+        ids = self._rows(rows, G, what)                                 # ((name, tensor), ...), hist first
+        w = self.weights if weights is None else weights
+        if w.dtype != torch.float32 or w.numel() != self.n_weights or not w.is_contiguous():
+            raise ValueError(f"{what}: weights must be a contiguous f32 [{self.n_weights}] view, got {w.dtype} {tuple(w.shape)}")
+        for name, v in (("scores", scores), ("out", out), *ids, ("weights", w)):
+            if v.device != self.device:
+                raise ValueError(f"{what}: {name} is on {v.device}, the prior on {self.device}")
+        ids = [v for _, v in ids]
+        if self.device.type != "cuda":
+            out[:, :V] = torch.from_numpy(self._blend_host(scores.numpy(), [v.numpy() for v in ids], w.tolist(), label_offset))
+            return out
+        if G > self.LIB.MAX_G:
+            raise ValueError(f"{what}: {G} rows, one launch takes up to {self.LIB.MAX_G}")
+        from .ops import _p, _stream
+        ld = lambda v: v.stride(0) if G > 1 else max(V, v.stride(0))
+        if out.data_ptr() == scores.data_ptr() and ld(out) != ld(scores):
+            raise ValueError(f"{what}: out starts where scores starts with another row stride: in place means out is scores")
+        code = lambda v: self.LIB.I64 if v.dtype == torch.int64 else self.LIB.I32
+        hist, n = ids[0], ids[0].shape[1]
+        with torch.cuda.device(self.device):                            # (what every *_blend_rows begins with, then the subclass's own)
+            self._launch((_p(scores), ld(scores), _p(out), ld(out), G, V, int(label_offset), _p(hist), code(hist), max(hist.stride(0), n), n),
+                         ids, w, _p, code, _stream())
+        return out
+
+    def for_loop(self, model, device, rows, what):
+        """What a loop checks once, on the host, before it captures anything with this prior."""
+        if torch.device(device) != self.device:
+            raise ValueError(f"{what}: the prior is on {self.device}, the loop on {torch.device(device)}: {self.HINTS[0]}")
+        V, lo = model.out_proj.out_features, model.label_offset
+        if self.P > V - 1 + lo:
+            raise ValueError(f"{what}: the prior has POIs 1 .. {self.P}, the model scores {V} columns for POIs {lo} .. {V - 1 + lo}: "
+                             f"{self.HINTS[1]}")
+        if rows > self.LIB.MAX_G:
+            raise ValueError(f"{what}: batch_size {rows}, one blend launch takes up to {self.LIB.MAX_G} rows")
+
+    def features(self, rows, label_offset, out, V=None, zeros=None):
+        """out[k, g, c] = what the rule adds to scores[g, c] per unit of weight k (WEIGHTS' order; 0 where it adds nothing): one
+        blend of zeros per weight (features_by_blend).  out: f32 [n_weights, G, >= V]; rows, label_offset as blend's."""
+        return features_by_blend(self, rows, label_offset, out, V, zeros)
+
+
+class MarkovPrior(Prior):
+    """The tables of the module's docstring on one device, their weights (user, transition, popularity) and a status word (Prior).
 
     P, U                   as the baseline's
     rowptr, col, ukey      the baseline's own tensors (shared, not copied)
     lg, lu, lp             f32 [nnz], [nnzU], [P]
-    weights                f32 [3] on the device: (user, transition, popularity); written by set_weights only
-    status                 int32 [1] on the device: the kernel ORs SBADINDEX into it and never clears it.  The loops zero it when
-                           a run starts and read it once when it ends; after blend() calls of your own, check() reads it."""
 
-    WEIGHTS = WEIGHTS                                                   # (what the loops ask of any prior: the names of a weights row,
-    n_weights = 3                                                       #  and their number)
+    rows of blend: a collated batch (hist = Restriction.hist(batch), user = batch.user) or a (hist [G, n], user [G]) pair of
+    int32 / int64 tensors.  The launch is mobgt_prior_blend_rows; it ORs SBADINDEX into status, and so does a CPU prior's blend."""
+
+    NAME, WEIGHTS, LIB = "MarkovPrior", WEIGHTS, _prior
+    SKIPPED = ("table rows or entries", "a rowptr pair was descending or beyond nnz, or an entry of col was outside [0, P) -- the "
+               "tables are not what MarkovBaseline.fit makes")
+    HINTS = ("fit the baseline on the loop's device (MarkovBaseline.fit(..., device=...))",
+             "the baseline was not fitted on the model's universe")
 
     def __init__(self, P, U, rowptr, col, lg, ukey, lu, lp, weights):
         self.P, self.U, self.rowptr, self.col, self.lg, self.ukey, self.lu, self.lp = int(P), int(U), rowptr, col, lg, ukey, lu, lp
-        self._host_weights = check_weights(weights, "MarkovPrior").reshape(3)
-        self.weights = torch.from_numpy(self._host_weights.copy()).to(self.device)
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._host_tables = None
+        super().__init__(weights)
 
     @property
     def device(self):
@@ -199,31 +340,8 @@ class MarkovPrior:
             self._host_tables = PriorTables(n(self.rowptr), n(self.col), n(self.lg), n(self.ukey), n(self.lu), n(self.lp), self.U, self.P)
         return self._host_tables
 
-    def get_weights(self):
-        """-> {"user": wu, "transition": wg, "popularity": wp} as last set (the host's copy: no device read)."""
-        return {k: float(v) for k, v in zip(WEIGHTS, self._host_weights)}
-
-    def set_weights(self, user=None, transition=None, popularity=None):
-        """Copy new weights into the device tensor the kernel reads (None: that weight stays).  Non-finite: ValueError, and
-        nothing is changed.  Graphs captured with this prior read the new values at their next replay."""
-        new = [old if v is None else v for v, old in zip((user, transition, popularity), self._host_weights.tolist())]
-        self._host_weights = check_weights(new, "MarkovPrior.set_weights")
-        self.weights.copy_(torch.from_numpy(self._host_weights.copy()), non_blocking=False)
-        return self
-
-    def reset_status(self):
-        """Zero the status word on the current stream (what a loop does when a run starts)."""
-        self.status.zero_()
-
-    def check(self, what="MarkovPrior.blend"):
-        """Read the status word (one host read); not zero: ValueError.  The word is left as it is."""
-        bits = int(self.status[0])
-        if bits:
-            raise ValueError(f"{what}: the kernel skipped table rows or entries (status {bits}): a rowptr pair was descending or beyond "
-                             "nnz, or an entry of col was outside [0, P) -- the tables are not what MarkovBaseline.fit makes")
-
     @staticmethod
-    def _ids(rows, G, what):
+    def _rows(rows, G, what):
         hist, user = rows if isinstance(rows, (tuple, list)) else (rows.x.reshape(rows.x.shape[0], -1), rows.user)
         hist, user = hist.reshape(hist.shape[0], -1), user.reshape(-1)
         if hist.shape[0] != G or user.shape[0] != G:
@@ -233,106 +351,35 @@ class MarkovPrior:
                 raise TypeError(f"{what}: {name} must be int32 or int64 ids, got {v.dtype}")
         if hist.shape[1] and hist.stride(1) != 1:
             hist = hist.contiguous()
-        return hist, user
+        return ("hist", hist), ("user", user)
 
-    def blend(self, scores, rows, label_offset, out=None, weights=None):
-        """The blend of `scores` [G, V] f32 (rows of unit column stride) -> `out`; out=None: IN PLACE, and scores is returned.
+    def _blend_host(self, scores, ids, w, label_offset):
+        status = [0]
+        res = blend_host(scores, *ids, self.tables(), w, label_offset, status=status)
+        self.status |= status[0]
+        return res
 
-        rows: a collated batch (hist = Restriction.hist(batch), user = batch.user) or a (hist [G, n], user [G]) pair of int32 /
-        int64 tensors.  label_offset: model.label_offset, 0 or 1.  out: f32 [G, >= V] that does not overlap scores; its columns
-        from V on are left alone.  weights: a device f32 [3] view read in place of the prior's own (a row of a sweep).
-
-        On the device ONE launch (mobgt_prior_blend_rows) on the current stream: no allocation, no host read -- SBADINDEX lands
-        in self.status (check()).  A CPU prior answers with blend_host and ORs the bit into self.status."""
-        what = "MarkovPrior.blend"
-        if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] and scores.stride(1) != 1):
-            raise ValueError(f"{what}: scores must be f32 [G, V] with unit column stride, got {scores.dtype} {tuple(scores.shape)}")
-        G, V = scores.shape
-        out = scores if out is None else out
-        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != G or out.shape[1] < V or (out.shape[1] and out.stride(1) != 1):
-            raise ValueError(f"{what}: out must be f32 [{G}, >= {V}] with unit column stride, got {out.dtype} {tuple(out.shape)}")
-        if label_offset not in (0, 1):
-            raise ValueError(f"{what}: label_offset must be 0 or 1 (model.label_offset), got {label_offset!r}")
-        hist, user = self._ids(rows, G, what)
-        w = self.weights if weights is None else weights
-        if w.dtype != torch.float32 or w.numel() != 3 or not w.is_contiguous():
-            raise ValueError(f"{what}: weights must be a contiguous f32 [3] view, got {w.dtype} {tuple(w.shape)}")
-        for name, v in (("scores", scores), ("out", out), ("hist", hist), ("user", user), ("weights", w)):
-            if v.device != self.device:
-                raise ValueError(f"{what}: {name} is on {v.device}, the prior on {self.device}")
-        if self.device.type != "cuda":
-            status = [0]
-            res = blend_host(scores.numpy(), hist.numpy(), user.numpy(), self.tables(), w.tolist(), label_offset, status=status)
-            out[:, :V] = torch.from_numpy(res)
-            self.status |= status[0]
-            return out
-        if G > _prior.MAX_G:
-            raise ValueError(f"{what}: {G} rows, one launch takes up to {_prior.MAX_G}")
-        from .ops import _p, _stream
-        code = lambda v: _prior.I64 if v.dtype == torch.int64 else _prior.I32
-        with torch.cuda.device(self.device):
-            _prior.launch("mobgt_prior_blend_rows", _p(scores), scores.stride(0) if G > 1 else max(V, scores.stride(0)), _p(out),
-                          out.stride(0) if G > 1 else max(V, out.stride(0)), G, V, int(label_offset),
-                          _p(hist), code(hist), max(hist.stride(0), hist.shape[1]), hist.shape[1],
-                          _p(user), code(user), max(user.stride(0), 1), 1,
-                          _p(self.rowptr), _p(self.col), _p(self.lg), int(self.col.numel()),
-                          _p(self.ukey), _p(self.lu), int(self.ukey.numel()), self.U, _p(self.lp), self.P, _p(w), _p(self.status),
-                          _stream())
-        return out
-
-    def for_loop(self, model, device, rows, what):
-        """What a loop checks once, on the host, before it captures anything with this prior."""
-        if torch.device(device) != self.device:
-            raise ValueError(f"{what}: the prior is on {self.device}, the loop on {torch.device(device)}: fit the baseline on the "
-                             "loop's device (MarkovBaseline.fit(..., device=...))")
-        V, lo = model.out_proj.out_features, model.label_offset
-        if self.P > V - 1 + lo:
-            raise ValueError(f"{what}: the prior has POIs 1 .. {self.P}, the model scores {V} columns for POIs {lo} .. {V - 1 + lo}: "
-                             "the baseline was not fitted on the model's universe")
-        if rows > _prior.MAX_G:
-            raise ValueError(f"{what}: batch_size {rows}, one blend launch takes up to {_prior.MAX_G} rows")
-
-    def tune(self, model, collator, val, grid, key="mrr", **loop_kw):
-        """Evaluate every weights row of `grid` ([L, 3]: user, transition, popularity) on `val` with train.EvalLoop(model, collator,
-        val, prior=self, prior_weights=..., **loop_kw) -- each batch is encoded once per loop, and a grid longer than MAX_SWEEP
-        takes one loop per MAX_SWEEP rows -- then set the weights of the largest result[key] (the first of equal ones) and return
-        the list of the L result dicts.  `val` must be held out of the sessions the baseline was fitted on, and is not the test
-        split: the weights are fitted to it."""
-        from .train import EvalLoop
-        grid = np.asarray(grid, dtype=np.float64)
-        if grid.ndim != 2 or grid.shape[1] != 3 or grid.shape[0] < 1:
-            raise ValueError(f"MarkovPrior.tune: grid must be [L >= 1, 3] rows of ({', '.join(WEIGHTS)}) weights, got shape {tuple(grid.shape)}")
-        check_weights(grid, "MarkovPrior.tune")
-        results = []
-        for i in range(0, len(grid), MAX_SWEEP):
-            results += EvalLoop(model, collator, val, prior=self, prior_weights=grid[i:i + MAX_SWEEP], **loop_kw).run()
-        best = max(range(len(results)), key=lambda i: (results[i][key], -i))
-        self.set_weights(*grid[best].tolist())
-        return results
-
-    def features(self, rows, label_offset, out, V=None, zeros=None):
-        """out[k, g, c] = what the rule adds to scores[g, c] per unit of weight k (user, transition, popularity; 0 where it adds
-        nothing): three blends of zeros, one per weight (features_by_blend).  out: f32 [3, G, >= V]; rows, label_offset as blend's."""
-        return features_by_blend(self, rows, label_offset, out, V, zeros)
-
-    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
-        """Fit the weights by maximum likelihood of val's targets under softmax(blend) (priorfit.fit: Newton passes of
-        train.PriorFitLoop(model, collator, val, self, **loop_kw), no grid), set them and return the priorfit.FitResult.  `val` must
-        be held out of the sessions the baseline was fitted on, and is not the test split: the weights are fitted to it."""
-        from .priorfit import fit
-        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)
+    def _launch(self, head, ids, w, _p, code, stream):
+        user = ids[1]
+        _prior.launch("mobgt_prior_blend_rows", *head, _p(user), code(user), max(user.stride(0), 1), 1,
+                      _p(self.rowptr), _p(self.col), _p(self.lg), int(self.col.numel()),
+                      _p(self.ukey), _p(self.lu), int(self.ukey.numel()), self.U, _p(self.lp), self.P, _p(w), _p(self.status), stream)
 
 
-class Stack:
+class Stack(Tuned):
     """One or more priors blended in the order given, behind the interface the loops use of any prior (EvalLoop / PredictLoop,
     Graphormer.metric_step / recommend_step): prior.Stack(mb.prior(), mb.distance_prior(pair_bins)).
 
-    priors      the members, a tuple: MarkovPrior, geoprior.DistancePrior, or anything with their interface
+    priors      the members, a tuple: any Prior (MarkovPrior, geoprior.DistancePrior, ctxprior.ContextPrior), or anything with their
+                interface
     WEIGHTS     the members' names concatenated, e.g. ("user", "transition", "popularity", "distance"); no name twice
     n_weights   len(WEIGHTS): the width of a weights row (blend(weights=), EvalLoop(prior_weights=), tune's grid)
 
     Each member keeps its own device weights and status word; a blend is one launch per member: the first writes `out`, the rest
-    run in place on it, so the result is the members' rules applied in turn, bit for bit."""
+    run in place on it, so the result is the members' rules applied in turn, bit for bit.  tune and fit_weights are the bare
+    priors' own (Tuned); a Stack is no Prior, because it has no weights tensor of its own."""
+
+    NAME = "prior.Stack"
 
     def __init__(self, *priors):
         if not priors:
@@ -408,25 +455,6 @@ class Stack:
                 p.set_weights(**mine)
         return self
 
-    def tune(self, model, collator, val, grid, key="mrr", **loop_kw):
-        """MarkovPrior.tune for the stack: evaluate every weights row of `grid` ([L, n_weights], columns WEIGHTS) on `val` with
-        train.EvalLoop(model, collator, val, prior=self, prior_weights=..., **loop_kw) -- each batch encoded once per loop, one
-        loop per MAX_SWEEP rows -- then set the weights of the largest result[key] (the first of equal ones) and return the
-        list of the L result dicts.  `val` must be held out of the sessions the members were fitted on, and is not the test
-        split."""
-        from .train import EvalLoop
-        grid = np.asarray(grid, dtype=np.float64)
-        if grid.ndim != 2 or grid.shape[1] != self.n_weights or grid.shape[0] < 1:
-            raise ValueError(f"prior.Stack.tune: grid must be [L >= 1, {self.n_weights}] rows of ({', '.join(self.WEIGHTS)}) weights, "
-                             f"got shape {tuple(grid.shape)}")
-        check_weights(grid, "prior.Stack.tune", self.WEIGHTS)
-        results = []
-        for i in range(0, len(grid), MAX_SWEEP):
-            results += EvalLoop(model, collator, val, prior=self, prior_weights=grid[i:i + MAX_SWEEP], **loop_kw).run()
-        best = max(range(len(results)), key=lambda i: (results[i][key], -i))
-        self.set_weights(**dict(zip(self.WEIGHTS, grid[best].tolist())))
-        return results
-
     def features(self, rows, label_offset, out, V=None, zeros=None):
         """The members' features in WEIGHTS' order: member i fills its n_weights planes of out, f32 [n_weights, G, >= V]."""
         if not isinstance(out, torch.Tensor) or out.dim() != 3 or out.shape[0] != self.n_weights:
@@ -437,10 +465,3 @@ class Stack:
             p.features(rows, label_offset, out[at:at + p.n_weights], V, zeros)
             at += p.n_weights
         return out
-
-    def fit_weights(self, model, collator, val, l2=1e-3, tol=1e-7, max_passes=12, scale_model=True, **loop_kw):
-        """MarkovPrior.fit_weights for the stack: all n_weights weights at once, by maximum likelihood (priorfit.fit), set and
-        returned as a priorfit.FitResult.  `val` must be held out of the sessions the members were fitted on, and is not the test
-        split: the weights are fitted to it."""
-        from .priorfit import fit
-        return fit(self, model, collator, val, l2=l2, tol=tol, max_passes=max_passes, scale_model=scale_model, **loop_kw)

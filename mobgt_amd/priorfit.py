@@ -1,4 +1,4 @@
-"""The weights of the priors (prior.MarkovPrior, geoprior.DistancePrior, prior.Stack) fitted by maximum likelihood on held-out
+"""The weights of the priors (any prior.Prior, or a prior.Stack) fitted by maximum likelihood on held-out
 samples, instead of a grid the caller has to invent (prior.tune).  Every prior is exactly linear in its weights,
 blend(s, w) = s + sum_k w_k F_k with F_k the table value its rule adds (0 where the rule adds nothing), so the log-likelihood of
 the targets under softmax(blend) is concave in w: its gradient is E_p[F] - F[y], its Hessian Cov_p[F], and a handful of Newton

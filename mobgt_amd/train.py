@@ -1568,7 +1568,7 @@ class PredictLoop(_FrozenModelLoop):
     within r of any POI of the trajectory).  The rows' candidate words are built inside the captured graph (ops.near_words) from
     positions packed once here, and combine with exclude_visited and candidates.
 
-    prior: a prior.MarkovPrior, a geoprior.DistancePrior or a prior.Stack on the loop's device, blended into the scores inside the captured graph before the lists are
+    prior: any prior (a prior.Prior) or a prior.Stack on the loop's device, blended into the scores inside the captured graph before the lists are
     taken, as in EvalLoop (vals are the blended scores; the anchor caveat of near="last" holds).  run() zeroes the prior's status
     word when it starts and reads it after the pass -- the loop's one host read, made only with a prior; not zero: ValueError."""
 
@@ -1649,7 +1649,7 @@ class PriorFitLoop(_FrozenModelLoop):
 
     -- eager with use_graph=False and for collators whose finish needs torch ops, as in the other loops.
 
-    prior: a prior.MarkovPrior, a geoprior.DistancePrior or a prior.Stack on the loop's device.  scale_model: the model's scores are
+    prior: any prior (a prior.Prior) or a prior.Stack on the loop's device.  scale_model: the model's scores are
     feature 0 and scaled by a weight of their own, K = 1 + prior.n_weights; else they are the base and K = prior.n_weights.
     weights: the first weight rows, [L, K] (default: one row, `start` -- the prior's current weights, after a 1 for the model's
     scale).  rows: how many weight rows every launch evaluates (default 4: a Newton pass's step lengths); the graphs always

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import anchor_cases as ac
 import ctxprior_cases as cc
 import geoprior_cases as gc
 import prior_cases as pc
@@ -237,6 +238,28 @@ def test_blend_equals_the_host_rule(V, G, label_offset, form):
         assert (bits(want) == 0xFFC12345).any() and (bits(want) == 0x80000000).any() and np.isinf(want).any()
 
 
+@pytest.mark.parametrize("wide", (False, True), ids=("i32", "i64"))
+@pytest.mark.parametrize("n", ac.WIDTHS)
+def test_the_anchor_search_across_waves_and_strides(n, wide):
+    """The history rows of anchor_cases, n ids wide, by direct call: the only id in the first and in the last position, and two
+    ids whose positions lie in different waves and strides, the later one deciding.  Slot and category are read AT the anchor
+    position: every position carries another valid (slot, category) -- 13 * 48 >= 600 of them -- so a wrong winner shows in
+    the output."""
+    t = tables(C=13)
+    d = _direct(t, ac.G, ac.V, ac.LABEL_OFFSET, wide=wide, seed=n)
+    scores = d["host"][0]
+    dtype = np.int64 if wide else np.int32
+    hist = ac.rows(n, 3, 17, dtype)
+    at = np.tile(np.arange(n, dtype=dtype), (ac.G, 1))
+    time, cat = at % t.n_slots, 1 + at // t.n_slots
+    assert n == 0 or (cat.max() <= t.n_cat and len(set(zip(time[0].tolist(), cat[0].tolist()))) == n)
+    assert _call(d, hist=up(hist), n_hist_cols=n, ld_hist=n, time=up(time), cat=up(cat), ld_ctx=n) == 0
+    d["host"] = (scores, hist, time, cat)
+    want = _assert_blended(d, t)
+    if n > 1:
+        assert (bits(want[3]) != bits(ctxprior.blend_host(scores, ac.loser(hist), time, cat, t, WEIGHTS, ac.LABEL_OFFSET)[3])).any()
+
+
 def test_blend_of_no_rows_launches_nothing():
     t = tables()
     d = _direct(t, 0, 40)
@@ -358,6 +381,21 @@ def test_fit_on_the_device_is_the_host_fit(world):
         data.ContextPrior.fit(ds, train, counts=counts, device="cpu")
     with pytest.raises(TypeError, match="a PrefixDataset holds every transition of a session once per prefix"):
         data.ContextPrior.fit(world["samples"], train, device=DEV)
+
+
+def test_every_prior_refuses_out_at_scores_with_another_row_stride(world):
+    """In place means out IS scores: an `out` that starts where scores starts with another row stride is refused by all three
+    priors alike, on the host, before a launch (the entry points' own EBADDIM is pinned by their return-code tests)."""
+    buf = torch.zeros(2, 8, device=DEV)
+    scores, out = buf[:, :3], torch.as_strided(buf, (2, 3), (4, 1))
+    ids = torch.tensor([[4, 9, 0], [7, 0, 0]], dtype=torch.int32, device=DEV)
+    batch = types.SimpleNamespace(x=ids, user=torch.ones(2, dtype=torch.int32, device=DEV), time=ids, cat=ids)
+    for p in (world["mb"].prior(), world["mb"].distance_prior(world["pb"]), world["cp"]):
+        with pytest.raises(ValueError, match=f"{type(p).__name__}.blend: .*in place means out is scores"):
+            p.blend(scores, batch, 1, out=out)
+        p.check()
+    torch.cuda.synchronize()
+    assert not buf.any()
 
 
 def test_the_public_blend_and_a_captured_graph(world):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import anchor_cases as ac
 import geoprior_cases as gc
 import prior_cases as pc
 from mobgt_amd import _geoprior, _lib_bins, data, geo, geoprior, metrics, ops, prior, workloads
@@ -230,6 +231,23 @@ def test_blend_equals_the_host_rule(V, G, label_offset, form):
             assert changed[[g for g in range(G) if g not in none]].mean(axis=1).min() > 0.3
     if G == 16 and V > CHUNK:
         assert (bits(want) == 0xFFC12345).any() and (bits(want) == 0x80000000).any() and np.isinf(want).any()
+
+
+@pytest.mark.parametrize("wide", (False, True), ids=("i32", "i64"))
+@pytest.mark.parametrize("n", ac.WIDTHS)
+def test_the_anchor_search_across_waves_and_strides(n, wide):
+    """The history rows of anchor_cases, n ids wide, by direct call: the only id in the first and in the last position, and two
+    ids whose positions lie in different waves and strides, the later one deciding -- two anchors lie at different distances, so
+    a wrong winner shows in the output."""
+    t = tables()
+    d = _direct(t, ac.G, ac.V, ac.LABEL_OFFSET, wide=wide, seed=n)
+    scores = d["host"][0]
+    hist = ac.rows(n, 3, 17, np.int64 if wide else np.int32)
+    assert _call(d, hist=up(hist), n_hist_cols=n, ld_hist=n) == 0
+    d["host"] = (scores, hist)
+    want = _assert_blended(d, t)
+    if n > 1:
+        assert (bits(want[3]) != bits(geoprior.blend_host(scores, ac.loser(hist), t, 0.75, ac.LABEL_OFFSET)[3])).any()
 
 
 def test_blend_of_no_rows_launches_nothing():

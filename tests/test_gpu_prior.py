@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import anchor_cases as ac
 import checkins_cases as cc
 import prior_cases as pc
 from mobgt_amd import _prior, data, metrics, prior, workloads
@@ -146,6 +147,23 @@ def test_the_weights_are_read_on_the_device_in_their_order():
         d = _direct(t, 16, CHUNK + 1, weights=w, seed=9)
         assert _call(d) == 0
         _assert_blended(d, t, weights=w)
+
+
+@pytest.mark.parametrize("wide", (False, True), ids=("i32", "i64"))
+@pytest.mark.parametrize("n", ac.WIDTHS)
+def test_the_anchor_search_across_waves_and_strides(n, wide):
+    """The history rows of anchor_cases, n ids wide, by direct call: the only id in the first and in the last position, and two
+    ids whose positions lie in different waves and strides, the later one deciding -- the rows of two anchors differ, so a wrong
+    winner shows in the output."""
+    t = tables(P=40)
+    d = _direct(t, ac.G, ac.V, ac.LABEL_OFFSET, wide=wide, seed=n)
+    scores, _, user = d["host"]
+    hist = ac.rows(n, 3, 17, np.int64 if wide else np.int32)
+    assert _call(d, hist=torch.from_numpy(hist).to(DEV), n_hist_cols=n, ld_hist=n) == 0
+    d["host"] = (scores, hist, user)
+    want = _assert_blended(d, t)
+    if n > 1:
+        assert (bits(want[3]) != bits(prior.blend_host(scores, ac.loser(hist), user, t, WEIGHTS, ac.LABEL_OFFSET)[3])).any()
 
 
 # ------------------------------------------------------------------------------------------------ the entry point itself

@@ -40,10 +40,10 @@ def _header(root, version=1, extra=""):
     _write(os.path.join(root, "include", "mobgt_toy.h"), HEADER % (version, extra))
 
 
-def _toy(root):
+def _toy(root, **kw):
     return _native.Library(os.path.join(root, "include", "mobgt_toy.h"), os.path.join(root, "csrc_toy"), os.path.join(root, "libmobgt_toy.so"),
                            "MOBGT_TOY_", missing="it is only a toy.", error=ToyError, hip=False,
-                           errors={"EBADDIM": "a bad size", "EALIGN": "a bad pointer"})
+                           errors={"EBADDIM": "a bad size", "EALIGN": "a bad pointer"}, **kw)
 
 
 @pytest.fixture
@@ -85,6 +85,41 @@ def test_build_only_when_stale(root):
         assert os.path.getmtime(toy.path) > 1_000_000_001, stale              # an input is newer -> rebuilt (now)
         os.utime(stale, (999_999_999, 999_999_999))
         os.utime(toy.path, (1_000_000_000, 1_000_000_000))
+
+
+def test_extra_inputs_count_as_the_sources_do(root):
+    """A header outside the source directory that the Makefile names: declared as an extra input it makes the library stale when
+    it is newer, and only then; not declared, build() does not see it (what left libmobgt_geoprior.so stale after an edit of
+    csrc_bins/bins_search.h)."""
+    shared = os.path.join(root, "csrc_other", "shared.h")
+    _write(shared, "/* included by toy.c's neighbours */\n")
+    _write(os.path.join(root, "csrc_toy", "Makefile"), MAKEFILE.replace(" Makefile\n", " Makefile ../csrc_other/shared.h\n"))
+    toy, blind = _toy(root, extra_inputs=(shared,)), _toy(root)
+    assert toy.extra_inputs == (shared,) and blind.extra_inputs == ()
+    toy.build()
+    os.utime(toy.path, (1_000_000_000, 1_000_000_000))
+    for name in [os.path.join(toy.csrc, f) for f in os.listdir(toy.csrc)] + [toy.header, shared]:
+        os.utime(name, (999_999_999, 999_999_999))
+    toy.build()
+    assert os.path.getmtime(toy.path) == 1_000_000_000                        # the extra input is older -> left alone
+    os.utime(shared, (1_000_000_001, 1_000_000_001))
+    blind.build()
+    assert os.path.getmtime(toy.path) == 1_000_000_000                        # newer, but not declared -> nothing happens
+    toy.build()
+    assert os.path.getmtime(toy.path) > 1_000_000_001                         # newer and declared -> rebuilt (now)
+
+
+def test_the_shipped_libraries_declare_the_headers_they_share():
+    """Without building: a path relative to the package, as the bindings write them, names an existing file."""
+    from mobgt_amd import _ctxprior, _geoprior, _pairbins, _prior
+    pkg = os.path.join(ROOT, "mobgt_amd")
+    blend_rows, bins_search = os.path.join(pkg, "csrc_prior", "blend_rows.h"), os.path.join(pkg, "csrc_bins", "bins_search.h")
+    bins_header = os.path.join(ROOT, "include", "mobgt_bins.h")
+    for module, want in ((_prior, [blend_rows]), (_ctxprior, [blend_rows]), (_geoprior, [blend_rows, bins_search, bins_header]),
+                         (_pairbins, [bins_search, bins_header])):
+        have = [os.path.normpath(f) for f in module.LIBRARY.extra_inputs]
+        assert have == want and all(os.path.isfile(f) for f in have), module.__name__
+    assert all(library.extra_inputs == () for library in _native.LIBRARIES)   # the five declare none: they include nothing shared
 
 
 def test_stale_abi_version_is_refused(root):
