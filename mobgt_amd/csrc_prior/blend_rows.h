@@ -1,5 +1,6 @@
-// What the three blend_rows kernels share (prior.hip, ../csrc_geoprior/geoprior.hip, ../csrc_ctxprior/ctxprior.hip): the leading
-// fields of their row arguments, the anchor search, and the argument checks of mobgt_*_blend_rows that all three make.
+// What the blend_rows kernels share (prior.hip, ../csrc_geoprior/geoprior.hip, ../csrc_ctxprior/ctxprior.hip,
+// ../csrc_visitprior/visitprior.hip): the leading fields of their row arguments, the anchor search of the three that have an
+// anchor, the wave's search in a CSR row, and the argument checks of mobgt_*_blend_rows that all of them make.
 //
 // THE ANCHOR SEARCH.  The anchor position of row g is the LAST i in [0, n_hist) with hist[g, i] != 0, -1 if there is none.  A
 // workgroup of TPB threads finds it in two phases around ONE barrier, which is the caller's:
@@ -55,6 +56,24 @@ __device__ __forceinline__ int32_t anchor_max(int32_t last, const int32_t* last_
 #pragma unroll
     for (int w = 0; w < TPB / WAVE; ++w) last = last_of_wave[w] > last ? last_of_wave[w] : last;
     return last;
+}
+
+// THE SEARCH IN A CSR ROW (prior.hip, ../csrc_visitprior/visitprior.hip).  The first i in [lo, hi) with a[i] >= x, hi if there is
+// none; a ascending.  By a whole wave: a step probes 64 places of [lo, hi), a lane a place, and keeps the gap between the last
+// probe below x and the one after it, so 2^31 elements take six dependent loads where a lane's own bisection takes 31.  Every lane
+// of the wave must call it with the same arguments; the result is the same in every lane, and lies in [lo, hi] whatever `a` holds.
+template <class T>
+__device__ inline int32_t wave_lower(const T* __restrict__ a, int32_t lo, int32_t hi, T x, int lane) {
+    while (lo < hi) {
+        const int64_t step = ((int64_t)hi - lo + WAVE - 1) / WAVE;
+        const int64_t at = lo + lane * step;
+        const int below = __popcll(__ballot(at < hi && a[at] < x));    // (ascending: the probes below x are the first `below`)
+        if (below == 0) return lo;
+        const int64_t last = lo + (below - 1) * step;                   // < hi: that probe was made
+        lo = (int32_t)(last + 1);
+        hi = (int32_t)(last + step < hi ? last + step : hi);
+    }
+    return lo;
 }
 
 // null only where the buffer has no element

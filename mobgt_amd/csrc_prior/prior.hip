@@ -54,22 +54,7 @@ __device__ inline int32_t lower(const T* __restrict__ a, int32_t lo, int32_t hi,
     return lo;
 }
 
-// The same, by a whole wave: a step probes 64 places of [lo, hi), a lane a place, and keeps the gap between the last probe
-// below x and the one after it, so 2^31 elements take six dependent loads where `lower` takes 31.  Every lane of the wave must
-// call it with the same arguments; the result is the same in every lane, and lies in [lo, hi] whatever `a` holds.
-template <class T>
-__device__ inline int32_t wave_lower(const T* __restrict__ a, int32_t lo, int32_t hi, T x, int lane) {
-    while (lo < hi) {
-        const int64_t step = ((int64_t)hi - lo + WAVE - 1) / WAVE;
-        const int64_t at = lo + lane * step;
-        const int below = __popcll(__ballot(at < hi && a[at] < x));    // (ascending: the probes below x are the first `below`)
-        if (below == 0) return lo;
-        const int64_t last = lo + (below - 1) * step;                   // < hi: that probe was made
-        lo = (int32_t)(last + 1);
-        hi = (int32_t)(last + step < hi ? last + step : hi);
-    }
-    return lo;
-}
+// (the same by a whole wave, six dependent loads for 2^31 elements where `lower` takes 31: wave_lower of blend_rows.h)
 
 __global__ __launch_bounds__(TPB) void blend_kernel(Rows in, Tables tb, const float* __restrict__ weights, int32_t* __restrict__ status) {
     __shared__ float tile[CHUNK];

@@ -760,3 +760,4 @@ from .baseline import MarkovBaseline  # noqa: E402,F401
 from .prior import MarkovPrior  # noqa: E402,F401
 from .geoprior import DistancePrior  # noqa: E402,F401
 from .ctxprior import ContextPrior  # noqa: E402,F401
+from .visitprior import VisitPrior  # noqa: E402,F401

@@ -190,7 +190,7 @@ class Tuned:
 
 
 class Prior(Tuned):
-    """What MarkovPrior, geoprior.DistancePrior and ctxprior.ContextPrior are: tables on one device, one weight per name of WEIGHTS
+    """What MarkovPrior, geoprior.DistancePrior, ctxprior.ContextPrior and visitprior.VisitPrior are: tables on one device, one weight per name of WEIGHTS
     and a status word, blended into [G, V] scores by one launch -- the interface the loops and Stack use of any prior.
 
     weights                f32 [n_weights] on the device, in WEIGHTS' order; written by set_weights only
@@ -370,7 +370,7 @@ class Stack(Tuned):
     """One or more priors blended in the order given, behind the interface the loops use of any prior (EvalLoop / PredictLoop,
     Graphormer.metric_step / recommend_step): prior.Stack(mb.prior(), mb.distance_prior(pair_bins)).
 
-    priors      the members, a tuple: any Prior (MarkovPrior, geoprior.DistancePrior, ctxprior.ContextPrior), or anything with their
+    priors      the members, a tuple: any Prior (MarkovPrior, geoprior.DistancePrior, ctxprior.ContextPrior, visitprior.VisitPrior), or anything with their
                 interface
     WEIGHTS     the members' names concatenated, e.g. ("user", "transition", "popularity", "distance"); no name twice
     n_weights   len(WEIGHTS): the width of a weights row (blend(weights=), EvalLoop(prior_weights=), tune's grid)

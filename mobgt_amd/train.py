@@ -1453,10 +1453,13 @@ class EvalLoop(_FrozenModelLoop):
     prior may also be a geoprior.DistancePrior (mb.distance_prior(pair_bins): a fitted distance-decay table, the rule in
     geoprior.py's docstring, the same anchor), a ctxprior.ContextPrior (data.ContextPrior.fit(ds, train): the category-transition
     and time-of-day tables, the rule in ctxprior.py's docstring, the same anchor, its category and its slot read from batch.cat
-    and batch.time) or a prior.Stack of several priors, blended in the order given, one launch each.
+    and batch.time), a visitprior.VisitPrior (data.VisitPrior.fit(ds, train): how often and how recently batch.user has been at
+    each POI, the rule in visitprior.py's docstring, no anchor) or a prior.Stack of several priors, blended in the order given,
+    one launch each.
 
     prior_weights: a sweep, [L, prior.n_weights] rows of prior.WEIGHTS -- (user, transition, popularity) for a MarkovPrior,
-    (distance,) for a DistancePrior, (category, time) for a ContextPrior, the members' names concatenated for a Stack --
+    (distance,) for a DistancePrior, (category, time) for a ContextPrior, (visits, recency) for a VisitPrior, the members' names
+    concatenated for a Stack --
     1 <= L <= 16.  Every batch is encoded ONCE;
     for each row the scores are blended out of place into one scratch [batch_size, V] with that row's weights and ranked into
     an accumulator of the row's own; run() returns the list of the L dicts, each what a loop with those weights returns.  The
