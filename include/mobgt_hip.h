@@ -222,7 +222,15 @@ int mobgt_hop_table_bwd(const float* d_table, const float* edge_encoder, const f
  * work     : scratch, mobgt_spd_workspace_bytes(G, N) bytes (272 < N <= 1088: per-row publication flags and rows of
  *            the multi-workgroup Floyd-Warshall; zeroed by the call itself)
  * Counts above 252 saturate the uint8 hop feature (the reference's edge tables have 128 rows).
+ * G <= 0, N <= 0, N > 32000, D <= 0 or D > MOBGT_SPD_MAX_D: MOBGT_EBADDIM before any launch -- a refused call reads no
+ * pointer and writes nothing.
+ * Dispatch by N: one workgroup per graph with M in LDS up to MOBGT_SPD_LDS_MAX_N; MOBGT_SPD_SPLIT_PARTS workgroups per
+ * graph up to MOBGT_SPD_SPLIT_MAX_N when `work` is given; one workgroup per graph out of global memory otherwise.
  */
+#define MOBGT_SPD_LDS_MAX_N 272     /* 272 * 272 * 2 B = 144.5 KiB of the 160 KiB LDS */
+#define MOBGT_SPD_SPLIT_MAX_N 1088  /* ceil(N / 16) rows x N x 2 B + one row <= 160 KiB */
+#define MOBGT_SPD_SPLIT_PARTS 16
+#define MOBGT_SPD_MAX_D 32
 int64_t mobgt_spd_workspace_bytes(int G, int N);
 /* Bound (in 100 MHz wall-clock ticks; < 0 restores the default, 200 ms) on how long a workgroup of the multi-workgroup
  * Floyd-Warshall waits for a row another workgroup publishes before its graph is handed to the single-workgroup redo
@@ -247,8 +255,8 @@ int mobgt_collate_finish(const int32_t* x, const int32_t* n_nodes, const int16_t
  *   mobgt_floyd_warshall  <- graphormer/algos.pyx:9-54   adj [n,n] int64 (non-zero = edge) -> M, path [n,n] int64
  *   mobgt_gen_edge_input  <- graphormer/algos.pyx:65-96  path [n,n] int64 (ANY path matrix), edge_feat [n,n,F] int64
  *                            -> out [n,n,max_dist,F] float32, -1 fill.  *err_flag (device int) is set non-zero
- *                            when a path has more hops than max_dist (the reference raises IndexError) or the
- *                            path matrix does not terminate.
+ *                            when a path has more hops than max_dist (the reference raises IndexError; max_dist = 0
+ *                            included, where `out` is empty and never touched) or the path matrix does not terminate.
  * `work` for mobgt_floyd_warshall: mobgt_floyd_warshall_workspace_bytes(n) bytes of device scratch.
  */
 int64_t mobgt_floyd_warshall_workspace_bytes(int n);

@@ -18,8 +18,8 @@ namespace {
 
 constexpr int UNREACH = 510;
 constexpr int FW_THREADS = 1024;
-constexpr int LDS_M_MAX_N = 272;          // 272*272*2 B = 144.5 KiB of the 160 KiB LDS
-constexpr int MAXD = 32;
+constexpr int LDS_M_MAX_N = MOBGT_SPD_LDS_MAX_N;      // 272*272*2 B = 144.5 KiB of the 160 KiB LDS
+constexpr int MAXD = MOBGT_SPD_MAX_D;
 
 template <bool IN_LDS>
 __global__ __launch_bounds__(FW_THREADS) void fw_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ n_nodes,
@@ -97,9 +97,9 @@ __global__ __launch_bounds__(FW_THREADS) void fw_kernel(const int32_t* __restric
 // published row and of its flag is an agent-scope (sc1, write-through) store, drained (s_waitcnt vmcnt(0) in
 // every storing wave + workgroup barrier) before the flag is raised; every load of the flag and of the row is
 // an agent-scope (sc1) load.  A release/acquire pair per step (L2 write-back + invalidate) cost ~15 us x N steps.
-constexpr int FW_PARTS = 16;
+constexpr int FW_PARTS = MOBGT_SPD_SPLIT_PARTS;
 constexpr int FW_SPLIT_THREADS = 512;
-constexpr int FW_SPLIT_MAX_N = 1088;     // ceil(N/16) rows x N x 2 B + one row <= 160 KiB
+constexpr int FW_SPLIT_MAX_N = MOBGT_SPD_SPLIT_MAX_N;     // ceil(N/16) rows x N x 2 B + one row <= 160 KiB
 // A workgroup waits for rows other workgroups publish.  Launches are sized to the device's resident capacity, but
 // nothing guarantees that capacity while other streams (RCCL, a second graph, another process) hold CUs or LDS: a
 // waiter whose producer cannot be scheduled would spin forever.  Every wait is therefore bounded in WALL time
@@ -322,7 +322,7 @@ extern "C" int mobgt_spd_batched(const int32_t* counts, const int32_t* n_nodes, 
                                  int16_t* rel_pos, uint8_t* edge_input, int16_t* in_degree, int16_t* out_degree,
                                  void* work, int G, int N, int D, void* stream) {
     (void)work;
-    if (G <= 0 || N <= 0 || D < 0 || D > MAXD || N > 32000) return MOBGT_EBADDIM;
+    if (G <= 0 || N <= 0 || D <= 0 || D > MAXD || N > 32000) return MOBGT_EBADDIM;     // before any launch: nothing is written
     hipStream_t st = (hipStream_t)stream;
     if (N <= LDS_M_MAX_N) {
         const size_t shm = (size_t)N * N * sizeof(int16_t);
@@ -378,12 +378,8 @@ extern "C" int mobgt_spd_batched(const int32_t* counts, const int32_t* n_nodes, 
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    if (D > 0) {
-        const dim3 grid((N * N + 255) / 256, G);
-        hipLaunchKernelGGL(edge_path_kernel, grid, dim3(256), 0, st, counts, n_nodes, spd, path, rel_pos, edge_input, N, D);
-    } else {
-        return MOBGT_EBADDIM;
-    }
+    const dim3 grid((N * N + 255) / 256, G);
+    hipLaunchKernelGGL(edge_path_kernel, grid, dim3(256), 0, st, counts, n_nodes, spd, path, rel_pos, edge_input, N, D);
     return (int)hipGetLastError();
 }
 
@@ -516,8 +512,9 @@ extern "C" int mobgt_gen_edge_input(int max_dist, const int64_t* path, const int
     const int64_t total = (int64_t)n * n * max_dist * F;
     hipError_t e = hipMemsetAsync(err_flag, 0, sizeof(int), st);
     if (e != hipSuccess) return (int)e;
-    if (total == 0) return 0;
-    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, total, -1.0f);
+    // max_dist == 0: nothing to fill, but a walk of even one hop is still "more hops than max_dist" (the reference's bounds
+    // check raises on its first write); the kernel reports it without touching `out`
+    if (total > 0) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, total, -1.0f);
     int cap = max_dist + 1 < n + 1 ? max_dist + 1 : n + 1;      // a simple path has at most n-1 hops
     if (cap < 2) cap = 2;
     if (cap > 510) cap = 511;

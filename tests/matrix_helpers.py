@@ -1,5 +1,6 @@
-"""Device-side helpers shared by the kernel matrices (tests/test_gpu_maskgemm_matrix.py, tests/test_gpu_gcn_matrix.py): staging
-of NumPy operands, destinations inside sentinel-filled guard buffers, strided operands inside wider buffers of 1000s."""
+"""Device-side helpers shared by the kernel matrices (tests/test_gpu_maskgemm_matrix.py, tests/test_gpu_gcn_matrix.py,
+tests/test_gpu_spd_matrix.py): staging of NumPy operands, destinations inside sentinel-filled guard buffers (float matrices:
+Guarded; integer arrays and bit patterns of any shape: GuardedFlat), strided operands inside wider buffers of 1000s."""
 import numpy as np
 import torch
 
@@ -41,6 +42,40 @@ class Guarded:
 
     def untouched(self):
         return bool((self.big == self.sent).all())
+
+
+# what no correct integer result holds; a float destination starts as a quiet NaN with a payload, compared as its int32 pattern
+POISON = {torch.uint8: 0xA5, torch.int16: -12345, torch.int32: -1234567, torch.int64: -1234567, torch.float32: 0x7FC5A5A5}
+
+
+class GuardedFlat:
+    """`shape` elements of an integer dtype (or f32) inside a poison-filled 1-d buffer with `guard` elements on either side (a
+    multiple of 16 bytes, so the view keeps the allocation's alignment).  `init`: a NumPy array the view starts as."""
+
+    def __init__(self, shape, dtype, guard=64, init=None):
+        self.shape = tuple(int(s) for s in np.atleast_1d(shape))
+        self.count = int(np.prod(self.shape, dtype=np.int64))
+        self.guard, self.dtype = guard, dtype
+        self.raw = torch.int32 if dtype == F32 else dtype
+        self.poison = POISON[dtype]
+        self.buf = torch.full((self.count + 2 * guard,), self.poison, dtype=self.raw, device=DEV)
+        self.view = self.buf[guard:guard + self.count]
+        if init is not None:
+            self.view.copy_(dev(np.ascontiguousarray(init).reshape(-1)).view(self.raw))
+
+    def ptr(self):
+        return self.view.data_ptr()
+
+    def result(self):
+        """The view on the host in its shape (a float view as int32 patterns); asserts that both guards still hold the poison."""
+        b = self.buf.cpu().numpy()
+        g = self.guard
+        assert (b[:g] == self.poison).all(), "an element in front of the array was written"
+        assert (b[g + self.count:] == self.poison).all(), "an element behind the array was written"
+        return b[g:g + self.count].reshape(self.shape)
+
+    def untouched(self):
+        return bool((self.buf == self.poison).all())
 
 
 def place(a, dtype=F32, off=4, pad=4, fill=1000.0, view=True):

@@ -11,7 +11,8 @@ from mobgt_amd import _baseline, _lib, _prefixes, baseline, layer_plan, ops, pre
 
 C = _lib.CONSTANTS
 VALUES = {"MOBGT_CHAIN_BIG_ROWS": 4096, "MOBGT_BIAS_LONG_PAIRS": 1 << 20, "MOBGT_HOP_DMAX": 20, "MOBGT_SKINNY_MAX_G": 16,
-          "MOBGT_SKINNY_MAX_K": 512, "MOBGT_SKINNY_MFMA_MAX_K": 448, "MOBGT_SKINNY_MFMA_K_STEP": 64, "MOBGT_TOPK_MAX_K": 64}
+          "MOBGT_SKINNY_MAX_K": 512, "MOBGT_SKINNY_MFMA_MAX_K": 448, "MOBGT_SKINNY_MFMA_K_STEP": 64, "MOBGT_TOPK_MAX_K": 64,
+          "MOBGT_SPD_LDS_MAX_N": 272, "MOBGT_SPD_SPLIT_MAX_N": 1088, "MOBGT_SPD_SPLIT_PARTS": 16, "MOBGT_SPD_MAX_D": 32}
 
 
 def test_the_header_declares_the_limits_and_the_cluster_size_entry_point():
@@ -27,6 +28,24 @@ def test_python_names_are_the_header_constants():
     assert (ops.BIAS_LONG_PAIRS, ops.HOP_DMAX) == (C["MOBGT_BIAS_LONG_PAIRS"], C["MOBGT_HOP_DMAX"])
     assert prefixes.DEVICE_MAX_L == _prefixes.MAX_L == _prefixes.CONSTANTS["MOBGT_PREFIXES_MAX_L"]
     assert baseline.DEVICE_MAX_L == _baseline.MAX_L == _baseline.CONSTANTS["MOBGT_BASELINE_MAX_L"]
+
+
+def test_the_shortest_path_dispatch_uses_the_header_constants():
+    """csrc/spd.hip takes its thresholds from the header (no literal of its own), the matrix's reference reads the same numbers,
+    and the LDS they stand for fits: N^2 int16 in one CU's 160 KiB, and ceil(N / parts) + 1 rows of the padded pitch."""
+    import os
+    import re
+    import spd_reference as sr
+    src = open(os.path.join(_lib.CSRC, "spd.hip")).read()
+    for local, name in (("LDS_M_MAX_N", "MOBGT_SPD_LDS_MAX_N"), ("FW_SPLIT_MAX_N", "MOBGT_SPD_SPLIT_MAX_N"),
+                        ("FW_PARTS", "MOBGT_SPD_SPLIT_PARTS"), ("MAXD", "MOBGT_SPD_MAX_D")):
+        assert re.search(rf"constexpr int {local} = {name};", src), local
+    names = ("LDS_MAX_N", "SPLIT_MAX_N", "SPLIT_PARTS", "MAX_D")
+    assert tuple(getattr(sr, n) for n in names) == tuple(C["MOBGT_SPD_" + n] for n in names)
+    lds = 160 * 1024
+    assert sr.LDS_MAX_N ** 2 * 2 == 147968 <= lds
+    split = lambda N: ((N + sr.SPLIT_PARTS - 1) // sr.SPLIT_PARTS + 1) * ((N + 7) & ~7) * 2      # noqa: E731
+    assert split(sr.SPLIT_MAX_N) == 150144 <= 152 * 1024 <= lds
 
 
 def _stand_in(*shape):
