@@ -113,4 +113,55 @@ __device__ __forceinline__ void sgemm_splitk_tile(const SgemmParams& p, const in
     __syncthreads();                                   // (the partial tiles are free again: a workgroup may run tile after tile)
 }
 
+// One 16 x 16 output tile of sgemm.hip's sgemm_kernel<1, B_NK, VEC, EXT> with a transposed bf16 result only (p.ct, p.ct_scale; no
+// bias, no activation, no mask on A), run by ONE wave with every operand of its K <= 16 * NK_MAXS columns requested before the
+// first product: a passenger of another launch has no neighbours that hide a three-slot ring's round trips.  The MFMAs run in
+// that kernel's order (k-steps ascending, x y z w inside a step), so the two agree bit for bit.  [N,K] operand, rows of A and B
+// 16-byte aligned, K % 16 == 0.  `row_idx` (optional, [M]): a row of A whose entry is negative or `skip` counts as zeros (a pad
+// row whose values nobody vouches for); the entry is requested with the operands and applied as a bit mask, not as a branch.
+constexpr int NK_MAXS = 12;
+template <typename TI>
+__device__ __forceinline__ void sgemm_nk_tile_burst(const SgemmParams& p, const int tile, const TI* row_idx, const int64_t skip) {
+    const int lane = threadIdx.x & 63;
+    const int i = lane & 15, kq = lane >> 4;
+    const int tiles_n = (p.N + 15) / 16;
+    const int m0 = (tile / tiles_n) * 16, n0 = (tile % tiles_n) * 16;
+    const int ra = min(m0 + i, p.M - 1);
+    const float* arow = p.A + (int64_t)ra * p.lda + 4 * kq;
+    const float* brow = p.B + (int64_t)min(n0 + i, p.N - 1) * p.ldb + 4 * kq;       // clamped: those products are never stored
+    const int nsteps = p.K / 16;
+    const TI ri_raw = row_idx ? row_idx[ra] : (TI)0;                                 // (widened below, behind the other requests)
+    float4 a_r[NK_MAXS], b_r[NK_MAXS];
+#pragma unroll
+    for (int s = 0; s < NK_MAXS; ++s) {
+        const int sc = min(s, nsteps - 1);                                          // (past K: a repeated load that is not multiplied)
+        a_r[s] = *reinterpret_cast<const float4*>(arow + 16 * sc);
+        b_r[s] = *reinterpret_cast<const float4*>(brow + 16 * sc);
+    }
+    float sc_r[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) sc_r[v] = p.ct_scale ? p.ct_scale[min(m0 + 4 * kq + v, p.M - 1)] : 1.f;
+    const int64_t ri = (int64_t)ri_raw;
+    const uint32_t keep = (ri < 0 || ri == skip) ? 0u : 0xFFFFFFFFu;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < NK_MAXS; ++s) {
+        if (s < nsteps) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(__float_as_uint(a_r[s].x) & keep), b_r[s].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(__float_as_uint(a_r[s].y) & keep), b_r[s].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(__float_as_uint(a_r[s].z) & keep), b_r[s].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(__float_as_uint(a_r[s].w) & keep), b_r[s].w, acc, 0, 0, 0);
+        }
+    }
+    const int c = n0 + i;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const int r = m0 + 4 * kq + v;
+        if (r < p.M && c < p.N) {
+            const float o = acc[v] + 0.f;                                           // (sgemm_kernel: acc + bias, bias absent)
+            p.ct[(int64_t)c * p.ldt + r] = (bf16_t)(p.ct_scale ? o * sc_r[v] : o);
+        }
+    }
+}
+
 }  // namespace mobgt_sgemm

@@ -36,7 +36,15 @@ _ROWS = (
          "input's one-launch backward (off: it finishes its own backward); no workgroup waits for another, so safe_forms keeps it"),
     Form("l0_token_host_eager", "MOBGT_L0_TOKEN_HOST_EAGER", False, "l0_token_host outside a graph capture as well (off: only a step "
          "that is being captured defers; an eager step is bound by the host, gains nothing and keeps its launch list)"),
+    Form("scatter_burst", "MOBGT_NO_SCATTER_BURST", True, "short batches, fused distance GCN: the encoder input's gradients are scattered "
+         "in one burst per position, the distance GCN's compact table written instead of scattered (off: job after job); no workgroup "
+         "waits for another, so safe_forms keeps it"),
+    Form("scatter_burst_eager", "MOBGT_SCATTER_BURST_EAGER", False, "scatter_burst outside a graph capture as well (off: only a step "
+         "that is being captured takes it; an eager step keeps its launch list)"),
     # ---- jobs that ride in another launch (off: a launch of their own)
+    Form("dist_gu_ride", "MOBGT_NO_DIST_GU_RIDE", True, "the distance GCN's backward product gu, in the burst scatter's launch (needs "
+         "scatter_burst); no workgroup waits for another, so safe_forms keeps it"),
+    Form("dist_gu_ride_eager", "MOBGT_DIST_GU_RIDE_EAGER", False, "dist_gu_ride outside a graph capture as well (with scatter_burst_eager)"),
     Form("pack_passenger", "MOBGT_NO_PACK_PASSENGER", True, "the layers' weight pack, in the next front launch"),
     Form("front_passengers", "MOBGT_NO_FRONT_PASSENGERS", True, "hop table forward and node-feature indices, in the category GCN's forward"),
     Form("bias_bwd_passenger", "MOBGT_NO_BIAS_BWD_PASSENGER", True, "short batches: the bias tables' backward, in the category GCN's backward"),

@@ -182,7 +182,10 @@ _XT_WORK = {}
 def xt_workspace(device, P, N, slot=0):
     """The bitmask product's operand buffer, bf16 [N, roundup(P, 128)], kept per (device, P, N, slot) and ZERO beyond column P
     (the kernels that fill it write columns < P only): a producer that writes its result there transposed
-    (ops.bias_act(yt=), ops.small_gemm(ct=)) saves the transpose launch in front of `mask_gemm`."""
+    (ops.bias_act(yt=), ops.small_gemm(ct=)) saves the transpose launch in front of `mask_gemm`.
+    Slot 2 is _DistGcnFn's gu and RESERVED for it over a stretch of the backward: with forms "dist_gu_ride" the encoder input's
+    scatter launch fills it and mask_rows_bwd reads it only after the category GCN's backward has run in between -- no other
+    user may take slot 2 (of any shape: a new user takes a new slot number)."""
     key = (str(device), int(P), int(N), int(slot))
     t = _XT_WORK.get(key)
     if t is None:
@@ -592,6 +595,9 @@ class _DistGcnFn(torch.autograd.Function):
         # the last layer's output as the four partial tables of its column blocks: the first carries the gradient (d out /
         # d parts[q] = 1 for every q), the other three are constants to autograd
         p0, rest = parts[0], parts[1:]
+        # the backward's gu product depends on nothing but d(out), which the encoder input's scatter reads anyway: parked for that
+        # launch (ops.park_dist_gu_job; forms "dist_gu_ride"), run by the backward below when nobody took it
+        ctx.gu_job = ops.park_dist_gu_job(p0, w2, rs_rows, xt_workspace(dev, R, 64, slot=2), R, NO) if any(ctx.needs_input_grad) else None
         ctx.mark_non_differentiable(rest)
         ctx.set_materialize_grads(False)             # (no zero tensor for `rest`'s absent gradient)
         return p0, rest
@@ -602,6 +608,7 @@ class _DistGcnFn(torch.autograd.Function):
         from .ops import _p, _stream
         ax_pad, y0, t1, y1, u, rs_rows, rows, w0, w1, w2, mask_t, scale = ctx.saved_tensors
         k_w0, k_b0, k_w1, k_b1, k_w2, k_b2 = ctx.sinks
+        rode = ops.take_dist_gu_job(ctx.gu_job)            # (also drops the job if it is still parked: nothing outlives this backward)
         if g is None:
             return (None,) * 16
         g = g.contiguous()
@@ -613,7 +620,8 @@ class _DistGcnFn(torch.autograd.Function):
         db2 = dst(k_b2, w2.shape[1])
         dW2 = ops.linear_wgrad_masked(u, g, db=db2, db_of_x=True, leaf=True, dw=k_w2[:] if k_w2 is not None else None)
         gut = xt_workspace(dev, R, 64, slot=2)
-        ops.small_gemm(g, w2, b_is_nk=True, ct=(gut, rs_rows, True))                 # (rs[rows] * (g W2^T))^T, bf16
+        if not rode:                                                                 # (else: the scatter's launch filled gut)
+            ops.small_gemm(g, w2, b_is_nk=True, ct=(gut, rs_rows, True))             # (rs[rows] * (g W2^T))^T, bf16
         dy1 = torch.empty(P, 64, dtype=torch.float32, device=dev)
         dtt = xt_workspace(dev, P, 16, slot=1)
         _lib.call("mobgt_mask_rows_bwd", _p(mask_t), mask_t.shape[1], _p(rows), _p(gut), gut.stride(0), _p(y1),
@@ -704,6 +712,8 @@ class GCN(nn.Module):
                 p0, rest = _DistGcnFn.apply(ax_in, mask_adj.mask, mask_adj.mask_t, mask_adj.scale, rows, g0.weight, g0.bias,
                                             g1.weight, g1.bias, g2.weight, g2.bias, float(self.leaky_relu.negative_slope),
                                             float(p_drop), seed, seed_dev, 0x2000 + g2.out_features)
+            if not p0.requires_grad:         # (a forward without gradients: no backward will come for the gu product it parked)
+                STEP.dist_gu_job = None
             if parts_ok:                 # the caller adds the partial tables itself (model_fqandtoyo.node_features: in its gather)
                 p0._mobgt_parts = tuple(rest.unbind(0))
                 return p0

@@ -395,12 +395,12 @@ class Graphormer(nn.Module):
         ops.token_fwd_deferral(one_launch and first_qkv is not None and self.act_dtype == torch.bfloat16 and C == 192 and Wp + Wt == 160)
         try:
             return self._node_features_tail(batched_data, G, N, poidist, catemb, real, one_launch, first_qkv, Wp, Wt, Wc, C,
-                                            poi_idx, time_idx, cat_idx, pos_idx, zero_idx, in_deg, out_deg)
+                                            poi_idx, time_idx, cat_idx, pos_idx, zero_idx, in_deg, out_deg, rows_only)
         finally:
             ops.token_fwd_deferral(False)
 
     def _node_features_tail(self, batched_data, G, N, poidist, catemb, real, one_launch, first_qkv, Wp, Wt, Wc, C,
-                            poi_idx, time_idx, cat_idx, pos_idx, zero_idx, in_deg, out_deg):
+                            poi_idx, time_idx, cat_idx, pos_idx, zero_idx, in_deg, out_deg, rows_only=False):
         f4 = self.embed_fuse_model4
         if one_launch:
             # every gathered row of :1259-1298 in ONE launch: [poi ; time] -> pt, the category row -> the trailing columns of
@@ -413,7 +413,9 @@ class Graphormer(nn.Module):
                  (catemb, cat_idx, 1, Wp + Wt, False, None),
                  (self.fre_embed_model.weight, zero_idx, 2, 0, False, 0), (self.in_degree_encoder.weight, in_deg, 2, 0, True, 0),
                  (self.out_degree_encoder.weight, out_deg, 2, 0, True, 0), (self.pos_embed.pe, pos_idx, 2, 0, True, None)],
-                [Wp + Wt, Wp + Wt + Wc, C])
+                [Wp + Wt, Wp + Wt + Wc, C],
+                # (the fused distance GCN's compact per-batch table: row p belongs to position p -- gather_indices, ops.node_index)
+                identity=0 if (rows_only and hasattr(poidist, "_mobgt_parts") and poidist.shape[0] == G * N) else None)
             # fuse2 (:1268) writes straight into the leading columns of fuse4's input (:1269): no torch.cat
             f2 = ops.linear_splitk(pt, self.embed_fuse_model2.fuse_embed.weight, self.embed_fuse_model2.fuse_embed.bias,
                                    self.act_dtype == torch.bfloat16, slope=self.embed_fuse_model2.leaky_relu.negative_slope,

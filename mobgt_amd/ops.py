@@ -8,7 +8,7 @@ import math
 
 import torch
 
-from . import _lib, _tokhost, forms
+from . import _lib, _tokhost, _tokscatter, forms
 from ._lib import F32, BF16, I64, I32, I16, U8, check
 from .step_state import STEP
 
@@ -1431,7 +1431,7 @@ class _GatherMultiFn(torch.autograd.Function):
     caller fills them: FuseEmbeddings' first Linear writes its result next to the category rows)."""
 
     @staticmethod
-    def forward(ctx, spec, out_widths, n, *args):
+    def forward(ctx, spec, out_widths, n, identity, *args):
         tables, idx = args[:n], args[n:]
         R = idx[0].numel()
         dev = tables[0].device
@@ -1449,6 +1449,15 @@ class _GatherMultiFn(torch.autograd.Function):
         else:
             launch()
         ctx.idx, ctx.spec, ctx.n = idx, spec, n
+        # the backward as one burst per position (forms "scatter_burst"; libmobgt_tokscatter): decided here, like every deferral of the
+        # step -- a step that is being captured takes it, an eager step is bound by the host and keeps its launch list unless
+        # forms "scatter_burst_eager" asks.  `identity`: the job whose table is the position list itself (see embed_gather_multi)
+        ctx.identity = identity if (identity is not None and tables[identity].shape[0] == R and not spec[identity][2]) else None
+        # (the model names an identity job only in the configuration the form is for -- fq variant, the one-launch encoder input,
+        #  the fused distance GCN's compact table, model_fqandtoyo._node_features_tail -- so a VALID identity job stands for those
+        #  conditions; any other caller keeps mobgt_embed_gather_multi's backward)
+        ctx.burst = (ctx.identity is not None and forms.on("scatter_burst")
+                     and (torch.cuda.is_current_stream_capturing() or forms.on("scatter_burst_eager")))
         ctx.ptrs = [t.data_ptr() for t in tables]
         ctx.shapes = [t.shape for t in tables]
         ctx.sinks = [grad_sink(t) for t in tables]          # (a table that is a trained parameter: its slice of the flat gradient)
@@ -1464,10 +1473,18 @@ class _GatherMultiFn(torch.autograd.Function):
             if g is not None and (g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16 or g.dtype != torch.float32):
                 g = g.float().contiguous()
             gbuf.append(g)
-        grads = [(ctx.sinks[t][:] if ctx.sinks[t] is not None else zeros_f32(tuple(sh), dev))
-                 if (ctx.needs_input_grad[3 + t] and gbuf[spec[t][0]] is not None) else None for t, sh in enumerate(ctx.shapes)]
-        jobs = [t for t in range(n) if grads[t] is not None]
-        if jobs:
+        wanted = [bool(ctx.needs_input_grad[4 + t] and gbuf[spec[t][0]] is not None) for t in range(n)]
+        jobs = [t for t in range(n) if wanted[t]]
+        burst = (ctx.burst and 1 <= len(jobs) <= _tokscatter.MAX_JOBS and ctx.idx[0].dtype in (torch.int64, torch.int32)
+                 and all(ctx.idx[t].dtype == ctx.idx[0].dtype and ctx.shapes[t][1] <= _tokscatter.MAX_WIDTH for t in jobs))
+        # the identity job's rows are WRITTEN by the burst launch, pads as zeros: no zero-fill (a table that is no parameter's)
+        ident = ctx.identity if (burst and ctx.identity in jobs and ctx.sinks[ctx.identity] is None) else None
+        grads = [(ctx.sinks[t][:] if ctx.sinks[t] is not None else
+                  torch.empty(tuple(sh), dtype=torch.float32, device=dev) if t == ident else zeros_f32(tuple(sh), dev))
+                 if wanted[t] else None for t, sh in enumerate(ctx.shapes)]
+        if jobs and burst:
+            _scatter_burst(ctx, jobs, grads, gbuf, ident, R)
+        elif jobs:
             m = len(jobs)
             ci, i64, vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
             # a row-0 gradient another node left for one of these tables (assemble_tokens: the graph token's pe[0])
@@ -1482,13 +1499,62 @@ class _GatherMultiFn(torch.autograd.Function):
                 (ci * m)(*[spec[t][1] for t in jobs]), None, (vp * m)(*[gbuf[spec[t][0]].data_ptr() for t in jobs]),
                 (i64 * m)(*[gbuf[spec[t][0]].stride(0) for t in jobs]), R, _IT[ctx.idx[0].dtype], 1, _p(extra), extra_job,
                 _stream())
-        return (None, None, None, *grads, *([None] * n))
+        return (None, None, None, None, *grads, *([None] * n))
 
 
-def embed_gather_multi(jobs, out_widths):
+def _scatter_burst(ctx, jobs, grads, gbuf, ident, R):
+    """_GatherMultiFn.backward as mobgt_tokscatter_bwd (include/mobgt_tokscatter.h): every index, then every gradient piece, then
+    every atomic of a position; the identity job written, not scattered; and, when the distance GCN parked its gu product
+    (STEP.dist_gu_job, forms "dist_gu_ride") and the identity job is that GCN's output, the product as passenger workgroups."""
+    spec, m = ctx.spec, len(jobs)
+    ci, i64, vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+    extra, extra_job = None, 0
+    for k, t in enumerate(jobs):
+        pend = _ROW0_PENDING.pop(ctx.ptrs[t], None)
+        if pend is not None:
+            extra, extra_job = pend, k
+    ride = (None, 0, None, None, 0, 0)
+    job = STEP.dist_gu_job
+    if job is not None and ident is not None:
+        g, coff, no = gbuf[spec[ident][0]], spec[ident][1], ctx.shapes[ident][1]
+        if (job["out_ptr"] == ctx.ptrs[ident] and job["R"] == R and job["NO"] == no and no % 16 == 0 and no <= _tokscatter.RIDE_MAX_K
+                and job["w2"].shape[0] <= _tokscatter.RIDE_MAX_N and (g.data_ptr() + 4 * coff) % 16 == 0 and g.stride(0) % 4 == 0
+                and job["w2"].is_contiguous() and job["w2"].data_ptr() % 16 == 0 and job["gut"].stride(0) >= R):
+            STEP.dist_gu_job = None                           # taken: _DistGcnFn.backward finds gut filled and skips its launch
+            job["taken"] = True
+            ride = (_p(job["w2"]), job["w2"].stride(0), _p(job["rs_rows"]), _p(job["gut"]), job["gut"].stride(0), job["w2"].shape[0])
+    _tokscatter.launch("mobgt_tokscatter_bwd",
+        m, (vp * m)(*[grads[t].data_ptr() for t in jobs]), (vp * m)(*[ctx.idx[t].data_ptr() for t in jobs]),
+        (i64 * m)(*[spec[t][3] for t in jobs]), (ci * m)(*[ctx.shapes[t][1] for t in jobs]), (ci * m)(*[spec[t][1] for t in jobs]),
+        (vp * m)(*[gbuf[spec[t][0]].data_ptr() for t in jobs]), (i64 * m)(*[gbuf[spec[t][0]].stride(0) for t in jobs]), R,
+        _IT[ctx.idx[0].dtype], _p(extra), extra_job, jobs.index(ident) if ident is not None else -1, *ride, _stream())
+
+
+def take_dist_gu_job(job):
+    """_DistGcnFn.backward asks: True when the scatter's launch carried `job` (its gut is filled).  Whatever is still parked is
+    dropped either way -- nothing outlives the backward of the forward that parked it."""
+    if STEP.dist_gu_job is job:
+        STEP.dist_gu_job = None
+    return bool(job is not None and job.get("taken"))
+
+
+def park_dist_gu_job(out, w2, rs_rows, gut, R, NO):
+    """_DistGcnFn.forward leaves its backward's gu = (rs[rows] (g W2^T))^T for the encoder input's scatter (forms "dist_gu_ride":
+    in a step that is being captured, or with "dist_gu_ride_eager").  -> the job, or None."""
+    STEP.dist_gu_job = None
+    if not (forms.on("dist_gu_ride") and forms.on("scatter_burst")
+            and (torch.cuda.is_current_stream_capturing() or (forms.on("dist_gu_ride_eager") and forms.on("scatter_burst_eager")))):
+        return None
+    STEP.dist_gu_job = job = dict(out_ptr=out.data_ptr(), w2=w2.detach(), rs_rows=rs_rows, gut=gut, R=int(R), NO=int(NO))
+    return job
+
+
+def embed_gather_multi(jobs, out_widths, identity=None):
     """jobs = [(table, index, out, coff, accum, padding_idx)]: table[index] -> columns [coff, coff + W) of output `out`
     (copied, or added when `accum`; accum = 2: this table's row is added to the PREVIOUS job's before that job stores --
     a constant partial table of the same shape, no gradient) -- all in one launch each way.
+    `identity`: the number of a job whose table has one row per position and whose index is that position's own number, or
+    negative (ops.node_index's POI row with rows_only): its gradient is the matching columns of the output's, pads zeroed.
     -> list of [R, out_widths[o]] f32 tensors."""
     n = len(jobs)
     tabs = [j[0].float().contiguous() for j in jobs]
@@ -1499,7 +1565,7 @@ def embed_gather_multi(jobs, out_widths):
     for k, sp in enumerate(spec):
         assert sp[2] != 2 or (k > 0 and tabs[k].shape[1] == tabs[k - 1].shape[1] and not tabs[k].requires_grad
                               and (k < 4 or any(s_[2] != 2 for s_ in spec[k - 3:k]))), "fold job (at most three per gather)"
-    return list(_GatherMultiFn.apply(spec, tuple(out_widths), n, *tabs, *idx))
+    return list(_GatherMultiFn.apply(spec, tuple(out_widths), n, identity, *tabs, *idx))
 
 
 class _JoinColsFn(torch.autograd.Function):

@@ -16,6 +16,7 @@ FIELDS = (
     Field("grad_sinks", CARRIED, dict, "TrainStep (ops.set_grad_sinks): parameter address -> (weak parameter, gradient view); ops.grad_sink reads"),
     Field("sink_census", SWITCH, lambda: {"on": False, "cur": {}, "max": {}}, "train.used_parameters' dry run counts ops.grad_sink requests per forward"),
     Field("bias_bwd_job", PARKED, _none, "_BuildBiasFn.forward parks; the category GCN's backward launch, the side stream or its own backward takes"),
+    Field("dist_gu_job", PARKED, _none, "_DistGcnFn.forward parks (ops.park_dist_gu_job); the encoder input's burst scatter takes, or that node's own backward drops"),
     Field("front_on", SWITCH, bool, "the model's forward (ops.front_deferral) around the hop table and the node indices"),
     Field("front_hop", PARKED, _none, "_HopTableFn.forward parks; the category GCN's / stock front's forward launch or ops.flush_front takes"),
     Field("front_ni", PARKED, _none, "ops.node_index parks; the same launches take"),
